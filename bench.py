@@ -26,7 +26,17 @@ GPU) and exits with its status. One rank per GPU:
 --dry rehearses the launch and the rank logic on CPU (gloo, the engine's dry
 planner instead of a device): no GPU, timings are host planning only.
 
-Output: ONE JSON line on rank 0 (driver contract), including
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N
+steps and prints the result line: value, ms_per_step, the host enqueue time and
+the whole-step HBM fraction, all from the timed steps. `--dump-outputs DIR`
+also writes what the last timed step left in the cell streams (a fixed sample
+of each stream that holds cells) and the counts it returned as DIR/<name>.npy. Everything that
+takes runs of its own -- the CPU baseline, the profiled and the serialised
+passes behind the per-kernel roofline, the device constraint check, the device
+ingest of the input text, the timed reassembly of a row-sharded witness -- is
+behind `--full`.
+
+Output: ONE JSON line on rank 0 (driver contract), with --full including
   roofline     dominant kernel, from HIP events the engine records around each
                of its launches on its own stream during the timed steps
                (svdw_profile_*; filtered by --profile-prefix),
@@ -227,6 +237,48 @@ def gpu_only_chain(workload, N, M, P, LB):
     return None
 
 
+# ----------------------------------------------------------------- output dump
+DUMP_BLOCK = 512            # cells per sampled block
+DUMP_BLOCKS = 256           # blocks per stream: 131072 cells = 8 MB as float64 limbs
+
+
+def dump_blocks(total, stream):
+    """[(off, n)] of the cells of a `total`-cell stream that --dump-outputs
+    writes: the whole stream if it fits, else its first and last block and
+    seeded blocks between them (fixed per stream index and length)."""
+    if total <= DUMP_BLOCK * DUMP_BLOCKS:
+        return [(0, total)] if total else []
+    rs = np.random.RandomState(0x5EED + stream)
+    starts = rs.randint(0, total - DUMP_BLOCK + 1, size=DUMP_BLOCKS - 2)
+    starts = sorted(int(x) for x in starts) + [total - DUMP_BLOCK]
+    return [(0, DUMP_BLOCK)] + [(o, DUMP_BLOCK) for o in starts]
+
+
+def cells_as_f64(cells):
+    """(n, 4) uint64 canonical Fr cells -> (n, 8) float64: the eight 32-bit
+    limbs of each cell, least significant first (exact in float64)."""
+    return np.ascontiguousarray(cells).view("<u4").reshape(-1, 8).astype(np.float64)
+
+
+def dump_outputs(ctx, cnt, outdir):
+    """What the last step left for its caller: the counts it returned and the
+    advice / lookup cell streams of both phases (sampled, dump_blocks)."""
+    os.makedirs(outdir, exist_ok=True)
+    keys = sorted(cnt)
+    np.save(os.path.join(outdir, "counts.npy"), np.array([float(cnt[k]) for k in keys]))
+    streams = (("advice0", 0, False), ("lookup0", 0, True), ("advice1", 1, False), ("lookup1", 1, True))
+    for i, (name, ph, lk) in enumerate(streams):
+        total = ctx.lookup_len(ph) if lk else ctx.advice_len(ph)
+        get = ctx.lookups if lk else ctx.advice
+        path = os.path.join(outdir, name + ".npy")
+        if not total:                  # a stream the workload leaves empty (counts.npy says so):
+            if os.path.exists(path):   # no file, nor one left by an earlier run into this DIR
+                os.remove(path)
+            continue
+        cells = np.concatenate([get(ph, off, n) for off, n in dump_blocks(total, i)])
+        np.save(path, cells_as_f64(cells))
+
+
 # ----------------------------------------------------------------- CPU baseline
 def cpu_info():
     model = "unknown"
@@ -357,6 +409,14 @@ def main():
     ap.add_argument("--p", type=int, default=None, help="PRECISION_BITS (default 63 svd, 32 verify_mul)")
     ap.add_argument("--lb", type=int, default=19)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the timed steps: CPU baseline, per-kernel "
+                         "roofline passes, device constraint check, device ingest, timed "
+                         "reassembly (--shard rows); each can still be switched off below")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's counts and a fixed sample "
+                         "of its advice / lookup cell streams as DIR/<name>.npy (float64: the "
+                         "32-bit limbs of each cell); --gpus 1 on a device")
     ap.add_argument("--cpu-rows", type=int, default=128)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-child", default=None, help=argparse.SUPPRESS)
@@ -374,7 +434,7 @@ def main():
                     help="--shard rows: also time reassembling the witness after each step "
                          "(RCCL gather to rank 0 or all-gather), reported beside the "
                          "witness-only value as the `reassembly` record (auto: root in "
-                         "rows mode)")
+                         "rows mode with --full, else none)")
     ap.add_argument("--no-check", action="store_true",
                     help="skip the untimed device constraint check of the last witness")
     ap.add_argument("--no-ingest", action="store_true",
@@ -389,8 +449,15 @@ def main():
     if args.cpu_baseline_child is not None:
         print(json.dumps(cpu_baseline_run(json.loads(args.cpu_baseline_child))), flush=True)
         return 0
+    if args.dump_outputs is not None and (args.gpus != 1 or args.dry):
+        raise SystemExit("bench.py: --dump-outputs needs --gpus 1 and a device (no --dry)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus)
+    if not args.full:
+        # a plain run: the timed steps only
+        args.no_cpu_baseline = args.no_profile = args.no_check = args.no_ingest = True
+        if args.gather == "auto":
+            args.gather = "none"
 
     svd = args.workload == "svd"
     if args.warmup is None:
@@ -481,6 +548,8 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     host_ms = (t_issued - t0) / args.steps * 1e3
+    if args.dump_outputs is not None:
+        dump_outputs(ctx, cnt, args.dump_outputs)
     graph_stats = ctx.graph_stats() if profile and graph_vm else None
     prof_elapsed = None
     if profile:

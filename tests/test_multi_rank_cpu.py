@@ -61,10 +61,11 @@ def test_single_rank_reduce_is_identity():
 @pytest.mark.parametrize("extra", [[], ["--shard", "replicas"]])
 def test_bench_gpus_flag_launches_ranks(extra):
     """`bench.py --gpus 2` outside torch.distributed starts two ranks itself (a
-    torch.distributed.run child); --dry rehearses them on CPU (gloo + planner)."""
+    torch.distributed.run child); --dry rehearses them on CPU (gloo + planner);
+    --full for the timed reassembly of the row-sharded witness."""
     import json
     import subprocess
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry", "--full",
                         "--n", "32", "--steps", "2", "--warmup", "1"] + extra,
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
