@@ -22,6 +22,7 @@
 #include <set>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/svdw.h"
@@ -395,10 +396,125 @@ struct Stream {
     uint64_t nl = 0, lcap = 0;
 };
 struct svdw_ctx {
-    // SVDW_HOST_TRACE=1: host-side timestamps of svd_witness's enqueue points on
-    // stderr (µs since the call started), to find host waits inside a call
-    bool host_trace = false;
-    std::chrono::steady_clock::time_point ht0;
+    // ---- options: svdw_set_option (kOptions), svdw_set_gemm_impl, svdw_set_shard,
+    // the profiler switches; a lane takes them over as a whole (copy_settings)
+    struct Options {
+        int gemm_impl = SVDW_GEMM_MFMA;         // svdw_set_gemm_impl
+        // STAGE_* (4 KiB-aligned block store windows; "stage_rot" 1: phase B from a
+        // block-dependent window on, tools/r6/place_ab.py over 8 placements of the
+        // 1024^2 cell streams: 1.739-1.891 -> 1.728-1.825 ms, mean 1.815 -> 1.751)
+        uint32_t stage_flags = STAGE_ALIGN | STAGE_ROT;
+        uint32_t stage_elems = kStageElems;     // "stage_elems": elements per stage block (16..256)
+        int gemm_crt = 1;                       // "gemm_crt": multi-modular GEMM (else digits)
+        // "gemm_kern": CRT GEMM kernel (CrtBatch::kern); -1: wide tiles or the
+        // persistent grid for a product queued on its own (svdw_honest_prover_mat_mul,
+        // gemm_solo; CrtBatch::kern 3), one block per unit inside the witness calls,
+        // beside their stage kernels
+        int gemm_kern = -1;
+        int res_wait = -1;                      // "res_wait": stages wait for the residue planes
+        int place_trials = 6;                   // "place_trials": candidate placements of a new cell stream
+        bool res_f64 = true;                    // "res_f64": CRT residue planes of m, u, v from the
+                                                // f64 inputs, one launch (else from the cells)
+        int phase1_overlap = 1;                 // "phase1_overlap": 0 off, 1 on st2 behind the
+                                                // GEMMs, 2 on st3 from quantization on
+        int prod_cell = 1;                      // "prod_cell": svd_witness's products (residues, GEMM,
+                                                // combine) on the cell stream and the u / v bounds and
+                                                // u.d beside them on st2 (1), not (0); -1: on row-sharded
+                                                // ranks only. On by default: the product chain is the
+                                                // critical path sharded, and unsharded it measured
+                                                // 2.5 % faster at 1024^2 and 2048^2, neutral at 512^2
+        uint32_t hold_us = 0;                   // "hold_us": timing aid, st spins this long first
+        bool rlc_prefix = false;                // "rlc_prefix": svd_witness's phase 1 starts with the
+                                                // ctx_gate cells of load_rlc_cache(.., 1)
+        int p1_at = -1;                         // "p1_at": phase 1 on st3 (mode 2) enqueued after
+                                                // phase-0 stage 0 / 1 / 2 (the u, v bounds), 3: at the
+                                                // end; -1: auto (tools/shard_sim.py --opt p1_at=):
+                                                // 0 on a rank of >= 4, 3 of 2-3, else 1
+        // pipelined svd_witness: "dchk_at" the d checks on the cell stream behind
+        // the products (0), on st2 with the bounds and u.d (1) or on st3 ahead of
+        // phase 1 (2); "gamma_at" k_gamma_prep at the head of the cell stream (0) or
+        // of st3 (1); -1: st3 on a row-sharded rank, whose cell stream (quantize ->
+        // residues -> GEMM -> combine, then the diff on st2) is the step's chain
+        // (8-way rank 0.331 -> 0.316-0.321 ms; 1024^2 / 512^2 +0.5 %, r5p / r5q)
+        int dchk_at = 0, gamma_at = -1;
+        bool f64_views = true;                  // "f64_views": launches read registered f64 inputs (f64_view)
+        bool overlap = true;                    // "overlap": products queued ahead of the check stages
+        bool stage_batch = true;                // "stage_batch": stage launches share k_stage_multi (BatchScope)
+        int graph_vm = 1;                       // "graph": 0 off, 1 verify_mul_witness captured (vm_graph)
+        // "vm_linear": the captured verify_mul_witness runs on the context stream
+        // alone (st2 = st3 = st while it is queued: a linear graph, no fork / join
+        // events); concurrency comes from the two lanes instead.
+        int vm_linear = 1;
+        int pipeline = 1;                       // "pipeline": 1 on, 0 off (svd_witness_pipe, below)
+        // Row-block sharding of one witness: this context computes the
+        // rows [R rank / world, R (rank + 1) / world) of every row-parallel stage
+        // (R = that stage's row count) into the globally laid-out streams; shared
+        // inputs (quantized operands, single constants, the Freivalds b.g values)
+        // are computed in full. `owned` lists the cell ranges this rank is the
+        // source of, for reassembly.
+        uint32_t shard_rank = 0, shard_world = 1;
+        // built-in event profiler (svdw_profile_*): one start/stop event pair per launch
+        bool prof = false;
+        std::string prof_filter;                // record only kernels whose name starts with this
+        // SVDW_HOST_TRACE=1: host-side timestamps of svd_witness's enqueue points on
+        // stderr (µs since the call started), to find host waits inside a call
+        bool host_trace = false;
+        auto tied() const {
+            return std::tie(gemm_impl, stage_flags, stage_elems, gemm_crt, gemm_kern, res_wait, place_trials,
+                            res_f64, phase1_overlap, prod_cell, hold_us, rlc_prefix, p1_at, dchk_at, gamma_at,
+                            f64_views, overlap, stage_batch, graph_vm, vm_linear, pipeline, shard_rank,
+                            shard_world, prof, prof_filter, host_trace);
+        }
+        bool operator==(const Options& o) const { return tied() == o.tied(); }
+    } opt;
+    // ---- one witness call (svd_witness, verify_mul_witness): meaningful while the
+    // call is being enqueued. Each call sets it from scratch (begin_call, then the
+    // call's own code); CallEnd drops what must not outlive the call.
+    struct PreGemm {
+        uint64_t off;
+        hipEvent_t ev;
+        hipStream_t st;                     // the stream it was launched on
+    };
+    // svd_witness's quantized matrices and their device f64 inputs (u, v): a
+    // row-sharded rank takes b.g of b = u^T, v^T from the f64 rows directly
+    // (k_colsum_f64), not from cells. Cleared at the end of the witness.
+    struct F64Src { svdw_mat m; const double* x; };
+    // loaded regions whose f64 source is on the device for the current call:
+    // launches read them through VIEW_F64 (quantized in registers) instead of
+    // waiting for the quantized cells (f64_view)
+    struct F64Region { uint32_t phase; uint64_t off, n; const double* x; };
+    struct Call {
+        bool in_pipe = false;                   // inside a pipelined svd_witness
+        bool prelaunched = false;               // this witness's products were queued on st2
+        bool prod_on_cell = false;              // this witness's products went on the cell stream
+        bool gemm_batched = false;              // this witness's products went out as one batch
+        std::vector<PreGemm> pre;               // GEMMs launched ahead on st2, in append order
+        hipStream_t pre_wait_st = nullptr;      // the last (stream, event) waited on for them
+        hipEvent_t pre_wait_ev = nullptr;
+        std::vector<hipEvent_t> gemm_done;      // their completion events (this witness)
+        std::vector<hipEvent_t> wait_before_cs; // verify_mul_many: wait before the c_s scans
+        const double* svd_f64[3] = {nullptr, nullptr, nullptr};   // device f64 m, u, v of svd_witness
+        std::vector<F64Region> f64reg;
+        std::vector<F64Src> f64src;
+        std::function<void(const svdw_svd_payload&)> early_p1;   // phase 1's enqueue at p1_at (svd_witness)
+        bool stage_front = false;               // stage_launch: the stage goes ahead of the batch's groups
+        // verify_mul_witness: the one cell and gamma powers written by k_gamma_prep
+        // (phase-1 offsets one_off / pows_off for d), so verify_mul does not launch them
+        struct PowsPre {
+            bool on = false;
+            uint64_t one_off = 0, pows_off = 0;
+            uint32_t d = 0;
+        } pows_pre;
+        // the captured verify_mul_witness (vm_graph): `linear` is set while a
+        // vm_linear call is queued (stream_dep returns lin_ev, never recorded, and
+        // dep_wait skips it)
+        bool linear = false;
+        bool capturing = false;                 // st is capturing: no allocation, no sync
+        bool gp_external = false;               // k_gamma_prep already queued ahead of the graph
+        const Fr* gp_ext_one = nullptr;         // the one cell it wrote (null: none)
+    } call;
+    // ---- the handle: parameters, streams, cells, caches, scratch
+    std::chrono::steady_clock::time_point ht0;   // host_trace: when the call started
     int device = -1;
     bool dry = true;
     hipStream_t st = nullptr;
@@ -412,8 +528,6 @@ struct svdw_ctx {
     // of this cell set and of this half of the bit-length words. Anything else
     // that touches the streams after a pipelined call settles first (settle).
     Stream alt[2];
-    int pipeline = 1;                       // "pipeline": 1 on, 0 off
-    bool in_pipe = false;                   // inside a pipelined svd_witness
     int pipe_par = 0;                       // this call's parity (cell set, bit words)
     hipEvent_t tail_ev[2][2] = {};          // [parity][st2, st3]
     bool tail_valid[2] = {false, false};
@@ -444,13 +558,6 @@ struct svdw_ctx {
     uint32_t gp_len = 0;
     hipEvent_t gp_ev = nullptr;
     hipStream_t gp_st = nullptr;            // the stream gp_ev was recorded on
-    // verify_mul_witness: the one cell and gamma powers written by k_gamma_prep
-    // (phase-1 offsets one_off / pows_off for d), so verify_mul does not launch them
-    struct PowsPre {
-        bool on = false;
-        uint64_t one_off = 0, pows_off = 0;
-        uint32_t d = 0;
-    } pows_pre;             // gamma_prep queued ahead (svd_witness)
     // Device bit-length words of matrices written in this witness (svd_witness:
     // quantized m, u, v at dbitw[0..2]): the row scans decide their operand
     // width on the device from these (NaSpec), so the host never waits for them.
@@ -472,9 +579,7 @@ struct svdw_ctx {
     bool bits_pending = false;
     uint32_t qbits[3] = {0, 0, 0};
     svdw_mat qmat[3] = {};
-    // built-in event profiler (svdw_profile_*): one start/stop event pair per launch
-    bool prof = false;
-    std::string prof_filter;                // record only kernels whose name starts with this
+    // the event profiler's records (opt.prof): one start/stop event pair per launch
     struct Rec {
         std::string name;
         double bytes, ops;
@@ -482,37 +587,8 @@ struct svdw_ctx {
     };
     std::vector<Rec> recs;
     std::vector<hipEvent_t> pool;
-    int gemm_impl = SVDW_GEMM_MFMA;         // svdw_set_gemm_impl
-    // STAGE_* (4 KiB-aligned block store windows; "stage_rot" 1: phase B from a
-    // block-dependent window on, tools/r6/place_ab.py over 8 placements of the
-    // 1024^2 cell streams: 1.739-1.891 -> 1.728-1.825 ms, mean 1.815 -> 1.751)
-    uint32_t stage_flags = STAGE_ALIGN | STAGE_ROT;
-    uint32_t stage_elems = kStageElems;     // "stage_elems": elements per stage block (16..256)
     hipStream_t stream_id[3] = {};          // st, st2, st3 as created (st / st2 / st3 are swapped at times)
-    int gemm_crt = 1;                       // "gemm_crt": multi-modular GEMM (else digits)
-    // "gemm_kern": CRT GEMM kernel (CrtBatch::kern); -1: wide tiles or the
-    // persistent grid for a product queued on its own (svdw_honest_prover_mat_mul,
-    // gemm_solo; CrtBatch::kern 3), one block per unit inside the witness calls,
-    // beside their stage kernels
-    int gemm_kern = -1;
-    bool gemm_solo = false;
-    int res_wait = -1;                      // "res_wait": stages wait for the residue planes
-    int place_trials = 6;                   // "place_trials": candidate placements of a new cell stream
-    bool gemm_batched = false;              // this witness's products went out as one batch
-    bool res_f64 = true;                    // "res_f64": CRT residue planes of m, u, v from the
-                                            // f64 inputs, one launch (else from the cells)
-    const double* svd_f64[3] = {nullptr, nullptr, nullptr};   // device f64 m, u, v of svd_witness
-    int phase1_overlap = 1;                 // "phase1_overlap": 0 off, 1 on st2 behind the
-                                            // GEMMs, 2 on st3 from quantization on
-    bool prelaunched = false;               // this witness's products were queued on st2
-    int prod_cell = 1;                      // "prod_cell": svd_witness's products (residues, GEMM,
-                                            // combine) on the cell stream and the u / v bounds and
-                                            // u.d beside them on st2 (1), not (0); -1: on row-sharded
-                                            // ranks only. On by default: the product chain is the
-                                            // critical path sharded, and unsharded it measured
-                                            // 2.5 % faster at 1024^2 and 2048^2, neutral at 512^2
-    bool prod_on_cell = false;              // this witness's products went on the cell stream
-    uint32_t hold_us = 0;                   // "hold_us": timing aid, st spins this long first
+    bool gemm_solo = false;                 // svdw_honest_prover_mat_mul: a product queued on its own (gemm_kern)
     Fr ext_gamma{};                          // init_rand of the last verify_mul (equality source 2)
     uint64_t ext_off = 0;                    // its cell in the RLC context
     // ctx_rlc of the last svd_witness with rlc_prefix: [E(one), E(zero), W(gamma)]
@@ -522,47 +598,13 @@ struct svdw_ctx {
         Fr cells[3];
         uint64_t src[2];
     } rlc;
-    bool rlc_prefix = false;                 // "rlc_prefix": svd_witness's phase 1 starts with the
-                                             // ctx_gate cells of load_rlc_cache(.., 1)
-    int p1_at = -1;                         // "p1_at": phase 1 on st3 (mode 2) enqueued after
-                                            // phase-0 stage 0 / 1 / 2 (the u, v bounds), 3: at the
-                                            // end; -1: auto (tools/shard_sim.py --opt p1_at=):
-                                            // 0 on a rank of >= 4, 3 of 2-3, else 1
-    std::function<void(const svdw_svd_payload&)> early_p1;   // that enqueue (svd_witness)
-    // pipelined svd_witness: "dchk_at" the d checks on the cell stream behind
-    // the products (0), on st2 with the bounds and u.d (1) or on st3 ahead of
-    // phase 1 (2); "gamma_at" k_gamma_prep at the head of the cell stream (0) or
-    // of st3 (1); -1: st3 on a row-sharded rank, whose cell stream (quantize ->
-    // residues -> GEMM -> combine, then the diff on st2) is the step's chain
-    // (8-way rank 0.331 -> 0.316-0.321 ms; 1024^2 / 512^2 +0.5 %, r5p / r5q)
-    int dchk_at = 0, gamma_at = -1;
     // Host-side replays cached for repeated calls of the same shape: the dry
     // plan of svd_witness's stream sizes (key: N, M, config) and prelaunch's
     // product offsets (key: stream state at entry, operand views, bounds).
     std::vector<uint64_t> plan_key, plan_val, log_key, log_val;
-    std::vector<hipEvent_t> gemm_done;      // their completion events (this witness)
-    std::vector<hipEvent_t> wait_before_cs; // verify_mul_many: wait before the c_s scans
-    // Row-block sharding of one witness: this context computes the
-    // rows [R rank / world, R (rank + 1) / world) of every row-parallel stage
-    // (R = that stage's row count) into the globally laid-out streams; shared
-    // inputs (quantized operands, single constants, the Freivalds b.g values)
-    // are computed in full. `owned` lists the cell ranges this rank is the
-    // source of, for reassembly.
-    uint32_t shard_rank = 0, shard_world = 1;
     struct Seg { uint32_t phase, lookup; uint64_t off, n; };
-    std::vector<Seg> owned;
+    std::vector<Seg> owned;                 // row-sharded: the cell ranges this rank is the source of
     DBuf bvfull[kMaxScanJobs];              // shard mode: full b.g values per verify_mul
-    // svd_witness's quantized matrices and their device f64 inputs (u, v): a
-    // row-sharded rank takes b.g of b = u^T, v^T from the f64 rows directly
-    // (k_colsum_f64), not from cells. Cleared at the end of the witness.
-    struct F64Src { svdw_mat m; const double* x; };
-    // loaded regions whose f64 source is on the device for the current call:
-    // launches read them through VIEW_F64 (quantized in registers) instead of
-    // waiting for the quantized cells (f64_view)
-    struct F64Region { uint32_t phase; uint64_t off, n; const double* x; };
-    std::vector<F64Region> f64reg;
-    bool f64_views = true;                  // "f64_views"
-    std::vector<F64Src> f64src;
     DBuf colpart;
     DBuf qfold;                             // k_quantize_multi's fold counters + group maxima
     // second stream: GEMMs overlap the HBM-bound stages; third: phase 1
@@ -580,15 +622,6 @@ struct svdw_ctx {
         uint8_t used[kMarks] = {};
         uint64_t seq = 0;
     } mk;
-    bool overlap = true;
-    struct PreGemm {
-        uint64_t off;
-        hipEvent_t ev;
-        hipStream_t st;                     // the stream it was launched on
-    };
-    std::vector<PreGemm> pre;               // GEMMs launched ahead on st2, in append order
-    hipStream_t pre_wait_st = nullptr;      // the last (stream, event) waited on for them
-    hipEvent_t pre_wait_ev = nullptr;
     std::vector<svdw_region> layout;        // every appended region of the current witness
     // per region: gate offsets within one element's cells and cells per element
     // (program regions; empty otherwise; svdw_check_gates)
@@ -627,8 +660,6 @@ struct svdw_ctx {
         size_t last = 0;                   // group of the latest stage
     };
     std::vector<Batch> batches;
-    bool stage_batch = true;
-    bool stage_front = false;               // stage_launch: the stage goes ahead of the batch's groups
     // device ingest (svdw_parse_svd_input_device) scratch
     DBuf ing_x, ing_e, ing_c, ing_p10, ing_val, ing_npos, ing_nd, ing_rpos, ing_kpos, ing_err, ing_q;
     // device equality records (eq_gen_device)
@@ -638,18 +669,7 @@ struct svdw_ctx {
     // a shape, when every buffer is sized) and replayed by later calls of the
     // same key; gamma enters only through k_gamma_prep, launched eagerly on st
     // ahead of the graph (gp_external), so the graph itself is gamma-free.
-    int graph_vm = 1;                       // "graph": 0 off, 1 verify_mul_witness
-    // "vm_linear": the captured verify_mul_witness runs on the context stream
-    // alone (st2 = st3 = st while it is queued: a linear graph, no fork / join
-    // events); concurrency comes from the two lanes instead. `linear` is set
-    // while such a call is queued: stream_dep returns lin_ev (never recorded)
-    // and dep_wait skips it.
-    int vm_linear = 1;
-    bool linear = false;
-    hipEvent_t lin_ev = nullptr;
-    bool capturing = false;                 // st is capturing: no allocation, no sync
-    bool gp_external = false;               // verify_mul_witness: k_gamma_prep already queued
-    const Fr* gp_ext_one = nullptr;         // the one cell it wrote (null: none)
+    hipEvent_t lin_ev = nullptr;            // "vm_linear": stream_dep's placeholder (call.linear)
     uint64_t epoch = 0;                     // bumped by every allocation / option change
     // (layout_chk index, eqk slot) of the constants that hold gamma (the
     // verify_mul gamma powers' init_rand), patched on replay
@@ -679,7 +699,7 @@ static const bool g_batch_log = env_flag("SVDW_BATCH_LOG");
 static const bool g_stage_log = env_flag("SVDW_STAGE_LOG");
 static void sync(svdw_ctx* c) {
     if (c->dry) return;
-    REQUIRE(!c->capturing, "internal: synchronisation during graph capture");
+    REQUIRE(!c->call.capturing, "internal: synchronisation during graph capture");
     hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
     hipck(hipStreamSynchronize(c->st2), "hipStreamSynchronize");
     if (c->st3) hipck(hipStreamSynchronize(c->st3), "hipStreamSynchronize");
@@ -689,7 +709,7 @@ static void sync(svdw_ctx* c) {
 // After a pipelined svd_witness its tail (st2, st3) is not joined into st:
 // anything else queued on the context waits for it first.
 static void settle(svdw_ctx* c) {
-    if (c->dry || !c->tail_pending || c->in_pipe) return;
+    if (c->dry || !c->tail_pending || c->call.in_pipe) return;
     for (int k = 0; k < 2; ++k)
         hipck(hipStreamWaitEvent(c->st, c->tail_ev[c->tail_last][k], 0), "hipStreamWaitEvent");
     c->tail_pending = false;
@@ -716,7 +736,7 @@ static void release_alt(svdw_ctx* c) {
 // 0.417 -> 0.444 ms and 1024^2 2.078 -> 2.100 ms, 8-way ranks unchanged --
 // HIP runs those waits and writes as kernels of their own -- so it was removed.)
 static hipEvent_t stream_dep(svdw_ctx* c, hipStream_t from, hipStream_t to) {
-    if (c->linear) {                                   // one stream: order is implicit
+    if (c->call.linear) {                                   // one stream: order is implicit
         flush_batch(c, from);
         return c->lin_ev;
     }
@@ -736,13 +756,41 @@ static hipEvent_t stream_dep(svdw_ctx* c, hipStream_t from, hipStream_t to) {
 }
 // `s` waits for a dependency stream_dep returned (or any other event)
 static void dep_wait(svdw_ctx* c, hipStream_t s, hipEvent_t e) {
-    if (c->linear && e == c->lin_ev) return;
+    if (c->call.linear && e == c->lin_ev) return;
     hipck(hipStreamWaitEvent(s, e, 0), "hipStreamWaitEvent");
 }
 // (Round 4 removed "gemm_priority", a high-priority second stream at 512 <=
 // max(N, M) < 1024: +2 % in round 2's tools/ab.py runs, but bench.py at 512^2
 // P=32 measured 0.68 ms with it and 0.41 ms without -- the stream created
 // mid-run shares a hardware queue with the cell stream, GPU_MAX_HW_QUEUES = 4.)
+// Launches go out on c->st: this scope sends those queued inside it to a side
+// stream instead, by exchanging st with that stream's slot (&c->st2, &c->st3;
+// null: no redirection) until it ends, by end() or by unwinding. (st_cell and
+// stream_id still name the streams as created.)
+struct OnStream {
+    svdw_ctx* c;
+    hipStream_t* slot;
+    OnStream(svdw_ctx* cc, hipStream_t* s) : c(cc), slot(s) {
+        if (slot) std::swap(c->st, *slot);
+    }
+    OnStream(const OnStream&) = delete;
+    OnStream& operator=(const OnStream&) = delete;
+    ~OnStream() { end(); }
+    void end() {
+        if (slot) std::swap(c->st, *slot);
+        slot = nullptr;
+    }
+    bool on() const { return slot != nullptr; }
+};
+static svdw_mat transposed(const svdw_mat& m) {
+    return svdw_mat{m.phase, m.cols, m.rows, m.off, m.cs, m.rs};
+}
+static uint32_t clog2(uint32_t k) {                    // least l with 2^l >= k
+    uint32_t l = 0;
+    while ((1ull << l) < k) ++l;
+    return l;
+}
+static uint32_t ceil_to(uint32_t x, uint32_t a) { return (x + a - 1) / a * a; }
 static bool same_cells(const svdw_mat& a, const svdw_mat& b) {
     if (a.phase != b.phase || a.off != b.off) return false;
     return (a.rows == b.rows && a.cols == b.cols && a.rs == b.rs && a.cs == b.cs) ||
@@ -776,16 +824,16 @@ static void fetch_bits(svdw_ctx* c) {
         reg_bits(c, c->qmat[i], c->qbits[i]);
     }
 }
-static bool sharded(const svdw_ctx* c) { return c->shard_world > 1; }
+static bool sharded(const svdw_ctx* c) { return c->opt.shard_world > 1; }
 static void host_mark(svdw_ctx* c, const char* what) {
-    if (!c->host_trace || c->dry) return;
+    if (!c->opt.host_trace || c->dry) return;
     const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - c->ht0).count();
     fprintf(stderr, "[svdw host] %9.1f us  %s\n", us, what);
 }
 // rows of a row-parallel stage (R rows) that this rank computes / owns
 static void shard_rows(const svdw_ctx* c, uint64_t R, uint64_t* r0, uint64_t* r1) {
-    *r0 = R * c->shard_rank / c->shard_world;
-    *r1 = R * (c->shard_rank + 1) / c->shard_world;
+    *r0 = R * c->opt.shard_rank / c->opt.shard_world;
+    *r1 = R * (c->opt.shard_rank + 1) / c->opt.shard_world;
 }
 static void own(svdw_ctx* c, uint32_t phase, bool lookup, uint64_t off, uint64_t n) {
     if (sharded(c) && n) c->owned.push_back({phase, lookup ? 1u : 0u, off, n});
@@ -830,8 +878,8 @@ struct ProfScope {
               bool batch = false, bool stage = false)
         : c(cc), s(ss) {
         if (!batch) flush_batch(c, s);      // earlier batched stages go first
-        if (!c->prof || c->dry) return;
-        if (!c->prof_filter.empty() && name.compare(0, c->prof_filter.size(), c->prof_filter) != 0)
+        if (!c->opt.prof || c->dry) return;
+        if (!c->opt.prof_filter.empty() && name.compare(0, c->opt.prof_filter.size(), c->opt.prof_filter) != 0)
             return;
         // every launch is tagged with its stream (@cell, @s2, @s3 as created), so a
         // bench can report the busiest stream's stage rate beside the all-stream one
@@ -856,7 +904,7 @@ struct ProfScope {
 
 static void ensure_buf(svdw_ctx* c, DBuf& b, size_t bytes) {
     if (c->dry || b.cap >= bytes) return;
-    REQUIRE(!c->capturing, "internal: allocation during graph capture");
+    REQUIRE(!c->call.capturing, "internal: allocation during graph capture");
     ++c->epoch;
     sync(c);
     if (b.p) hipck(hipFree(b.p), "hipFree");
@@ -909,7 +957,7 @@ static double stage_store_rate(svdw_ctx* c, Fr* buf, uint64_t cells) {
     a.C = C;
     a.nv = 1;
     a.nk = 1;
-    a.flags = c->stage_flags;
+    a.flags = c->opt.stage_flags;
     a.cdiv_magic = (uint32_t)(((1ull << 32) + C - 1) / C);
     for (uint32_t k = 0; k < C; ++k) a.adv[k] = SlotOp{(uint8_t)KSRC, (uint8_t)(8 * (k % 8)), 0, 0};
     a.K[0] = fr_from_u64(0x9e3779b97f4a7c15ull);
@@ -938,7 +986,7 @@ static double stage_store_rate(svdw_ctx* c, Fr* buf, uint64_t cells) {
 // none at 4096^2) and a few ms once per allocation.
 static Fr* place_cells(svdw_ctx* c, uint64_t cells) {
     const uint64_t bytes = cells * sizeof(Fr);
-    int k = c->place_trials;
+    int k = c->opt.place_trials;
     if (k > 1 && bytes >= (256ull << 20)) {
         size_t fr = 0, tot = 0;
         if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = 0;
@@ -957,7 +1005,7 @@ static Fr* place_cells(svdw_ctx* c, uint64_t cells) {
         if (hipMalloc((void**)&p, bytes) != hipSuccess) break;
         cand.push_back(p);
         const double r = stage_store_rate(c, p, cells);
-        if (c->host_trace) fprintf(stderr, "place_cells: %.2f GB candidate %d at %p: %.3f TB/s\n", bytes / 1e9, i,
+        if (c->opt.host_trace) fprintf(stderr, "place_cells: %.2f GB candidate %d at %p: %.3f TB/s\n", bytes / 1e9, i,
                                    (void*)p, r / 1e12);
         if (r > br) {
             br = r;
@@ -970,7 +1018,7 @@ static Fr* place_cells(svdw_ctx* c, uint64_t cells) {
 }
 static void grow(svdw_ctx* c, Fr*& ptr, uint64_t used, uint64_t& cap, uint64_t need) {
     if (c->dry || need <= cap) return;
-    REQUIRE(!c->capturing, "internal: allocation during graph capture");
+    REQUIRE(!c->call.capturing, "internal: allocation during graph capture");
     ++c->epoch;
     uint64_t ncap = std::max(need, cap + cap / 2);
     Fr* np = ptr ? nullptr : place_cells(c, ncap);
@@ -1057,8 +1105,8 @@ static DView view_of(svdw_ctx* c, const svdw_mat& m) {
 // kernel (VIEW_F64), so the launch does not wait for k_quantize_multi. The
 // checker's copies of the views (note_gates) stay cell views.
 static DView f64_view(const svdw_ctx* c, const DView& v) {
-    if (!c->f64_views || c->f64reg.empty() || v.mode != VIEW_STRIDED || !v.ptr || !v.rows || !v.cols) return v;
-    for (const auto& r : c->f64reg) {
+    if (!c->opt.f64_views || c->call.f64reg.empty() || v.mode != VIEW_STRIDED || !v.ptr || !v.rows || !v.cols) return v;
+    for (const auto& r : c->call.f64reg) {
         const Fr* base = c->ph[r.phase].adv + r.off;
         const int64_t o = v.ptr - base;
         const int64_t er = (int64_t)(v.rows - 1) * v.rs, ec = (int64_t)(v.cols - 1) * v.cs;
@@ -1126,13 +1174,13 @@ static void stage_launch(svdw_ctx* c, uint32_t phase, PB& pb, uint32_t nelem, ui
     a.e_begin = eb;
     a.e_end = ee;
     a.cols = cols ? cols : 1;
-    a.flags = c->stage_flags;
+    a.flags = c->opt.stage_flags;
     // small blocks overlap better with concurrent work, but a stage with field
     // multiplications / inversions keeps one element per thread of a full block
     bool heavy = false;
     for (uint32_t i = 0; i < a.nmo; ++i)
         heavy |= a.mo[i].op == MO_MUL || a.mo[i].op == MO_ISZERO || a.mo[i].op == MO_POWK;
-    a.E = heavy ? kStageElems : c->stage_elems;
+    a.E = heavy ? kStageElems : c->opt.stage_elems;
     // keep the block's LDS (element values) within 64 KiB: fewer elements per
     // block for stages with many values (signed_div_scale)
     while (a.E > 64 && stage_lds_bytes(a.nv ? a.nv : 1, a.E, a.C + a.L) > 65536) a.E -= 64;
@@ -1166,7 +1214,7 @@ static void stage_launch(svdw_ctx* c, uint32_t phase, PB& pb, uint32_t nelem, ui
         for (size_t k = 0; k < b.groups.size(); ++k)
             for (const auto& q : b.groups[k])
                 if (reads(q)) g = k + 1;
-        if (c->stage_front && g == 0) {                   // a launch of its own, ahead of the batch
+        if (c->call.stage_front && g == 0) {                   // a launch of its own, ahead of the batch
             b.groups.insert(b.groups.begin(), std::vector<svdw_ctx::Pending>{});
             b.groups[0].push_back({a, std::string("k_stage:") + tag, bytes});
             b.last = 0;
@@ -1228,7 +1276,7 @@ struct BatchScope {
     hipStream_t st = nullptr;
     bool mine = false;
     explicit BatchScope(svdw_ctx* cc, hipStream_t on = nullptr) : c(cc) {
-        if (c->dry || !c->stage_batch) return;
+        if (c->dry || !c->opt.stage_batch) return;
         if (!on) on = c->st;
         for (auto& b : c->batches)
             if (b.st == on) return;
@@ -1366,16 +1414,9 @@ static svdw_vec put_cell(svdw_ctx* c, uint32_t phase, const Fr& v, bool constant
     // critical path); it depends on nothing, so it goes on st2 itself (never
     // back onto the cell stream: with st and st2 exchanged, as for a pipelined
     // witness's diff and ids, it stays where it is).
-    const bool aside = c->prelaunched && !c->dry && c->st2 != c->st_cell;
-    if (aside) std::swap(c->st, c->st2);
-    uint64_t off = 0;
-    try {
-        off = run_stage(c, phase, pb, 1, 1, "load_cell");
-    } catch (...) {
-        if (aside) std::swap(c->st, c->st2);
-        throw;
-    }
-    if (aside) std::swap(c->st, c->st2);
+    const bool aside = c->call.prelaunched && !c->dry && c->st2 != c->st_cell;
+    OnStream on(c, aside ? &c->st2 : nullptr);
+    const uint64_t off = run_stage(c, phase, pb, 1, 1, "load_cell");
     return svdw_vec{phase, 1, off, 1};
 }
 
@@ -1674,7 +1715,7 @@ static void gemm_exec(svdw_ctx* c, hipStream_t s, const svdw_mat& a, const svdw_
     DBuf& BB = bbuf ? *bbuf : c->digB;
     const uint32_t N = a.rows, K = a.cols, M = b.cols;
     const bool sym = is_transpose_of(b, a);
-    if (!sa && !sb && c->gemm_crt && c->gemm_impl == SVDW_GEMM_MFMA && bits_a <= 128 &&
+    if (!sa && !sb && c->opt.gemm_crt && c->opt.gemm_impl == SVDW_GEMM_MFMA && bits_a <= 128 &&
         bits_b <= 128 && K <= 8192 && !c->dry) {
         // host-known bounds: hand them to the CRT kernels as device words
         // (stream-ordered memsets, one pair per stream)
@@ -1686,7 +1727,7 @@ static void gemm_exec(svdw_ctx* c, hipStream_t s, const svdw_mat& a, const svdw_
         sa = w;
         sb = w + 1;
     }
-    if (sa && sb && c->gemm_crt && K <= 8192) {   // |acc| <= K 2^14 <= 2^27 (bias in k_gemm_crt)
+    if (sa && sb && c->opt.gemm_crt && K <= 8192) {   // |acc| <= K 2^14 <= 2^27 (bias in k_gemm_crt)
         // multi-modular path: residue planes, one int8 GEMM per modulus, CRT
         uint32_t lk = 0;
         while ((1ull << lk) < K) ++lk;
@@ -1718,7 +1759,7 @@ static void gemm_exec(svdw_ctx* c, hipStream_t s, const svdw_mat& a, const svdw_
                          (double)N * M * K);
             hipck(launch_gemm_crt(sym, Ar, Br, N, M, rpa, sym ? rpa : rpb,
                                   kpad, (uint8_t*)c->crtR.p, out, M, 1, sa, sym ? sa : sb, lk, s,
-                                  c->gemm_kern >= 0 ? (uint32_t)c->gemm_kern : (c->gemm_solo ? 3u : 0u)),
+                                  c->opt.gemm_kern >= 0 ? (uint32_t)c->opt.gemm_kern : (c->gemm_solo ? 3u : 0u)),
                   "k_gemm_crt");
         }
         if (!quantized)
@@ -1757,7 +1798,7 @@ static void gemm_exec(svdw_ctx* c, hipStream_t s, const svdw_mat& a, const svdw_
     }
     int DA = round_digits(digits_for_bits(bits_a)), DB = round_digits(digits_for_bits(bits_b));
     const bool digits_ok = DA && DB && K <= 8192 && gemm_digits_supported(DA, DB);
-    if (digits_ok && c->gemm_impl == SVDW_GEMM_MFMA) {
+    if (digits_ok && c->opt.gemm_impl == SVDW_GEMM_MFMA) {
         const uint32_t kcn = (K + 63) / 64;
         const uint32_t npad = (N + 31) / 32 * 32, mpad = (M + 31) / 32 * 32;
         ensure_buf(c, c->digA, (size_t)npad * kcn * DA * 64);
@@ -1818,7 +1859,7 @@ static svdw_mat row_block(const svdw_mat& a, uint64_t r0, uint64_t r1) {
     return svdw_mat{a.phase, (uint32_t)(r1 - r0), a.cols, a.off + r0 * a.rs, a.rs, a.cs};
 }
 // honest_prover_mat_mul (src/matrix/mod.rs:546-568). bits_a/bits_b: known bounds or ~0u.
-// If the product was launched ahead on st2 (c->pre), only append and order st after it.
+// If the product was launched ahead on st2 (c->call.pre), only append and order st after it.
 static svdw_mat honest_prover_mat_mul(svdw_ctx* c, uint32_t phase, const svdw_mat& a,
                                       const svdw_mat& b, uint32_t bits_a = ~0u,
                                       uint32_t bits_b = ~0u) {
@@ -1841,16 +1882,16 @@ static svdw_mat honest_prover_mat_mul(svdw_ctx* c, uint32_t phase, const svdw_ma
     if (bits_a == ~0u) bits_a = bits_of(c, a);
     if (bits_b == ~0u) bits_b = bits_of(c, b);
     if (c->dry) return cs;
-    if (!c->pre.empty()) {
-        if (c->pre.front().off != off) fail(SVDW_EDEVICE, "internal: pre-launched GEMM offset mismatch");
+    if (!c->call.pre.empty()) {
+        if (c->call.pre.front().off != off) fail(SVDW_EDEVICE, "internal: pre-launched GEMM offset mismatch");
         // (launched on this very stream: already ordered; the three batched
         // products share one event: one wait per stream)
-        if (c->pre.front().st != c->st && !(c->pre_wait_st == c->st && c->pre_wait_ev == c->pre.front().ev)) {
-            dep_wait(c, c->st, c->pre.front().ev);
-            c->pre_wait_st = c->st;
-            c->pre_wait_ev = c->pre.front().ev;
+        if (c->call.pre.front().st != c->st && !(c->call.pre_wait_st == c->st && c->call.pre_wait_ev == c->call.pre.front().ev)) {
+            dep_wait(c, c->st, c->call.pre.front().ev);
+            c->call.pre_wait_st = c->st;
+            c->call.pre_wait_ev = c->call.pre.front().ev;
         }
-        c->pre.erase(c->pre.begin());
+        c->call.pre.erase(c->call.pre.begin());
         return cs;
     }
     const bool sym = is_transpose_of(b, a);
@@ -1997,7 +2038,7 @@ struct VMul {
 // three products per element on the device instead of a square-and-multiply chain.
 static void gamma_prep(svdw_ctx* c, uint32_t d, const Fr& gamma, hipStream_t s, const PowCells* pc = nullptr) {
     if (c->dry) return;
-    REQUIRE(!c->capturing, "internal: gamma inside a captured graph");
+    REQUIRE(!c->call.capturing, "internal: gamma inside a captured graph");
     const uint32_t len = std::max(d, 1u);
     REQUIRE((len + 255) / 256 <= (uint32_t)kGammaTab - 32, "verify_mul: vector too long");
     ensure_buf(c, c->gpc, (size_t)len * sizeof(Fr));
@@ -2112,17 +2153,17 @@ static void verify_mul_many(svdw_ctx* c, uint32_t phase, const VMul* vm, int n, 
     const Fr* gpc = (const Fr*)c->gpc.p;
     const Fr* gtab = (const Fr*)c->gtab.p;
     // verify_mul_witness: k_gamma_prep already wrote the one cell and the powers
-    const bool pre = c->pows_pre.on && n == 1 && pl[0].one_off == c->pows_pre.one_off &&
-                     pl[0].pows_off == c->pows_pre.pows_off && vm[0].cs.cols == c->pows_pre.d &&
+    const bool pre = c->call.pows_pre.on && n == 1 && pl[0].one_off == c->call.pows_pre.one_off &&
+                     pl[0].pows_off == c->call.pows_pre.pows_off && vm[0].cs.cols == c->call.pows_pre.d &&
                      pl[0].one_loff == 0;
-    c->pows_pre.on = false;
+    c->call.pows_pre.on = false;
     // the one cells and gamma powers: read by no kernel of the call (gpc, not
     // these cells, feeds the scans), so a pipelined svd_witness launches them
     // after the scans, off the head of phase 1's stream
     auto pows_launch = [&] {
         if (pre) return;
         // (a captured graph must not hold gamma: the powers' launch carries it)
-        for (int i = 0; i < n; ++i) REQUIRE(!c->capturing || vm[i].cs.cols <= 1, "internal: gamma inside a captured graph");
+        for (int i = 0; i < n; ++i) REQUIRE(!c->call.capturing || vm[i].cs.cols <= 1, "internal: gamma inside a captured graph");
         BatchScope bs(c);                                 // the one cells and gamma powers: one launch
         for (int i = 0; i < n; ++i) {
             Plan& p = pl[i];
@@ -2141,7 +2182,7 @@ static void verify_mul_many(svdw_ctx* c, uint32_t phase, const VMul* vm, int n, 
         }
         bs.end();
     };
-    const bool pows_late = c->in_pipe;
+    const bool pows_late = c->call.in_pipe;
     if (!pows_late) pows_launch();
     // One scan launch over jobs (a_q against the vector wc_q / tab_q, cells at
     // v_q); operand widths host-known or read on the device (na 0).
@@ -2186,7 +2227,7 @@ static void verify_mul_many(svdw_ctx* c, uint32_t phase, const VMul* vm, int n, 
     // b = X^T of an f64 input of svd_witness: X, else null
     auto f64_of = [&](const svdw_mat& b) -> const svdw_ctx::F64Src* {
         if (b.cols > 8192) return nullptr;
-        for (auto& s : c->f64src)
+        for (auto& s : c->call.f64src)
             if (is_transpose_of(b, s.m) && s.m.rs == (int64_t)s.m.cols && s.m.cs == 1) return &s;
         return nullptr;
     };
@@ -2302,7 +2343,7 @@ static void verify_mul_many(svdw_ctx* c, uint32_t phase, const VMul* vm, int n, 
         launch(as_, "k_matvec_scan:a");
     }
     host_mark(c, "verify_mul b, a scans queued");
-    for (hipEvent_t ev : c->wait_before_cs)
+    for (hipEvent_t ev : c->call.wait_before_cs)
         dep_wait(c, c->st, ev);
     // the c_s scans; each row's is_equal(c_s.g, a.(b.g)) cells from its row
     // total and the a scan's last cell (k_matvec_scan_dpp's eq epilogue)
@@ -2353,8 +2394,6 @@ static void prelaunch_products_f64(svdw_ctx* c, const svdw_mat (&A)[3], const sv
                                    const std::vector<uint64_t>& log, uint32_t phase,
                                    unsigned* W, hipStream_t pst) {
     const uint32_t N = A[0].rows, M = A[0].cols;
-    auto clog2 = [](uint32_t k) { uint32_t l = 0; while ((1ull << l) < k) ++l; return l; };
-    auto ceil_to = [](uint32_t x, uint32_t a) { return (x + a - 1) / a * a; };
     const uint32_t lkM = clog2(M), lkN = clog2(N), kpM = ceil_to(M, 256), kpN = ceil_to(N, 256);
     uint64_t rr0[3], rr1[3];
     for (int g = 0; g < 3; ++g) {
@@ -2378,9 +2417,9 @@ static void prelaunch_products_f64(svdw_ctx* c, const svdw_mat (&A)[3], const sv
         int k = 0;
         for (auto& pr : pairs) { g.wa[k] = (int16_t)pr[0]; g.wb[k] = (int16_t)pr[1]; g.lk[k] = (uint32_t)pr[2]; ++k; }
     };
-    if (rows_m) seg(c->svd_f64[0] + rr0[0] * M, rows_m, M, rp_m, kpM, c->digA, {{0, 2, (int)lkM}});
-    seg(c->svd_f64[2], M, M, rp_v, kpM, c->digB, {{0, 2, (int)lkM}, {2, 2, (int)lkM}});
-    seg(c->svd_f64[1], N, N, rp_u, kpN, c->digC, {{1, 1, (int)lkN}});
+    if (rows_m) seg(c->call.svd_f64[0] + rr0[0] * M, rows_m, M, rp_m, kpM, c->digA, {{0, 2, (int)lkM}});
+    seg(c->call.svd_f64[2], M, M, rp_v, kpM, c->digB, {{0, 2, (int)lkM}, {2, 2, (int)lkM}});
+    seg(c->call.svd_f64[1], N, N, rp_u, kpN, c->digC, {{1, 1, (int)lkN}});
     {
         ProfScope ps(c, pst, "k_residues_f64",
                      8.0 * ((double)rows_m * M + (double)M * M + (double)N * N), 0);
@@ -2394,8 +2433,8 @@ static void prelaunch_products_f64(svdw_ctx* c, const svdw_mat (&A)[3], const sv
     // without waiting for the residue planes; -1: so on unsharded contexts,
     // tools/ab.py r6f: 512^2 0.378 -> 0.371 ms, 1024^2 2.035 -> 2.026 ms, while
     // the 8-way rank's chain is better served by the wait, 0.321 -> 0.327 ms)
-    const bool rw = c->res_wait >= 0 ? c->res_wait != 0 : sharded(c);
-    if (rw || !c->in_pipe || !c->f64_views || c->f64reg.empty())
+    const bool rw = c->opt.res_wait >= 0 ? c->opt.res_wait != 0 : sharded(c);
+    if (rw || !c->call.in_pipe || !c->opt.f64_views || c->call.f64reg.empty())
         stream_dep(c, pst, pst != c->st ? c->st : c->st2);
     const uint8_t* P[3] = {(const uint8_t*)c->digA.p, (const uint8_t*)c->digC.p,
                            (const uint8_t*)c->digB.p};                 // A planes of m, u, v
@@ -2441,16 +2480,16 @@ static void prelaunch_products_f64(svdw_ctx* c, const svdw_mat (&A)[3], const sv
             }
             roff += rbytes[g];
         }
-        c->gemm_batched = true;
-        b.kern = c->gemm_kern >= 0 ? (uint32_t)c->gemm_kern : 0u;
+        c->call.gemm_batched = true;
+        b.kern = c->opt.gemm_kern >= 0 ? (uint32_t)c->opt.gemm_kern : 0u;
         if (b.njobs) {
             ProfScope ps(c, pst, "k_gemm_crt:multi", bytes, ops);
             hipck(launch_gemm_crt_multi(b, pst), "k_gemm_crt_multi");
         }
         const hipEvent_t done = stream_dep(c, pst, nullptr);   // one completion point
         for (int g = 0; g < 3; ++g) {
-            c->pre.push_back({log[g], done, pst});
-            c->gemm_done.push_back(done);
+            c->call.pre.push_back({log[g], done, pst});
+            c->call.gemm_done.push_back(done);
         }
     }
 }
@@ -2473,18 +2512,18 @@ static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const s
     uint64_t n0[2], nl0[2];                               // stream state at entry (for the replay)
     for (int p = 0; p < 2; ++p) { n0[p] = c->ph[p].n; nl0[p] = c->ph[p].nl; }
     auto prelaunch = [&] {
-        if (c->dry || !c->overlap || !known_bits || !c->pre.empty()) return;
+        if (c->dry || !c->opt.overlap || !known_bits || !c->call.pre.empty()) return;
         // The three products depend only on m, u, v: take their stream offsets
         // from a dry replay of this function and launch them now on st2, so the
         // integer GEMMs run under the HBM-bound check stages on st. Called after
         // the first check stage is queued, so the device is busy while the host
         // waits for the operand bit lengths.
-        const bool on_device = dev_bits && c->gemm_impl == SVDW_GEMM_MFMA;
+        const bool on_device = dev_bits && c->opt.gemm_impl == SVDW_GEMM_MFMA;
         if (!on_device) fetch_bits(c);
         // residue planes straight from svd_witness's f64 inputs (one launch for m,
         // u and v) when they are on the device and the CRT path applies
-        const bool from_f64 = on_device && dev_quantized && c->res_f64 && c->gemm_crt &&
-                              c->svd_f64[0] && c->svd_f64[1] && c->svd_f64[2] && N <= 8192 &&
+        const bool from_f64 = on_device && dev_quantized && c->opt.res_f64 && c->opt.gemm_crt &&
+                              c->call.svd_f64[0] && c->call.svd_f64[1] && c->call.svd_f64[2] && N <= 8192 &&
                               M <= 8192;
         std::vector<uint64_t> key = {n0[0], n0[1], nl0[0], nl0[1], d.phase, d.len, d.off,
                                      (uint64_t)d.stride, f64_key(err_svd), f64_key(err_u), max_bits_d};
@@ -2503,15 +2542,13 @@ static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const s
             c->log_key = key;
             c->log_val = log;
         }
-        svdw_mat ut = u, vt = v;
-        std::swap(ut.rows, ut.cols); std::swap(ut.rs, ut.cs);
-        std::swap(vt.rows, vt.cols); std::swap(vt.rs, vt.cs);
+        const svdw_mat ut = transposed(u), vt = transposed(v);
         // loads of m, u, v done: the quantization event when svd_witness recorded
         // one (the cell stream may already hold later stages), else st's position
         // products on the cell stream (prod_cell): already behind the loads there
-        c->prod_on_cell = from_f64 && c->bits_pending && (c->prod_cell > 0 || (c->prod_cell < 0 && sharded(c)));
-        hipStream_t pst = c->prod_on_cell ? c->st : c->st2;
-        if (c->prod_on_cell) {
+        c->call.prod_on_cell = from_f64 && c->bits_pending && (c->opt.prod_cell > 0 || (c->opt.prod_cell < 0 && sharded(c)));
+        hipStream_t pst = c->call.prod_on_cell ? c->st : c->st2;
+        if (c->call.prod_on_cell) {
         } else if (c->bits_pending) {
             dep_wait(c, c->st2, c->ev_bits);
         } else {
@@ -2527,7 +2564,7 @@ static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const s
         const unsigned* sb[3] = {sl[2], sl[1], sl[2]};
         if (from_f64) {
             prelaunch_products_f64(c, A, B, log, m.phase, const_cast<unsigned*>(dev_bits), pst);   // (c->bits)
-            c->prelaunched = true;
+            c->call.prelaunched = true;
             host_mark(c, "products queued");
             return;
         }
@@ -2551,39 +2588,31 @@ static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const s
             else
                 gemm_exec(c, c->st2, Ag, B[g], outg, ba[g], bb[g]);
             if (g == 0 && r1 > r0 && on_device) vplanes = true;
-            c->pre.push_back({log[g], stream_dep(c, c->st2, nullptr), c->st2});
-            c->gemm_done.push_back(c->pre.back().ev);
+            c->call.pre.push_back({log[g], stream_dep(c, c->st2, nullptr), c->st2});
+            c->call.gemm_done.push_back(c->call.pre.back().ev);
         }
-        c->prelaunched = true;
+        c->call.prelaunched = true;
         host_mark(c, "products queued");
     };
     prelaunch();
     // what goes aside on st2 (d checks, single constant cells) is read by no
     // later kernel: batched until the end of phase 0 (two launches)
     BatchScope aside(c, c->st2);
-    if (!c->prelaunched) aside.close();
+    if (!c->call.prelaunched) aside.close();
     {
         // The d checks (three latency-bound stages over r elements) depend on d
         // only: with the products queued ahead they go behind them on st2, off
         // the cell stream, which starts on the u / v bounds at once. Pipelined
         // (st2 then carries every stage of the call back to back, st3 phase 1),
         // on the cell stream behind the products, its least loaded stream.
-        struct Swap {
-            svdw_ctx* c;
-            hipStream_t* other;
-            Swap(svdw_ctx* cc, bool o, bool third) : c(cc), other(o ? (third ? &cc->st3 : &cc->st2) : nullptr) {
-                if (other) std::swap(c->st, *other);
-            }
-            ~Swap() { if (other) std::swap(c->st, *other); }
-            bool on() const { return other != nullptr; }
-        };
         // (pipelined: where dchk_at puts them; st3 only when it exists)
-        const int da = !c->in_pipe ? 1 : (c->dchk_at == 2 && !c->st3 ? 1 : c->dchk_at);
-        Swap sw(c, c->overlap && known_bits && !c->dry && c->bits_pending && da != 0, da == 2);
+        const int da = !c->call.in_pipe ? 1 : (c->opt.dchk_at == 2 && !c->st3 ? 1 : c->opt.dchk_at);
+        const bool aside_d = c->opt.overlap && known_bits && !c->dry && c->bits_pending && da != 0;
+        OnStream sw(c, aside_d ? (da == 2 ? &c->st3 : &c->st2) : nullptr);
         // d loaded -- unless every load these stages (and the bounds and u.d
         // queued behind them with the products on the cell stream) read comes
         // from the registered f64 inputs (f64_view): then st2 starts at once
-        const bool from_f64 = c->f64_views && !c->f64reg.empty() && c->prod_on_cell;
+        const bool from_f64 = c->opt.f64_views && !c->call.f64reg.empty() && c->call.prod_on_cell;
         if (sw.on() && !from_f64) dep_wait(c, c->st, c->ev_bits);
         BatchScope bs(c);                   // (desc_order_range reads desc_order_sub: two launches)
         entries_less_than(c, d, max_bits);
@@ -2596,25 +2625,22 @@ static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const s
     // first phase-0 stages queued ahead of it, the third stream starts early
     // instead of after the host has queued all of phase 0.
     auto early_phase1 = [&](int at) {
-        const int p1_at = c->p1_at >= 0 ? c->p1_at
-                                         : (!sharded(c) ? 1 : (c->shard_world >= 4 ? 0 : 3));
-        if (!c->early_p1 || p1_at != at || !c->prelaunched || c->pre.size() != 3) return;
-        svdw_mat t_u = u, t_v = v;
-        std::swap(t_u.rows, t_u.cols); std::swap(t_u.rs, t_u.cs);
-        std::swap(t_v.rows, t_v.cols); std::swap(t_v.rs, t_v.cs);
-        const svdw_svd_payload pl{t_u, t_v, svdw_mat{m.phase, N, M, c->pre[0].off, (int64_t)M, 1},
-                                  svdw_mat{m.phase, N, N, c->pre[1].off, (int64_t)N, 1},
-                                  svdw_mat{m.phase, M, M, c->pre[2].off, (int64_t)M, 1}};
+        const int p1_at = c->opt.p1_at >= 0 ? c->opt.p1_at
+                                         : (!sharded(c) ? 1 : (c->opt.shard_world >= 4 ? 0 : 3));
+        if (!c->call.early_p1 || p1_at != at || !c->call.prelaunched || c->call.pre.size() != 3) return;
+        const svdw_mat t_u = transposed(u), t_v = transposed(v);
+        const svdw_svd_payload pl{t_u, t_v, svdw_mat{m.phase, N, M, c->call.pre[0].off, (int64_t)M, 1},
+                                  svdw_mat{m.phase, N, N, c->call.pre[1].off, (int64_t)N, 1},
+                                  svdw_mat{m.phase, M, M, c->call.pre[2].off, (int64_t)M, 1}};
         // the products' bounds (|c_s| < 2^(bits_a + bits_b + lk)) before
         // honest_prover_mat_mul registers them: the c_s scans then size their
         // operand on the device (NaSpec) instead of falling back to full
         // Montgomery products (8-way shard rank: 81 -> 25 us)
-        auto clog2 = [](uint32_t k) { uint32_t l = 0; while ((1ull << l) < k) ++l; return l; };
         c->prods.push_back({pl.m_times_vt, m, t_v, clog2(M)});
         c->prods.push_back({pl.u_times_ut, u, t_u, clog2(N)});
         c->prods.push_back({pl.v_times_vt, v, t_v, clog2(M)});
-        auto f = std::move(c->early_p1);
-        c->early_p1 = nullptr;
+        auto f = std::move(c->call.early_p1);
+        c->call.early_p1 = nullptr;
         f(pl);
     };
     early_phase1(0);
@@ -2623,8 +2649,8 @@ static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const s
     // With the products on the cell stream they go on st2 instead (behind the
     // d checks, in the same batch), and the cell stream waits for them before
     // the diff, by when they are done.
-    const bool pc = c->prod_on_cell && c->prelaunched;
-    if (pc) std::swap(c->st, c->st2);
+    const bool pc = c->call.prod_on_cell && c->call.prelaunched;
+    OnStream on2(c, pc ? &c->st2 : nullptr);
     BatchScope bs(c);
     const bool batched = bs.mine || pc;
     BigU unit = big_from_u128(((unsigned __int128)1 << P) + 1);
@@ -2634,18 +2660,16 @@ static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const s
     check_mat_entries_bounded(c, v, unit);
     host_mark(c, "bounds(v) queued");
     if (!batched) early_phase1(2);
-    svdw_mat ut = u, vt = v;
-    std::swap(ut.rows, ut.cols); std::swap(ut.rs, ut.cs);
-    std::swap(vt.rows, vt.cols); std::swap(vt.rs, vt.cs);
+    const svdw_mat ut = transposed(u), vt = transposed(v);
     DView udv;
     EqCell udpad;
     // products on the cell stream: u.d (all the diff needs from st2) in a launch
     // ahead of the bounds, so the cell stream waits for it alone (pipelined, the
     // diff follows on st2 itself: u.d shares the bounds' launch)
     if (r == M) {
-        c->stage_front = pc && !c->in_pipe;
+        c->call.stage_front = pc && !c->call.in_pipe;
         const svdw_mat ud = mat_times_diag_mat(c, u, d);
-        c->stage_front = false;
+        c->call.stage_front = false;
         udv = view_of(c, ud);
     } else {
         const svdw_vec z = put_cell(c, 0 + u.phase, fr_zero(), true);   // zero padding constant
@@ -2656,12 +2680,12 @@ static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const s
     }
     udv.rows = N;
     bs.end();
+    on2.end();
     if (pc) {
-        std::swap(c->st, c->st2);
         // the cell stream waits for u.d (and what precedes it on st2), not for
         // the d checks' dependent second group batched behind it; pipelined,
         // the diff is on st2 itself and st carries the next call: no wait
-        flush_batch(c, c->st2, c->in_pipe ? nullptr : c->st);
+        flush_batch(c, c->st2, c->call.in_pipe ? nullptr : c->st);
     }
     if (batched) {
         host_mark(c, "bounds(u), bounds(v), u.d queued");
@@ -2669,18 +2693,18 @@ static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const s
         early_phase1(2);
     }
     uint32_t bm = ~0u, bu = ~0u, bv = ~0u;
-    if (known_bits && c->pre.empty()) {                  // products not launched ahead
+    if (known_bits && c->call.pre.empty()) {                  // products not launched ahead
         fetch_bits(c);
         bm = known_bits[0]; bu = known_bits[1]; bv = known_bits[2];
     }
     // products batched (one completion point): diff and the two ids in one launch;
-    // pipelined (c->in_pipe), on st2 behind the bounds, so that st is free for
+    // pipelined (c->call.in_pipe), on st2 behind the bounds, so that st is free for
     // the next call's product chain (honest_prover_mat_mul's wait for the
     // products lands on st2)
-    const bool dst2 = c->in_pipe && pc;
-    if (dst2) std::swap(c->st, c->st2);
+    const bool dst2 = c->call.in_pipe && pc;
+    OnStream on_diff(c, dst2 ? &c->st2 : nullptr);
     BatchScope bs2(c);
-    if (!c->gemm_batched) bs2.close();
+    if (!c->call.gemm_batched) bs2.close();
     svdw_mat mvt = honest_prover_mat_mul(c, m.phase, m, vt, bm, bv);
     BigU es = scale_err(err_svd, P), eu = scale_err(err_u, P);
     host_mark(c, "u.d queued");
@@ -2694,7 +2718,7 @@ static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const s
     svdw_mat vvt = honest_prover_mat_mul(c, m.phase, v, vt, bv, bv);
     check_mat_id(c, vvt, q2, eu, &qq);
     bs2.end();
-    if (dst2) std::swap(c->st, c->st2);
+    on_diff.end();
     aside.end();
     host_mark(c, "ids queued");
     return svdw_svd_payload{ut, vt, mvt, uut, vvt};
@@ -2706,6 +2730,60 @@ static void check_svd_phase1(svdw_ctx* c, const svdw_mat& m, const svdw_mat& u, 
     verify_mul_many(c, 1, vm, 3, g);
 }
 
+// Exact cell stream sizes of a witness call from a dry replay of it (planner:
+// the call on a fresh planning context), cached by key: no growth copies
+// inside the step. grow_to_plan sizes the current cell set to them.
+template <class F>
+static void plan_sizes(svdw_ctx* c, const std::vector<uint64_t>& key, F&& planner) {
+    if (key == c->plan_key) return;
+    svdw_ctx plan;
+    plan.P = c->P; plan.LB = c->LB;
+    planner(&plan);
+    c->plan_key = key;
+    c->plan_val = {plan.ph[0].n, plan.ph[0].nl, plan.ph[1].n, plan.ph[1].nl};
+}
+static void grow_to_plan(svdw_ctx* c) {
+    for (int p = 0; p < 2; ++p) {
+        grow(c, c->ph[p].adv, 0, c->ph[p].cap, c->plan_val[2 * p]);
+        grow(c, c->ph[p].lk, 0, c->ph[p].lcap, c->plan_val[2 * p + 1]);
+    }
+}
+template <class F>
+static void plan_and_grow(svdw_ctx* c, const std::vector<uint64_t>& key, F&& planner) {
+    plan_sizes(c, key, planner);
+    grow_to_plan(c);
+}
+// The opening of a witness call: empty streams, and the call's state reset to
+// what both witness functions start from (clear(), never a fresh vector: the
+// 256^2 verify_mul_witness is host-bound, an allocation per call would show).
+static void begin_call(svdw_ctx* c, const char* what) {
+    c->ht0 = std::chrono::steady_clock::now();
+    host_mark(c, what);
+    clear_streams(c);
+    c->dep_next = 0;
+    c->call.prelaunched = false;
+    c->call.prod_on_cell = false;
+    c->call.gemm_batched = false;
+    c->call.gemm_done.clear();
+    c->call.wait_before_cs.clear();
+    c->call.pre.clear();
+    c->call.pre_wait_st = nullptr;
+    c->call.pre_wait_ev = nullptr;
+}
+// The end of a witness call, by return or by unwinding: what the call
+// registered for its own launches (its f64 inputs, phase 1's early enqueue,
+// the events the c_s scans wait for) does not outlive it.
+struct CallEnd {
+    svdw_ctx* c;
+    ~CallEnd() {
+        c->call.early_p1 = nullptr;
+        c->call.svd_f64[0] = c->call.svd_f64[1] = c->call.svd_f64[2] = nullptr;
+        c->call.f64src.clear();
+        c->call.f64reg.clear();
+        c->call.wait_before_cs.clear();
+        c->call.stage_front = false;
+    }
+};
 // A witness call's side streams start after everything queued on st (the
 // previous call's work joins st at its end): without this, the next call's
 // gamma tables (st3) and first stages (st2, f64 views need no load) could
@@ -2721,23 +2799,12 @@ static svdw_counts svd_witness(svdw_ctx* c, const double* m, const double* u, co
                                const svdw_svd_config& cfg, const Fr& gamma) {
     REQUIRE(N >= 1 && M >= 1, "empty matrix");
     const uint32_t r = std::min(N, M);
-    c->ht0 = std::chrono::steady_clock::now();
-    host_mark(c, "svd_witness start");
-    clear_streams(c);
-    c->dep_next = 0;
-    c->prelaunched = false;
-    c->prod_on_cell = false;
-    c->gemm_batched = false;
-    c->gemm_done.clear();
-    c->wait_before_cs.clear();
-    c->pre.clear();
-    c->pre_wait_st = nullptr;
-    c->pre_wait_ev = nullptr;
-    c->in_pipe = false;
+    begin_call(c, "svd_witness start");
+    c->call.in_pipe = false;
     struct PipeGuard {                     // an exception inside a pipelined call: its
         svdw_ctx* c;                       // tail is whatever reached st2 / st3 -- join it
         ~PipeGuard() {
-            if (!c->in_pipe) return;
+            if (!c->call.in_pipe) return;
             const int par = c->pipe_par;
             (void)hipEventRecord(c->tail_ev[par][0], c->st2);
             (void)hipEventRecord(c->tail_ev[par][1], c->st3);
@@ -2745,29 +2812,26 @@ static svdw_counts svd_witness(svdw_ctx* c, const double* m, const double* u, co
             c->tail_pending = true;
             c->tail_last = par;
             c->pipe_par ^= 1;
-            c->in_pipe = false;
+            c->call.in_pipe = false;
         }
     } pguard{c};
+    CallEnd call_end{c};
     if (!c->dry) {
         // exact sizes from the dry planner: no growth copies inside the step
-        const std::vector<uint64_t> key = {N, M, cfg.max_bits_d, f64_key(cfg.max_norm),
-                                           f64_key(cfg.eps_svd), f64_key(cfg.eps_u), c->rlc_prefix};
-        if (key != c->plan_key) {
-            svdw_ctx plan;
-            plan.P = c->P; plan.LB = c->LB;
-            plan.rlc_prefix = c->rlc_prefix;
-            svd_witness(&plan, nullptr, nullptr, nullptr, nullptr, N, M, false, cfg, gamma);
-            c->plan_key = key;
-            c->plan_val = {plan.ph[0].n, plan.ph[0].nl, plan.ph[1].n, plan.ph[1].nl};
-        }
+        plan_sizes(c, {N, M, cfg.max_bits_d, f64_key(cfg.max_norm), f64_key(cfg.eps_svd), f64_key(cfg.eps_u),
+                       c->opt.rlc_prefix},
+                   [&](svdw_ctx* plan) {
+                       plan->opt.rlc_prefix = c->opt.rlc_prefix;
+                       svd_witness(plan, nullptr, nullptr, nullptr, nullptr, N, M, false, cfg, gamma);
+                   });
         // Pipelined (svd_witness_pipe): device inputs on the f64 product path
         // with the products on the cell stream, and two cell sets that fit in
         // at most 60 % of the device memory (1024^2 P=63: 2 x 9.3 GB; 4096^2
         // P=63, 2 x 148 GB, runs unpipelined)
         const double wbytes = 32.0 * (double)(c->plan_val[0] + c->plan_val[1] + c->plan_val[2] + c->plan_val[3]);
-        const bool qualifies = c->pipeline && on_device && c->overlap && c->res_f64 && c->gemm_crt &&
-                               c->gemm_impl == SVDW_GEMM_MFMA && N <= 8192 && M <= 8192 &&
-                               (c->prod_cell > 0 || (c->prod_cell < 0 && sharded(c)));
+        const bool qualifies = c->opt.pipeline && on_device && c->opt.overlap && c->opt.res_f64 && c->opt.gemm_crt &&
+                               c->opt.gemm_impl == SVDW_GEMM_MFMA && N <= 8192 && M <= 8192 &&
+                               (c->opt.prod_cell > 0 || (c->opt.prod_cell < 0 && sharded(c)));
         // The other cell set must already hold this witness, or its growth must
         // fit in the device's free memory now (other contexts, the lane's state
         // and torch's allocations count) with 10 % of the device to spare for
@@ -2782,8 +2846,8 @@ static svdw_counts svd_witness(svdw_ctx* c, const double* m, const double* u, co
             }
         }
         if (qualifies && !fits) release_alt(c);
-        c->in_pipe = fits;
-        if (c->in_pipe) {
+        c->call.in_pipe = fits;
+        if (c->call.in_pipe) {
             // the other cell set (last written by call j - 2): every stream waits
             // for that call's tail, the last reader of these cells and bit words
             // (st2's first stages write cells that call's st3 scans read)
@@ -2807,17 +2871,11 @@ static svdw_counts svd_witness(svdw_ctx* c, const double* m, const double* u, co
             settle(c);
             after_previous(c);
         }
-        auto grow_set = [&] {
-            for (int p = 0; p < 2; ++p) {
-                grow(c, c->ph[p].adv, 0, c->ph[p].cap, c->plan_val[2 * p]);
-                grow(c, c->ph[p].lk, 0, c->ph[p].lcap, c->plan_val[2 * p + 1]);
-            }
-        };
-        if (!c->in_pipe) {
-            grow_set();
+        if (!c->call.in_pipe) {
+            grow_to_plan(c);
         } else {
             try {
-                grow_set();
+                grow_to_plan(c);
             } catch (const SvdwError& e) {
                 if (e.code != SVDW_ENOMEM) throw;
                 // the other set could not be allocated after all: back to this
@@ -2825,12 +2883,12 @@ static svdw_counts svd_witness(svdw_ctx* c, const double* m, const double* u, co
                 for (int p = 0; p < 2; ++p) std::swap(c->ph[p], c->alt[p]);
                 std::swap(c->gpc, c->gpc_alt);
                 std::swap(c->gtab, c->gtab_alt);
-                c->in_pipe = false;
+                c->call.in_pipe = false;
                 release_alt(c);
                 clear_streams(c);
                 settle(c);
                 after_previous(c);
-                grow_set();
+                grow_to_plan(c);
             }
         }
     }
@@ -2842,7 +2900,7 @@ static svdw_counts svd_witness(svdw_ctx* c, const double* m, const double* u, co
     // stream here); [E(one), E(zero), W(gamma)] go to ctx_rlc, whose cell 2 is init_rand.
     c->ext_off = 0;
     c->rlc.n = 0;
-    if (c->rlc_prefix) {
+    if (c->opt.rlc_prefix) {
         const svdw_vec one = put_cell(c, 1, fr_from_u64(1), true);
         const svdw_vec zero = put_cell(c, 1, fr_zero(), true);
         c->ext_off = 2;
@@ -2854,8 +2912,8 @@ static svdw_counts svd_witness(svdw_ctx* c, const double* m, const double* u, co
         c->rlc.src[1] = (uint64_t)zero.phase << 62 | zero.off;
     }
     c->gp_ev = nullptr;
-    if (!c->dry && c->hold_us) {       // every stream of the step waits for st's hold
-        hipck(launch_hold(c->hold_us, c->st), "k_hold");
+    if (!c->dry && c->opt.hold_us) {       // every stream of the step waits for st's hold
+        hipck(launch_hold(c->opt.hold_us, c->st), "k_hold");
         stream_dep(c, c->st, c->st3);
         stream_dep(c, c->st, c->st2);  // (st2's first stages need no load with f64 views)
     }
@@ -2863,8 +2921,8 @@ static svdw_counts svd_witness(svdw_ctx* c, const double* m, const double* u, co
         // gamma^j depends on gamma only: queue it first, on its own stream, so it
         // runs beside quantization instead of on the phase-1 chain (pipelined: on
         // the cell stream, the least loaded one, into this parity's tables)
-        const bool g3 = c->gamma_at == 1 || (c->gamma_at < 0 && sharded(c));
-        hipStream_t gs = c->in_pipe && !(g3 && c->st3) ? c->st_cell : c->st3;
+        const bool g3 = c->opt.gamma_at == 1 || (c->opt.gamma_at < 0 && sharded(c));
+        hipStream_t gs = c->call.in_pipe && !(g3 && c->st3) ? c->st_cell : c->st3;
         gamma_prep(c, std::max(N, M), gamma, gs);
         c->gp_ev = stream_dep(c, gs, nullptr);
         c->gp_st = gs;
@@ -2885,7 +2943,7 @@ static svdw_counts svd_witness(svdw_ctx* c, const double* m, const double* u, co
         // (pipelined: a half per parity, call j - 1's row scans still read theirs)
         const size_t words = (64 + nbm + nbu + nbv + 63) / 64 * 64;
         ensure_buf(c, c->bits, 2 * words * sizeof(unsigned));
-        dbits = (unsigned*)c->bits.p + (c->in_pipe ? c->pipe_par * words : 0);
+        dbits = (unsigned*)c->bits.p + (c->call.in_pipe ? c->pipe_par * words : 0);
     }
     QuantSegs qs;
     memset(&qs, 0, sizeof qs);
@@ -2895,8 +2953,8 @@ static svdw_counts svd_witness(svdw_ctx* c, const double* m, const double* u, co
     // (u, v: the rank's rows and column block only, when b.g comes from the f64
     // inputs and so do the products' residue planes: no kernel reads the rest;
     // the conditions of f64_of and of check_svd_phase0's from_f64 prelaunch)
-    const bool part = sharded(c) && on_device && N <= 8192 && M <= 8192 && c->overlap && c->res_f64 &&
-                      c->gemm_crt && c->gemm_impl == SVDW_GEMM_MFMA;
+    const bool part = sharded(c) && on_device && N <= 8192 && M <= 8192 && c->opt.overlap && c->opt.res_f64 &&
+                      c->opt.gemm_crt && c->opt.gemm_impl == SVDW_GEMM_MFMA;
     svdw_mat zu = zkmatrix_new(c, 0, u, N, N, on_device, dbits ? dbits + 64 + nbm : nullptr, qp, false, part);
     svdw_mat zv = zkmatrix_new(c, 0, v, M, M, on_device, dbits ? dbits + 64 + nbm + nbu : nullptr, qp, false,
                                part);
@@ -2946,58 +3004,41 @@ static svdw_counts svd_witness(svdw_ctx* c, const double* m, const double* u, co
     // 1 % slower.
     const bool p1_small = std::max(N, M) < 1024;
     // (pipelined: st2 carries the diff and ids after the bounds, phase 1 goes to st3)
-    const int p1mode = c->phase1_overlap == 1 && (sharded(c) || p1_small || c->in_pipe) ? 2 : c->phase1_overlap;
+    const int p1mode = c->opt.phase1_overlap == 1 && (sharded(c) || p1_small || c->call.in_pipe) ? 2 : c->opt.phase1_overlap;
     bool p1_queued = false;
     auto queue_phase1 = [&](const svdw_svd_payload& pl, bool overlap) {
         const bool p1_overlap = p1mode && overlap;
         hipStream_t p1s = p1mode == 2 ? c->st3 : c->st2;
         // phase 1 beside the products (st3, or st2 while the products run on the
         // cell stream): it waits for the loads, and its c_s scans for the products
-        if (p1_overlap && (p1s == c->st3 || c->prod_on_cell)) {
+        if (p1_overlap && (p1s == c->st3 || c->call.prod_on_cell)) {
             dep_wait(c, p1s, c->ev_bits);
-            c->wait_before_cs = c->gemm_done;
+            c->call.wait_before_cs = c->call.gemm_done;
         }
         {
-            struct Swap {
-                svdw_ctx* c;
-                hipStream_t* other;
-                Swap(svdw_ctx* cc, hipStream_t* o) : c(cc), other(o) { if (other) std::swap(c->st, *other); }
-                ~Swap() { if (other) std::swap(c->st, *other); }
-            } sw(c, p1_overlap ? (p1s == c->st3 ? &c->st3 : &c->st2) : nullptr);
+            OnStream on(c, p1_overlap ? (p1s == c->st3 ? &c->st3 : &c->st2) : nullptr);
             check_svd_phase1(c, zm, zu, zv, pl, gamma);
         }
-        c->wait_before_cs.clear();
+        c->call.wait_before_cs.clear();
         p1_queued = true;
         host_mark(c, "phase 1 (early) queued");
     };
-    struct Clear {
-        svdw_ctx* c;
-        ~Clear() { c->early_p1 = nullptr; }
-    } clr{c};
-    if (p1mode == 2 && !c->dry) c->early_p1 = [&](const svdw_svd_payload& pl) { queue_phase1(pl, true); };
-    struct F64 {
-        svdw_ctx* c;
-        ~F64() {
-            c->svd_f64[0] = c->svd_f64[1] = c->svd_f64[2] = nullptr;
-            c->f64src.clear();
-            c->f64reg.clear();
-        }
-    } f64clr{c};
+    if (p1mode == 2 && !c->dry) c->call.early_p1 = [&](const svdw_svd_payload& pl) { queue_phase1(pl, true); };
     if (on_device && !c->dry) {
-        c->svd_f64[0] = m; c->svd_f64[1] = u; c->svd_f64[2] = v;
-        c->f64src = {{zu, u}, {zv, v}};
-        c->f64reg = {{zm.phase, zm.off, (uint64_t)N * M, m}, {zu.phase, zu.off, (uint64_t)N * N, u},
+        c->call.svd_f64[0] = m; c->call.svd_f64[1] = u; c->call.svd_f64[2] = v;
+        c->call.f64src = {{zu, u}, {zv, v}};
+        c->call.f64reg = {{zm.phase, zm.off, (uint64_t)N * M, m}, {zu.phase, zu.off, (uint64_t)N * N, u},
                      {zv.phase, zv.off, (uint64_t)M * M, v}, {zdm.phase, zdm.off, (uint64_t)r, d}};
     }
     svdw_svd_payload pl =
         check_svd_phase0(c, zm, zu, zv, zd, es, eu, cfg.max_bits_d, c->qbits, dbits, true);
-    c->early_p1 = nullptr;
-    const bool p1_overlap = p1mode && c->prelaunched && !c->dry;
+    c->call.early_p1 = nullptr;
+    const bool p1_overlap = p1mode && c->call.prelaunched && !c->dry;
     hipStream_t p1s = p1mode == 2 ? c->st3 : c->st2;
     host_mark(c, "phase 0 queued");
     if (!p1_queued) queue_phase1(pl, p1_overlap);
     host_mark(c, "phase 1 queued");
-    if (c->in_pipe) {
+    if (c->call.in_pipe) {
         // no join into st: the next call's product chain starts on st while this
         // call's stages (st2) and row scans (st3) finish; they end at tail_ev
         const int par = c->pipe_par;
@@ -3009,14 +3050,14 @@ static svdw_counts svd_witness(svdw_ctx* c, const double* m, const double* u, co
         c->tail_pending = true;
         c->tail_last = par;
         c->pipe_par ^= 1;
-        c->in_pipe = false;
+        c->call.in_pipe = false;
         host_mark(c, "svd_witness end (pipelined)");
         return svdw_counts{c->ph[0].n, c->ph[1].n, c->ph[0].nl, c->ph[1].nl};
     }
     if (p1_overlap) stream_dep(c, p1s, c->st);
     // st2 also carries the d checks and single cells queued aside (and, with
     // phase 1 on st3, nothing else joins it): join it too
-    if (c->prelaunched && !c->dry && !(p1_overlap && p1s == c->st2)) stream_dep(c, c->st2, c->st);
+    if (c->call.prelaunched && !c->dry && !(p1_overlap && p1s == c->st2)) stream_dep(c, c->st2, c->st);
     host_mark(c, "svd_witness end");
     return svdw_counts{c->ph[0].n, c->ph[1].n, c->ph[0].nl, c->ph[1].nl};
 }
@@ -3043,38 +3084,18 @@ static svdw_counts verify_mul_witness(svdw_ctx* c, const double* a, const double
                                       uint32_t K, uint32_t M, bool on_device, const Fr& gamma) {
     REQUIRE(N >= 1 && K >= 1 && M >= 1, "empty matrix");
     REQUIRE(!sharded(c), "verify_mul_witness: not for row-sharded contexts");
-    c->ht0 = std::chrono::steady_clock::now();
-    host_mark(c, "verify_mul_witness start");
-    clear_streams(c);
-    c->dep_next = 0;
+    begin_call(c, "verify_mul_witness start");
+    CallEnd call_end{c};
     settle(c);
     after_previous(c);
-    c->prelaunched = false;
-    c->prod_on_cell = false;
-    c->gemm_batched = false;
-    c->gemm_done.clear();
-    c->wait_before_cs.clear();
-    c->pre.clear();
-    c->pre_wait_st = nullptr;
-    c->pre_wait_ev = nullptr;
-    if (!c->dry) {
-        const std::vector<uint64_t> key = {0x766d77ull, N, K, M};      // sizes from the dry plan
-        if (key != c->plan_key) {
-            svdw_ctx plan;
-            plan.P = c->P; plan.LB = c->LB;
-            verify_mul_witness(&plan, nullptr, nullptr, N, K, M, false, gamma);
-            c->plan_key = key;
-            c->plan_val = {plan.ph[0].n, plan.ph[0].nl, plan.ph[1].n, plan.ph[1].nl};
-        }
-        for (int p = 0; p < 2; ++p) {
-            grow(c, c->ph[p].adv, 0, c->ph[p].cap, c->plan_val[2 * p]);
-            grow(c, c->ph[p].lk, 0, c->ph[p].lcap, c->plan_val[2 * p + 1]);
-        }
-    }
+    if (!c->dry)
+        plan_and_grow(c, {0x766d77ull, N, K, M}, [&](svdw_ctx* plan) {
+            verify_mul_witness(plan, nullptr, nullptr, N, K, M, false, gamma);
+        });
     c->ext_off = 0;
     c->gp_ev = nullptr;
-    if (!c->dry && c->hold_us) {       // every stream of the step waits for st's hold
-        hipck(launch_hold(c->hold_us, c->st), "k_hold");
+    if (!c->dry && c->opt.hold_us) {       // every stream of the step waits for st's hold
+        hipck(launch_hold(c->opt.hold_us, c->st), "k_hold");
         stream_dep(c, c->st, c->st3);
         stream_dep(c, c->st, c->st2);
     }
@@ -3083,15 +3104,15 @@ static svdw_counts verify_mul_witness(svdw_ctx* c, const double* a, const double
     const uint32_t qpb = on_device ? quant_per_block((uint64_t)N * K + (uint64_t)K * M) : kQuantPerBlock;
     const uint32_t nba = (uint32_t)(((uint64_t)N * K + qpb - 1) / qpb),
                    nbb = (uint32_t)(((uint64_t)K * M + qpb - 1) / qpb);
-    c->pows_pre.on = false;
+    c->call.pows_pre.on = false;
     if (!c->dry) {
         // phase 1 opens with verify_mul's one cell and its d - 1 gamma-power
         // elements (verify_mul_many's first appends): k_gamma_prep writes them
         PowCells pc;
         // (queued ahead: only if that launch wrote them where they are now)
-        if (c->ph[1].n == 0 && vm_pow_cells(c, M, gamma, &pc) && (!c->gp_external || c->gp_ext_one == pc.one))
-            c->pows_pre = {true, 0, 1, M};
-        if (c->gp_external) {                         // queued on st ahead of the captured graph
+        if (c->ph[1].n == 0 && vm_pow_cells(c, M, gamma, &pc) && (!c->call.gp_external || c->call.gp_ext_one == pc.one))
+            c->call.pows_pre = {true, 0, 1, M};
+        if (c->call.gp_external) {                         // queued on st ahead of the captured graph
             c->gp_gamma = gamma;
             c->gp_len = std::max(M, 1u);
         } else {
@@ -3126,33 +3147,24 @@ static svdw_counts verify_mul_witness(svdw_ctx* c, const double* a, const double
         c->dwords = {{za, 0}, {zb, 1}};
     }
     host_mark(c, "quantize queued");
-    struct RegClear {
-        svdw_ctx* c;
-        ~RegClear() { c->f64reg.clear(); }
-    } regclr{c};
     if (on_device && !c->dry)
-        c->f64reg = {{za.phase, za.off, (uint64_t)N * K, a}, {zb.phase, zb.off, (uint64_t)K * M, b}};
+        c->call.f64reg = {{za.phase, za.off, (uint64_t)N * K, a}, {zb.phase, zb.off, (uint64_t)K * M, b}};
     // c_s = a * b (honest_prover_mat_mul's cells), the CRT GEMM sized on the device
     uint64_t off;
     append(c, 0, (uint64_t)N * M, 0, &off, nullptr, "product", N);
     const svdw_mat cs{0, N, M, off, (int64_t)M, 1};
-    {
-        uint32_t lk = 0;
-        while ((1ull << lk) < K) ++lk;
-        c->prods.push_back({cs, za, zb, lk});
-    }
+    const uint32_t lk = clog2(K);
+    c->prods.push_back({cs, za, zb, lk});
     // device inputs: residue planes of a and b^T straight from the f64 inputs
     // (one launch), the GEMM and combine on st, and verify_mul on the third
     // stream from the loads on: its one / gamma-power cells and the b and a
     // scans run beside the product, only the c_s scans wait for it
-    const bool f64 = on_device && !c->dry && c->res_f64 && c->gemm_crt && c->gemm_impl == SVDW_GEMM_MFMA &&
+    const bool f64 = on_device && !c->dry && c->opt.res_f64 && c->opt.gemm_crt && c->opt.gemm_impl == SVDW_GEMM_MFMA &&
                      K <= 8192 && qs.nseg == 2;
     hipEvent_t loaded = nullptr;
     if (f64) {
         loaded = stream_dep(c, c->st, nullptr);
-        uint32_t lk = 0;
-        while ((1ull << lk) < K) ++lk;
-        const uint32_t kpad = (K + 255) / 256 * 256, rpa = (N + 127) / 128 * 128, rpb = (M + 127) / 128 * 128;
+        const uint32_t kpad = ceil_to(K, 256), rpa = ceil_to(N, 128), rpb = ceil_to(M, 128);
         ensure_buf(c, c->digA, (size_t)kCrtMaxResidues * rpa * kpad);
         ensure_buf(c, c->digB, (size_t)kCrtMaxResidues * rpb * kpad);
         ensure_buf(c, c->crtR, crt_scratch_bytes(N, M));
@@ -3175,7 +3187,7 @@ static svdw_counts verify_mul_witness(svdw_ctx* c, const double* a, const double
             ProfScope ps(c, c->st, "k_gemm_crt", 32.0 * N * M, (double)N * M * K);
             hipck(launch_gemm_crt(false, (const uint8_t*)c->digA.p, (const uint8_t*)c->digB.p, N, M, rpa, rpb,
                                   kpad, (uint8_t*)c->crtR.p, cellp(c, 0, off), M, 1, dbits, dbits + 1, lk,
-                                  c->st, c->gemm_kern >= 0 ? (uint32_t)c->gemm_kern : 0u),
+                                  c->st, c->opt.gemm_kern >= 0 ? (uint32_t)c->opt.gemm_kern : 0u),
                   "k_gemm_crt");
         }
     } else if (!c->dry) {
@@ -3184,18 +3196,13 @@ static svdw_counts verify_mul_witness(svdw_ctx* c, const double* a, const double
     host_mark(c, "product queued");
     const VMul vm{za, zb, cs};
     if (f64) {
-        c->wait_before_cs = {stream_dep(c, c->st, nullptr)};
+        c->call.wait_before_cs = {stream_dep(c, c->st, nullptr)};
         dep_wait(c, c->st3, loaded);
-        std::swap(c->st, c->st3);
-        try {
+        {
+            OnStream on(c, &c->st3);
             verify_mul_many(c, 1, &vm, 1, gamma);
-        } catch (...) {
-            std::swap(c->st, c->st3);
-            c->wait_before_cs.clear();
-            throw;
         }
-        std::swap(c->st, c->st3);
-        c->wait_before_cs.clear();
+        c->call.wait_before_cs.clear();
         stream_dep(c, c->st3, c->st);                     // join
     } else {
         verify_mul_many(c, 1, &vm, 1, gamma);
@@ -3339,26 +3346,63 @@ static void ctx_init_device(svdw_ctx* c) {
 // The settings (options, shard, profiler) of `s` onto the lane `d`; a change
 // bumps the lane's epoch (its captured graph no longer applies).
 static void copy_settings(svdw_ctx* d, const svdw_ctx* s) {
-    const int64_t a[] = {s->gemm_impl, s->stage_flags, s->stage_elems, s->gemm_crt, s->gemm_kern, s->res_wait, s->place_trials, s->res_f64,
-                         s->phase1_overlap, s->prod_cell, s->hold_us, s->rlc_prefix, s->p1_at, s->dchk_at, s->gamma_at,
-                         s->f64_views, s->overlap, s->stage_batch, s->graph_vm, s->vm_linear, s->pipeline,
-                         s->shard_rank, s->shard_world, s->prof, s->host_trace};
-    const int64_t b[] = {d->gemm_impl, d->stage_flags, d->stage_elems, d->gemm_crt, d->gemm_kern, d->res_wait, d->place_trials, d->res_f64,
-                         d->phase1_overlap, d->prod_cell, d->hold_us, d->rlc_prefix, d->p1_at, d->dchk_at, d->gamma_at,
-                         d->f64_views, d->overlap, d->stage_batch, d->graph_vm, d->vm_linear, d->pipeline,
-                         d->shard_rank, d->shard_world, d->prof, d->host_trace};
-    if (!memcmp(a, b, sizeof a) && d->prof_filter == s->prof_filter) return;
-    d->gemm_impl = s->gemm_impl; d->stage_flags = s->stage_flags; d->stage_elems = s->stage_elems;
-    d->gemm_crt = s->gemm_crt; d->gemm_kern = s->gemm_kern; d->res_wait = s->res_wait; d->place_trials = s->place_trials; d->res_f64 = s->res_f64; d->phase1_overlap = s->phase1_overlap;
-    d->prod_cell = s->prod_cell; d->hold_us = s->hold_us; d->rlc_prefix = s->rlc_prefix;
-    d->p1_at = s->p1_at; d->f64_views = s->f64_views; d->overlap = s->overlap;
-    d->dchk_at = s->dchk_at; d->gamma_at = s->gamma_at;
-    d->stage_batch = s->stage_batch; d->graph_vm = s->graph_vm; d->pipeline = s->pipeline;
-    d->vm_linear = s->vm_linear;
-    d->shard_rank = s->shard_rank; d->shard_world = s->shard_world; d->prof = s->prof;
-    d->host_trace = s->host_trace; d->prof_filter = s->prof_filter;
+    if (d->opt == s->opt) return;
+    d->opt = s->opt;
     ++d->epoch;
 }
+// svdw_set_option's names: a value in [lo, hi] (else SVDW_EINVAL with `msg`)
+// goes to `set` (a bool member takes value != 0).
+struct OptionDef {
+    const char* name;
+    int64_t lo, hi;
+    const char* msg;
+    void (*set)(svdw_ctx*, int64_t);
+};
+template <auto Member>
+static void set_opt(svdw_ctx* c, int64_t v) {
+    c->opt.*Member = static_cast<std::remove_reference_t<decltype(c->opt.*Member)>>(v);
+}
+static void set_lanes(svdw_ctx* c, int64_t v) { c->lanes = (int)v; }   // (the handle's, not the state's)
+static void set_pipeline(svdw_ctx* c, int64_t v) {
+    c->opt.pipeline = (int)v;
+    if (!v) {                                        // the other cell set is not needed any more
+        release_alt(c);
+        if (c->lane) release_alt(c->lane);
+    }
+}
+static void set_stage_rot(svdw_ctx* c, int64_t v) {
+    c->opt.stage_flags = v ? (c->opt.stage_flags | STAGE_ROT) : (c->opt.stage_flags & ~STAGE_ROT);
+}
+static const char kStageElemsMsg[] = "stage_elems: a multiple of 16 in [16, 256]";
+static void set_stage_elems(svdw_ctx* c, int64_t v) {
+    REQUIRE(v % 16 == 0, kStageElemsMsg);
+    c->opt.stage_elems = (uint32_t)v;
+}
+using Opt = svdw_ctx::Options;
+static const OptionDef kOptions[] = {
+    {"lanes", 1, 2, "lanes: 1 or 2", set_lanes},   // verify_mul_witness on two alternating states
+    {"pipeline", 0, 1, "pipeline: 0 or 1", set_pipeline},   // pipelined svd_witness (svd_witness)
+    {"vm_linear", 0, 1, "vm_linear: 0 or 1", set_opt<&Opt::vm_linear>},   // captured verify_mul_witness on one stream
+    {"graph", 0, 1, "graph: 0 or 1", set_opt<&Opt::graph_vm>},   // captured verify_mul_witness (vm_graph)
+    {"gemm_impl", SVDW_GEMM_MFMA, SVDW_GEMM_VALU, "gemm_impl: 0 (mfma) or 1 (valu)", set_opt<&Opt::gemm_impl>},
+    {"stage_elems", 16, 256, kStageElemsMsg, set_stage_elems},
+    {"prod_cell", -1, 1, "prod_cell: -1, 0 or 1", set_opt<&Opt::prod_cell>},
+    {"phase1_overlap", 0, 2, "phase1_overlap: 0, 1 or 2", set_opt<&Opt::phase1_overlap>},
+    {"hold_us", 0, 100000, "hold_us: 0..100000", set_opt<&Opt::hold_us>},   // timing aid: GPU-only schedule of a witness
+    {"rlc_prefix", INT64_MIN, INT64_MAX, "", set_opt<&Opt::rlc_prefix>},
+    {"res_f64", INT64_MIN, INT64_MAX, "", set_opt<&Opt::res_f64>},
+    {"gemm_crt", 0, 1, "gemm_crt: 0 or 1", set_opt<&Opt::gemm_crt>},
+    {"res_wait", -1, 1, "res_wait: -1 (auto), 0 or 1", set_opt<&Opt::res_wait>},   // pipelined: st2 waits for the residue planes
+    {"place_trials", 0, 8, "place_trials: 0..8", set_opt<&Opt::place_trials>},   // cell streams >= 256 MiB: best of this many placements
+    {"stage_rot", 0, 1, "stage_rot: 0 or 1", set_stage_rot},   // phase B from a block-dependent window on
+    {"gemm_kern", -1, 2, "gemm_kern: -1 (auto), 0, 1 or 2", set_opt<&Opt::gemm_kern>},   // CRT GEMM kernel variant (bit-identical)
+    {"stage_batch", INT64_MIN, INT64_MAX, "", set_opt<&Opt::stage_batch>},   // small independent stages share k_stage_multi launches
+    {"f64_views", INT64_MIN, INT64_MAX, "", set_opt<&Opt::f64_views>},
+    {"p1_at", -1, 3, "p1_at: -1 (auto), 0, 1, 2 or 3", set_opt<&Opt::p1_at>},
+    {"dchk_at", 0, 2, "dchk_at: 0 (cell stream), 1 (st2) or 2 (st3)", set_opt<&Opt::dchk_at>},   // pipelined: the d checks' stream
+    {"gamma_at", -1, 1, "gamma_at: -1 (auto), 0 (cell stream) or 1 (st3)", set_opt<&Opt::gamma_at>},   // pipelined: k_gamma_prep's stream
+    {"overlap", INT64_MIN, INT64_MAX, "", set_opt<&Opt::overlap>},
+};
 // "lanes": exchange this state with the lane's (created on first use).
 static_assert(std::is_nothrow_move_constructible<svdw_ctx>::value && std::is_nothrow_move_assignable<svdw_ctx>::value, "svdw_ctx moves");
 static void lane_switch(svdw_ctx* c) {
@@ -3389,7 +3433,7 @@ static hipEvent_t xevent(svdw_ctx* c, int i);
 static svdw_counts verify_mul_witness_api(svdw_ctx* c, const double* a, const double* b, uint32_t N,
                                           uint32_t K, uint32_t M, bool on_device, const Fr& gamma,
                                           hipStream_t caller = nullptr, bool has_caller = false) {
-    const bool plain = on_device && !c->dry && !c->prof && !c->hold_us && !sharded(c) && N >= 1 && K >= 1 &&
+    const bool plain = on_device && !c->dry && !c->opt.prof && !c->opt.hold_us && !sharded(c) && N >= 1 && K >= 1 &&
                        M >= 1;
     if (plain && c->lanes > 1 && lane_fits(c)) lane_switch(c);
     if (has_caller && !c->dry) {
@@ -3398,7 +3442,7 @@ static svdw_counts verify_mul_witness_api(svdw_ctx* c, const double* a, const do
         hipck(hipStreamWaitEvent(c->st, e, 0), "hipStreamWaitEvent");
         c->xwait_side = e;                        // (st2 / st3: through st, see after_previous)
     }
-    const bool usable = c->graph_vm && plain;
+    const bool usable = c->opt.graph_vm && plain;
     if (!usable) {
         vmg_drop(c);
         c->vmg.seen.clear();
@@ -3411,27 +3455,27 @@ static svdw_counts verify_mul_witness_api(svdw_ctx* c, const double* a, const do
         hipStream_t s2 = nullptr, s3 = nullptr;
         bool on = false;
         explicit Linear(svdw_ctx* cc) : c(cc) {
-            if (!c->vm_linear) return;
+            if (!c->opt.vm_linear) return;
             if (!c->lin_ev) hipck(hipEventCreateWithFlags(&c->lin_ev, hipEventDisableTiming), "hipEventCreate");
             s2 = c->st2;
             s3 = c->st3;
             c->st2 = c->st3 = c->st;
-            c->linear = on = true;
+            c->call.linear = on = true;
         }
         ~Linear() {
             if (!on) return;
             c->st2 = s2;
             c->st3 = s3;
-            c->linear = false;
+            c->call.linear = false;
         }
     } lin{c};
-    struct Flags {
-        svdw_ctx* c;
+    struct Flags {                 // set here, ahead of verify_mul_witness, and kept over its eager
+        svdw_ctx* c;               // rerun below: this function's end clears them, not CallEnd
         ~Flags() {
-            c->gp_external = false;
-            c->capturing = false;
+            c->call.gp_external = false;
+            c->call.capturing = false;
             c->gp_ev = nullptr;
-            c->pows_pre.on = false;
+            c->call.pows_pre.on = false;
         }
     } flags{c};
     // gamma's tables (and the one / gamma-power cells when phase 1 holds them)
@@ -3443,8 +3487,8 @@ static svdw_counts verify_mul_witness_api(svdw_ctx* c, const double* a, const do
     const bool pw = vm_pow_cells(c, M, gamma, &pc);
     gamma_prep(c, M, gamma, c->st, pw ? &pc : nullptr);
     host_mark(c, "vm: gamma_prep queued");
-    c->gp_external = true;
-    c->gp_ext_one = pw ? pc.one : nullptr;
+    c->call.gp_external = true;
+    c->call.gp_ext_one = pw ? pc.one : nullptr;
     // (the cell set and gamma tables too: a pipelined svd_witness alternates between two)
     auto key_now = [&] {
         return std::vector<uint64_t>{N, K, M, (uint64_t)(uintptr_t)a, (uint64_t)(uintptr_t)b, c->epoch,
@@ -3466,7 +3510,7 @@ static svdw_counts verify_mul_witness_api(svdw_ctx* c, const double* a, const do
         vmg_drop(c);
         hipGraph_t graph = nullptr;
         hipck(hipStreamBeginCapture(c->st, hipStreamCaptureModeRelaxed), "hipStreamBeginCapture");
-        c->capturing = true;
+        c->call.capturing = true;
         svdw_counts k{};
         try {
             k = verify_mul_witness(c, a, b, N, K, M, on_device, gamma);
@@ -3474,14 +3518,14 @@ static svdw_counts verify_mul_witness_api(svdw_ctx* c, const double* a, const do
             if (c->st3) stream_dep(c, c->st3, c->st);
         } catch (...) {
             // nothing captured ran: end the capture and run the call eagerly
-            c->capturing = false;
+            c->call.capturing = false;
             graph = nullptr;
             if (hipStreamEndCapture(c->st, &graph) == hipSuccess && graph) (void)hipGraphDestroy(graph);
             (void)hipGetLastError();
             c->vmg.seen.clear();
             return verify_mul_witness(c, a, b, N, K, M, on_device, gamma);
         }
-        c->capturing = false;
+        c->call.capturing = false;
         hipck(hipStreamEndCapture(c->st, &graph), "hipStreamEndCapture");
         hipGraphExec_t exec = nullptr;
         const hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
@@ -3670,9 +3714,9 @@ int svdw_ctx_create(const svdw_params* p, svdw_ctx** out) {
         c->LB = p->lookup_bits;
         c->device = p->device;
         c->dry = p->device < 0;
-        if (const char* h = getenv("SVDW_HOST_TRACE")) c->host_trace = atoi(h) != 0;
+        if (const char* h = getenv("SVDW_HOST_TRACE")) c->opt.host_trace = atoi(h) != 0;
         if (const char* g = getenv("SVDW_GEMM"))
-            c->gemm_impl = (!strcmp(g, "valu") || !strcmp(g, "dot4")) ? SVDW_GEMM_VALU : SVDW_GEMM_MFMA;
+            c->opt.gemm_impl = (!strcmp(g, "valu") || !strcmp(g, "dot4")) ? SVDW_GEMM_VALU : SVDW_GEMM_MFMA;
         if (!c->dry) {
             try {
                 ctx_init_device(c);
@@ -3692,9 +3736,9 @@ int svdw_ctx_reset(svdw_ctx* c) {
         REQUIRE(c, "null ctx");
         sync(c);
         clear_streams(c);
-        c->pre.clear();
-        c->pre_wait_st = nullptr;
-        c->pre_wait_ev = nullptr;
+        c->call.pre.clear();
+        c->call.pre_wait_st = nullptr;
+        c->call.pre_wait_ev = nullptr;
     });
 }
 int svdw_reserve(svdw_ctx* c, uint32_t phase, uint64_t na, uint64_t nl) {
@@ -3879,10 +3923,7 @@ int svdw_zkvector_new(svdw_ctx* c, uint32_t phase, const double* data, uint32_t 
 int svdw_transpose_matrix(const svdw_mat* a, svdw_mat* out) {
     return guarded([&] {
         REQUIRE(a && out, "null argument");
-        svdw_mat t = *a;
-        std::swap(t.rows, t.cols);
-        std::swap(t.rs, t.cs);
-        *out = t;
+        *out = transposed(*a);
     });
 }
 int svdw_load_witness(svdw_ctx* c, uint32_t phase, const uint64_t value[4], svdw_vec* out) {
@@ -4347,8 +4388,8 @@ int svdw_set_shard(svdw_ctx* c, uint32_t rank, uint32_t world) {
         REQUIRE(c, "null ctx");
         REQUIRE(world >= 1 && rank < world, "svdw_set_shard: need rank < world");
         ++c->epoch;
-        c->shard_rank = rank;
-        c->shard_world = world;
+        c->opt.shard_rank = rank;
+        c->opt.shard_world = world;
         c->owned.clear();
     });
 }
@@ -4709,76 +4750,12 @@ int svdw_set_option(svdw_ctx* c, const char* name, int64_t value) {
         REQUIRE(c && name, "null argument");
         sync(c);
         ++c->epoch;                                  // a captured launch sequence may change
-        const std::string n(name);
-        if (n == "lanes") {                          // verify_mul_witness on two alternating states
-            REQUIRE(value == 1 || value == 2, "lanes: 1 or 2");
-            c->lanes = (int)value;
-        } else if (n == "pipeline") {                // pipelined svd_witness (svd_witness)
-            REQUIRE(value == 0 || value == 1, "pipeline: 0 or 1");
-            c->pipeline = (int)value;
-            if (!value) {                            // the other cell set is not needed any more
-                release_alt(c);
-                if (c->lane) release_alt(c->lane);
+        for (const OptionDef& o : kOptions)
+            if (!strcmp(o.name, name)) {
+                REQUIRE(value >= o.lo && value <= o.hi, o.msg);
+                return o.set(c, value);
             }
-        } else if (n == "vm_linear") {               // captured verify_mul_witness on one stream
-            REQUIRE(value == 0 || value == 1, "vm_linear: 0 or 1");
-            c->vm_linear = (int)value;
-        } else if (n == "graph") {                   // captured verify_mul_witness (vm_graph)
-            REQUIRE(value == 0 || value == 1, "graph: 0 or 1");
-            c->graph_vm = (int)value;
-        } else if (n == "gemm_impl") {
-            REQUIRE(value == SVDW_GEMM_MFMA || value == SVDW_GEMM_VALU, "gemm_impl: 0 (mfma) or 1 (valu)");
-            c->gemm_impl = (int)value;
-        } else if (n == "stage_elems") {
-            REQUIRE(value >= 16 && value <= 256 && value % 16 == 0,
-                    "stage_elems: a multiple of 16 in [16, 256]");
-            c->stage_elems = (uint32_t)value;
-        } else if (n == "prod_cell") {
-            REQUIRE(value >= -1 && value <= 1, "prod_cell: -1, 0 or 1");
-            c->prod_cell = (int)value;
-        } else if (n == "phase1_overlap") {
-            REQUIRE(value >= 0 && value <= 2, "phase1_overlap: 0, 1 or 2");
-            c->phase1_overlap = (int)value;
-        } else if (n == "hold_us") {         // timing aid: GPU-only schedule of a witness
-            REQUIRE(value >= 0 && value <= 100000, "hold_us: 0..100000");
-            c->hold_us = (uint32_t)value;
-        } else if (n == "rlc_prefix") {
-            c->rlc_prefix = value != 0;
-        } else if (n == "res_f64") {
-            c->res_f64 = value != 0;
-        } else if (n == "gemm_crt") {
-            REQUIRE(value == 0 || value == 1, "gemm_crt: 0 or 1");
-            c->gemm_crt = (int)value;
-        } else if (n == "res_wait") {                // pipelined: st2 waits for the residue planes
-            REQUIRE(value >= -1 && value <= 1, "res_wait: -1 (auto), 0 or 1");
-            c->res_wait = (int)value;
-        } else if (n == "place_trials") {            // cell streams >= 256 MiB: best of this many placements
-            REQUIRE(value >= 0 && value <= 8, "place_trials: 0..8");
-            c->place_trials = (int)value;
-        } else if (n == "stage_rot") {               // phase B from a block-dependent window on
-            REQUIRE(value == 0 || value == 1, "stage_rot: 0 or 1");
-            c->stage_flags = value ? (c->stage_flags | STAGE_ROT) : (c->stage_flags & ~STAGE_ROT);
-        } else if (n == "gemm_kern") {               // CRT GEMM kernel variant (bit-identical)
-            REQUIRE(value >= -1 && value <= 2, "gemm_kern: -1 (auto), 0, 1 or 2");
-            c->gemm_kern = (int)value;
-        } else if (n == "stage_batch") {          // small independent stages share k_stage_multi launches
-            c->stage_batch = value != 0;
-        } else if (n == "f64_views") {
-            c->f64_views = value != 0;
-        } else if (n == "p1_at") {
-            REQUIRE(value >= -1 && value <= 3, "p1_at: -1 (auto), 0, 1, 2 or 3");
-            c->p1_at = (int)value;
-        } else if (n == "dchk_at") {                 // pipelined: the d checks' stream
-            REQUIRE(value >= 0 && value <= 2, "dchk_at: 0 (cell stream), 1 (st2) or 2 (st3)");
-            c->dchk_at = (int)value;
-        } else if (n == "gamma_at") {                // pipelined: k_gamma_prep's stream
-            REQUIRE(value >= -1 && value <= 1, "gamma_at: -1 (auto), 0 (cell stream) or 1 (st3)");
-            c->gamma_at = (int)value;
-        } else if (n == "overlap") {
-            c->overlap = value != 0;
-        } else {
-            fail(SVDW_EINVAL, "unknown option " + n);
-        }
+        fail(SVDW_EINVAL, std::string("unknown option ") + name);
     });
 }
 int svdw_graph_stats(svdw_ctx* c, uint64_t* captures, uint64_t* replays) {
@@ -4794,7 +4771,7 @@ int svdw_set_gemm_impl(svdw_ctx* c, int impl) {
         REQUIRE(impl == SVDW_GEMM_MFMA || impl == SVDW_GEMM_VALU, "unknown GEMM implementation");
         sync(c);
         ++c->epoch;
-        c->gemm_impl = impl;
+        c->opt.gemm_impl = impl;
     });
 }
 int svdw_profile_enable(svdw_ctx* c, int on) {
@@ -4803,13 +4780,13 @@ int svdw_profile_enable(svdw_ctx* c, int on) {
         sync(c);
         for (auto& r : c->recs) { c->pool.push_back(r.e0); c->pool.push_back(r.e1); }
         c->recs.clear();
-        c->prof = on != 0;
+        c->opt.prof = on != 0;
     });
 }
 int svdw_profile_filter(svdw_ctx* c, const char* prefix) {
     return guarded([&] {
         REQUIRE(c, "null ctx");
-        c->prof_filter = prefix ? prefix : "";
+        c->opt.prof_filter = prefix ? prefix : "";
     });
 }
 int svdw_profile_collect(svdw_ctx* c, svdw_kstat* out, uint32_t cap, uint32_t* n) {

@@ -151,6 +151,58 @@ def test_removed_options_are_rejected():
         ctx.close()
 
 
+def test_every_option_keeps_its_range():
+    """Every svdw_set_option name with its accepted range (both bounds set, one
+    below and one above are SVDW_EINVAL), the options that take any integer,
+    and an unknown name; with every option back at its default the context
+    plans the same witness as a fresh one."""
+    L = _lib.lib()
+    ranged = {"lanes": (1, 2), "pipeline": (0, 1), "vm_linear": (0, 1), "graph": (0, 1),
+              "gemm_impl": (0, 1), "gemm_crt": (0, 1), "stage_rot": (0, 1),
+              "prod_cell": (-1, 1), "res_wait": (-1, 1), "gamma_at": (-1, 1),
+              "phase1_overlap": (0, 2), "dchk_at": (0, 2), "gemm_kern": (-1, 2),
+              "p1_at": (-1, 3), "place_trials": (0, 8), "hold_us": (0, 100000)}
+    boolean = ("rlc_prefix", "res_f64", "stage_batch", "f64_views", "overlap")
+    defaults = {"lanes": 2, "pipeline": 1, "vm_linear": 1, "graph": 1, "gemm_impl": 0,
+                "gemm_crt": 1, "stage_rot": 1, "prod_cell": 1, "res_wait": -1, "gamma_at": -1,
+                "phase1_overlap": 1, "dchk_at": 0, "gemm_kern": -1, "p1_at": -1,
+                "place_trials": 6, "hold_us": 0, "stage_elems": 256, "rlc_prefix": 0,
+                "res_f64": 1, "stage_batch": 1, "f64_views": 1, "overlap": 1}
+    assert set(defaults) == set(ranged) | set(boolean) | {"stage_elems"}
+    N, M, P, LB = 24, 20, 63, 19
+    m, u, d, v = gen_svd_input(N, M, seed=5)
+    ctx = hs.Context(device=-1, precision_bits=P, lookup_bits=LB)
+    fresh = hs.Context(device=-1, precision_bits=P, lookup_bits=LB)
+    try:
+        def set_(name, value):
+            return L.svdw_set_option(ctx.handle, name.encode(), value)
+
+        for name, (lo, hi) in ranged.items():
+            assert set_(name, lo) == 0, (name, lo)
+            assert set_(name, hi) == 0, (name, hi)
+            for bad in (lo - 1, hi + 1):
+                assert set_(name, bad) == -1, (name, bad)
+                assert name.encode() in L.svdw_last_error(), (name, bad)
+        for ok in (16, 128, 256):
+            assert set_("stage_elems", ok) == 0, ok
+        for bad in (0, 8, 24, 272):
+            assert set_("stage_elems", bad) == -1, bad
+            assert b"stage_elems" in L.svdw_last_error()
+        for name in boolean:
+            for value in (-1, 0, 7):
+                assert set_(name, value) == 0, (name, value)
+        assert set_("no_such_option", 1) == -1
+        assert b"unknown option" in L.svdw_last_error()
+        for name, value in defaults.items():
+            assert set_(name, value) == 0, (name, value)
+        got = hs.svd_witness(ctx, m, u, v, d, 3)
+        assert got == hs.svd_witness(fresh, m, u, v, d, 3)
+        assert got == hs.plan_svd(N, M, P, LB)
+    finally:
+        ctx.close()
+        fresh.close()
+
+
 def test_completion_marks_dry():
     """svdw_mark / svdw_mark_done / svdw_mark_wait on the planning context:
     tickets count up from 1, a dry context's marks are complete at once, and a
