@@ -95,6 +95,26 @@ int main(int argc, char** argv) {
     printf("advice0[0] = %016llx%016llx%016llx%016llx (m[0][0]=%.17g)\n",
            (unsigned long long)cell[3], (unsigned long long)cell[2],
            (unsigned long long)cell[1], (unsigned long long)cell[0], m[0]);
+    /* the same cell as halo2curves holds it in memory (Fr([u64; 4]), Montgomery form) */
+    uint64_t mont[4], back[4];
+    CHECK(svdw_copy_cells(ctx, 0, 0, 0, 1, SVDW_FORM_MONTGOMERY, mont));
+    printf("  montgomery = %016llx%016llx%016llx%016llx\n",
+           (unsigned long long)mont[3], (unsigned long long)mont[2],
+           (unsigned long long)mont[1], (unsigned long long)mont[0]);
+    CHECK(svdw_fr_convert(mont, 1, SVDW_FORM_MONTGOMERY, SVDW_FORM_CANONICAL, back));
+    if (back[0] != cell[0] || back[1] != cell[1] || back[2] != cell[2] || back[3] != cell[3]) {
+        fprintf(stderr, "Montgomery round trip differs\n");
+        return 1;
+    }
+    /* ZkVector::dequantize of d (loaded after m, u, v) */
+    const uint32_t nd = N < M ? N : M;
+    svdw_vec dv = {0, nd, (uint64_t)N * M + (uint64_t)N * N + (uint64_t)M * M, 1};
+    double* dq = malloc(sizeof(double) * nd);
+    CHECK(svdw_dequantize_vec(ctx, &dv, dq, 0));
+    printf("d dequantized = [");
+    for (uint32_t i = 0; i < nd && i < 4; ++i) printf("%s%.17g", i ? ", " : "", dq[i]);
+    printf("%s] (d[0]=%.17g)\n", nd > 4 ? ", ..." : "", d[0]);
+    free(dq);
     /* README.md:93: "SVD should verify on matrix but fail on matrix-wrong" */
     svdw_check_result chk;
     CHECK(svdw_check_gates(ctx, &chk));

@@ -188,6 +188,16 @@ SIGNATURES = {
                                   ct.POINTER(Vec)]),
     "svdw_check_equalities": (_i32, [_P, _u32, _P, _P, ct.POINTER(EqCheck)]),
     "svdw_profile_collect": (_i32, [_P, ct.POINTER(KStat), _u32, ct.POINTER(_u32)]),
+    "svdw_export_cells": (_i32, [_P, _u32, _i32, _u64, _u64, _i32, _P]),
+    "svdw_copy_cells": (_i32, [_P, _u32, _i32, _u64, _u64, _i32, _P]),
+    "svdw_export_mat": (_i32, [_P, ct.POINTER(Mat), _i32, _P, _i32]),
+    "svdw_export_vec": (_i32, [_P, ct.POINTER(Vec), _i32, _P, _i32]),
+    "svdw_dequantize_mat": (_i32, [_P, ct.POINTER(Mat), _P, _i32]),
+    "svdw_dequantize_vec": (_i32, [_P, ct.POINTER(Vec), _P, _i32]),
+    "svdw_assign_columns_form": (_i32, [_P, _u32, _i32, _P, _P, _P]),
+    "svdw_fr_convert": (_i32, [_P, _u64, _i32, _i32, _P]),
+    "svdw_quantization": (_i32, [_dbl, _u32, _P]),
+    "svdw_dequantization": (_i32, [_P, _u32, ct.POINTER(_dbl)]),
     "svdw_plan_svd": (_i32, [_u32, _u32, _u32, _u32, ct.POINTER(SvdConfig), ct.POINTER(Counts)]),
 }
 

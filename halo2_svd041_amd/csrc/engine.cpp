@@ -29,6 +29,7 @@
 #include "ingest.hpp"
 #include "ingest_dev.hpp"
 #include "kernels.hpp"
+#include "export.hpp"
 
 using namespace svdw;
 
@@ -664,6 +665,12 @@ struct svdw_ctx {
     DBuf ing_x, ing_e, ing_c, ing_p10, ing_val, ing_npos, ing_nd, ing_rpos, ing_kpos, ing_err, ing_q;
     // device equality records (eq_gen_device)
     DBuf eq_cp, eq_ks, eq_reg, eq_w, eq_k, eq_err, eq_st;
+    // read-out (svdw_copy_cells, the host variants of svdw_export_* / svdw_dequantize_*):
+    // two staging halves of at most kExportChunk bytes each, and the events that
+    // order them ([0..1] half converted, [2..3] half copied out, [4..5] the join
+    // of st2 / st3 into st ahead of every read-out)
+    DBuf exp_buf[2];
+    hipEvent_t exp_ev[6] = {};
     // ---- captured verify_mul_witness ("graph", vm_graph): the launch sequence of
     // a device-input call is captured once into a HIP graph (the second call of
     // a shape, when every buffer is sized) and replayed by later calls of the
@@ -3266,7 +3273,7 @@ static std::vector<DBuf*> dbufs(svdw_ctx* c) {
                             &c->gtab_alt, &c->crtR, &c->gbits, &c->colpart, &c->qfold, &c->ing_x, &c->ing_e,
                             &c->ing_c, &c->ing_p10, &c->ing_val, &c->ing_npos, &c->ing_nd, &c->ing_rpos,
                             &c->ing_kpos, &c->ing_err, &c->ing_q, &c->eq_cp, &c->eq_ks, &c->eq_reg, &c->eq_w,
-                            &c->eq_k, &c->eq_err, &c->eq_st};
+                            &c->eq_k, &c->eq_err, &c->eq_st, &c->exp_buf[0], &c->exp_buf[1]};
     for (int i = 0; i < kMaxScanJobs; ++i) {
         v.push_back(&c->wbc[i]);
         v.push_back(&c->wbt[i]);
@@ -3299,6 +3306,8 @@ static void ctx_release(svdw_ctx* c) {
         if (c->hbits) (void)hipHostFree(c->hbits);
         if (c->ev_bits) (void)hipEventDestroy(c->ev_bits);
         for (auto e : c->xev)
+            if (e) (void)hipEventDestroy(e);
+        for (auto e : c->exp_ev)
             if (e) (void)hipEventDestroy(e);
         for (auto& m : c->mk.ev)
             for (auto e : m)
@@ -3903,6 +3912,184 @@ int svdw_copy_advice(svdw_ctx* c, uint32_t phase, uint64_t off, uint64_t n, uint
 }
 int svdw_copy_lookup(svdw_ctx* c, uint32_t phase, uint64_t off, uint64_t n, uint64_t* out) {
     return copy_cells(c, phase, off, n, out, true);
+}
+
+// ------------------------------------------------------------- read-out
+// Cells in the form the consumer holds them (export.hpp): a stream range or a
+// view, canonical or Montgomery, or dequantized to f64; into device memory
+// (queued, no host wait) or host memory (staged through bounded scratch).
+static constexpr size_t kExportChunk = 64ull << 20;       // bytes of cells per staging half
+static void check_form(int form) {
+    REQUIRE(form == SVDW_FORM_CANONICAL || form == SVDW_FORM_MONTGOMERY,
+            "unknown form (SVDW_FORM_CANONICAL or SVDW_FORM_MONTGOMERY)");
+}
+static hipEvent_t export_event(svdw_ctx* c, int i) {
+    if (!c->exp_ev[i])
+        hipck(hipEventCreateWithFlags(&c->exp_ev[i], hipEventDisableTiming), "hipEventCreate");
+    return c->exp_ev[i];
+}
+// The cell stream behind everything queued on the context so far: a pipelined
+// witness's tail (settle) and whatever a call left on the side streams.
+static void export_join(svdw_ctx* c) {
+    settle(c);
+    flush_batch(c, c->st);
+    int i = 4;
+    for (hipStream_t t : {c->st2, c->st3}) {
+        const hipEvent_t e = export_event(c, i++);
+        if (!t || t == c->st) continue;
+        flush_batch(c, t);
+        hipck(hipEventRecord(e, t), "hipEventRecord");
+        hipck(hipStreamWaitEvent(c->st, e, 0), "hipStreamWaitEvent");
+    }
+}
+static ExportSrc range_src(svdw_ctx* c, uint32_t phase, int lookup, uint64_t off, uint64_t n) {
+    REQUIRE(phase < 2, "phase must be 0 or 1");
+    REQUIRE(!c->dry, "planning context has no cells");
+    const Stream& s = c->ph[phase];
+    const uint64_t len = lookup ? s.nl : s.n;
+    REQUIRE(off <= len && n <= len - off, "export range outside the stream");
+    return ExportSrc{lookup ? s.lk : s.adv, off, n, 0, 0, 0, 0};
+}
+static ExportSrc view_src(svdw_ctx* c, const svdw_mat& m) {
+    REQUIRE(!c->dry, "planning context has no cells");
+    check_mat(c, m);
+    return ExportSrc{c->ph[m.phase].adv, m.off, (uint64_t)m.rows * m.cols, 0, m.rs, m.cs, m.cols};
+}
+// cells [k0, k0 + cnt) of s
+static ExportSrc sub_src(const ExportSrc& s, uint64_t k0, uint64_t cnt) {
+    ExportSrc r = s;
+    r.n = cnt;
+    if (s.cols) r.k0 = s.k0 + k0;
+    else r.off = s.off + k0;
+    return r;
+}
+// conv(sub, dev): queue the conversion of `sub` into device memory dev on st;
+// esz: bytes per converted cell. Into device memory in one launch; into host
+// memory in chunks through the two staging halves, chunk k + 1's conversion (st)
+// beside chunk k's copy (st2), then waits.
+static void export_run(svdw_ctx* c, const ExportSrc& s, size_t esz, void* dst, bool on_device,
+                       const std::function<void(const ExportSrc&, void*)>& conv) {
+    if (!s.n) return;
+    if (on_device) {
+        export_join(c);
+        conv(s, dst);
+        return;
+    }
+    const uint64_t chunk = kExportChunk / sizeof(Fr);      // cells per half
+    for (int h = 0; h < (s.n > chunk ? 2 : 1); ++h)        // (allocating synchronises: first)
+        ensure_buf(c, c->exp_buf[h], (size_t)std::min(s.n, chunk) * esz);
+    export_join(c);
+    const hipStream_t cp = c->st2 && c->st2 != c->st ? c->st2 : c->st;
+    uint64_t k0 = 0;
+    for (uint64_t i = 0; k0 < s.n; ++i, k0 += chunk) {
+        const int h = (int)(i & 1);
+        const uint64_t cnt = std::min(chunk, s.n - k0);
+        if (i >= 2) hipck(hipStreamWaitEvent(c->st, export_event(c, 2 + h), 0), "hipStreamWaitEvent");
+        conv(sub_src(s, k0, cnt), c->exp_buf[h].p);
+        hipck(hipEventRecord(export_event(c, h), c->st), "hipEventRecord");
+        hipck(hipStreamWaitEvent(cp, export_event(c, h), 0), "hipStreamWaitEvent");
+        hipck(hipMemcpyAsync((char*)dst + k0 * esz, c->exp_buf[h].p, cnt * esz, hipMemcpyDeviceToHost, cp), "D2H");
+        hipck(hipEventRecord(export_event(c, 2 + h), cp), "hipEventRecord");
+    }
+    sync(c);
+}
+static void export_cells_to(svdw_ctx* c, const ExportSrc& s, int form, void* dst, bool on_device) {
+    if (!on_device && form == SVDW_FORM_CANONICAL && !s.cols) {   // straight from the stream
+        if (!s.n) return;
+        export_join(c);
+        hipck(hipMemcpyAsync(dst, s.src + s.off, s.n * sizeof(Fr), hipMemcpyDeviceToHost, c->st), "D2H");
+        sync(c);
+        return;
+    }
+    export_run(c, s, sizeof(Fr), dst, on_device, [&](const ExportSrc& sub, void* dev) {
+        ProfScope ps(c, c->st, form == SVDW_FORM_MONTGOMERY ? "k_export_mont" : "k_export", 64.0 * (double)sub.n, 0);
+        hipck(launch_export(sub, form, (Fr*)dev, 0, c->st), "k_export");
+    });
+}
+static void dequantize_to(svdw_ctx* c, const ExportSrc& s, double* dst, bool on_device) {
+    export_run(c, s, sizeof(double), dst, on_device, [&](const ExportSrc& sub, void* dev) {
+        ProfScope ps(c, c->st, "k_dequantize", 40.0 * (double)sub.n, 0);
+        hipck(launch_dequantize(sub, c->P, (double*)dev, c->st), "k_dequantize");
+    });
+}
+int svdw_export_cells(svdw_ctx* c, uint32_t phase, int lookup, uint64_t off, uint64_t n, int form, void* dst) {
+    return guarded([&] {
+        REQUIRE(c && dst, "null argument");
+        check_form(form);
+        export_cells_to(c, range_src(c, phase, lookup, off, n), form, dst, true);
+    });
+}
+int svdw_copy_cells(svdw_ctx* c, uint32_t phase, int lookup, uint64_t off, uint64_t n, int form, uint64_t* out) {
+    return guarded([&] {
+        REQUIRE(c && out, "null argument");
+        check_form(form);
+        export_cells_to(c, range_src(c, phase, lookup, off, n), form, out, false);
+    });
+}
+int svdw_export_mat(svdw_ctx* c, const svdw_mat* a, int form, void* dst, int on_device) {
+    return guarded([&] {
+        REQUIRE(c && a && dst, "null argument");
+        check_form(form);
+        export_cells_to(c, view_src(c, *a), form, dst, on_device != 0);
+    });
+}
+int svdw_export_vec(svdw_ctx* c, const svdw_vec* v, int form, void* dst, int on_device) {
+    return guarded([&] {
+        REQUIRE(c && v && dst, "null argument");
+        check_form(form);
+        export_cells_to(c, view_src(c, mat_of_vec(*v)), form, dst, on_device != 0);
+    });
+}
+int svdw_dequantize_mat(svdw_ctx* c, const svdw_mat* a, double* out, int on_device) {
+    return guarded([&] {
+        REQUIRE(c && a && out, "null argument");
+        dequantize_to(c, view_src(c, *a), out, on_device != 0);
+    });
+}
+int svdw_dequantize_vec(svdw_ctx* c, const svdw_vec* v, double* out, int on_device) {
+    return guarded([&] {
+        REQUIRE(c && v && out, "null argument");
+        dequantize_to(c, view_src(c, mat_of_vec(*v)), out, on_device != 0);
+    });
+}
+// Host helpers (fr.hpp / export.hpp on the host, no context, no GPU).
+static Fr fr_raw_words(const uint64_t w[4]) { return big_from_words(w).v; }
+static void fr_store_words(const Fr& x, uint64_t w[4]) {
+    for (int i = 0; i < 4; ++i) w[i] = (uint64_t)x.w[2 * i] | ((uint64_t)x.w[2 * i + 1] << 32);
+}
+static bool fr_reduced(const Fr& x) {
+    Fr t;
+    return sub_p(t, x) != 0;                               // x - p borrows: x < p
+}
+int svdw_fr_convert(const uint64_t* in, uint64_t n, int from, int to, uint64_t* out) {
+    return guarded([&] {
+        REQUIRE(n == 0 || (in && out), "null argument");
+        check_form(from);
+        check_form(to);
+        for (uint64_t i = 0; i < n; ++i)
+            REQUIRE(fr_reduced(fr_raw_words(in + 4 * i)), "svdw_fr_convert: input value >= p");
+        for (uint64_t i = 0; i < n; ++i) {
+            Fr x = fr_raw_words(in + 4 * i);
+            if (from != to) x = to == SVDW_FORM_MONTGOMERY ? fr_to_mont(x) : fr_from_mont(x);
+            fr_store_words(x, out + 4 * i);
+        }
+    });
+}
+int svdw_quantization(double x, uint32_t precision_bits, uint64_t out[4]) {
+    return guarded([&] {
+        REQUIRE(out, "null argument");
+        if (precision_bits < 1 || precision_bits > 63) fail(SVDW_ERANGE, "precision_bits must be in [1, 63]");
+        fr_store_words(quantize_fr(x, ldexp(1.0, (int)precision_bits)), out);
+    });
+}
+int svdw_dequantization(const uint64_t value[4], uint32_t precision_bits, double* out) {
+    return guarded([&] {
+        REQUIRE(value && out, "null argument");
+        if (precision_bits < 1 || precision_bits > 63) fail(SVDW_ERANGE, "precision_bits must be in [1, 63]");
+        const Fr x = fr_raw_words(value);
+        REQUIRE(fr_reduced(x), "svdw_dequantization: value >= p");
+        *out = dequantize_fr(x, precision_bits);
+    });
 }
 
 int svdw_zkmatrix_new(svdw_ctx* c, uint32_t phase, const double* data, uint32_t rows,
@@ -4560,9 +4747,24 @@ int svdw_break_points(const svdw_ctx* c, uint32_t phase, uint64_t* out, uint64_t
         for (uint64_t i = 0; i < cap && i < b.size() && out; ++i) out[i] = b[i];
     });
 }
+// One column's cells: the stream range [s, s + len) then zero rows up to `rows`.
+// Canonical: a device copy and a memset; Montgomery: converted while it is
+// written (k_export pads the column itself), no second pass over the column.
+static void assign_column(svdw_ctx* c, int form, const Fr* stream, uint64_t s, uint64_t len, uint64_t rows, Fr* dst) {
+    if (form == SVDW_FORM_MONTGOMERY) {
+        hipck(launch_export(ExportSrc{stream, s, len, 0, 0, 0, 0}, form, dst, rows - len, c->st), "k_export");
+        return;
+    }
+    hipck(hipMemcpyAsync(dst, stream + s, len * sizeof(Fr), hipMemcpyDeviceToDevice, c->st), "D2D");
+    if (len < rows) hipck(hipMemsetAsync(dst + len, 0, (rows - len) * sizeof(Fr), c->st), "hipMemsetAsync");
+}
 int svdw_assign_columns(svdw_ctx* c, uint32_t phase, void* advice, uint8_t* selectors, void* lookup) {
+    return svdw_assign_columns_form(c, phase, SVDW_FORM_CANONICAL, advice, selectors, lookup);
+}
+int svdw_assign_columns_form(svdw_ctx* c, uint32_t phase, int form, void* advice, uint8_t* selectors, void* lookup) {
     return guarded([&] {
         REQUIRE(c && phase < 2, "bad argument");
+        check_form(form);
         REQUIRE(!c->dry, "svdw_assign_columns needs a device context");
         REQUIRE(c->phys.valid, "svdw_assign_columns: call svdw_physical_layout after the witness");
         sync(c);
@@ -4593,11 +4795,7 @@ int svdw_assign_columns(svdw_ctx* c, uint32_t phase, void* advice, uint8_t* sele
             const bool last = col + 1 == ncols;
             const uint64_t len = last ? T - s : P.bp[phase][col] + 1;
             if (advice) {
-                Fr* dst = (Fr*)advice + col * rows;
-                hipck(hipMemcpyAsync(dst, c->ph[phase].adv + s, len * sizeof(Fr), hipMemcpyDeviceToDevice,
-                                     c->st), "D2D");
-                if (len < rows)
-                    hipck(hipMemsetAsync(dst + len, 0, (rows - len) * sizeof(Fr), c->st), "hipMemsetAsync");
+                assign_column(c, form, c->ph[phase].adv, s, len, rows, (Fr*)advice + col * rows);
             }
             if (selectors)
                 hipck(launch_selectors(selectors + col * rows, (const uint32_t*)c->gateq[phase].p, s, len,
@@ -4607,10 +4805,7 @@ int svdw_assign_columns(svdw_ctx* c, uint32_t phase, void* advice, uint8_t* sele
             const uint64_t nl = (TL + P.R - 1) / P.R;
             for (uint64_t col = 0; col < nl; ++col) {
                 const uint64_t s = col * P.R, len = std::min(P.R, TL - s);
-                Fr* dst = (Fr*)lookup + col * rows;
-                hipck(hipMemcpyAsync(dst, c->ph[phase].lk + s, len * sizeof(Fr), hipMemcpyDeviceToDevice,
-                                     c->st), "D2D");
-                hipck(hipMemsetAsync(dst + len, 0, (rows - len) * sizeof(Fr), c->st), "hipMemsetAsync");
+                assign_column(c, form, c->ph[phase].lk, s, len, rows, (Fr*)lookup + col * rows);
             }
         }
         hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");

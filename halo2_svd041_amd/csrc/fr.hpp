@@ -3,8 +3,9 @@
 // Representation: 8 x u32 little-endian limbs. In memory a canonical Fr is
 // byte-identical to halo2curves' `Fr::to_repr()` (32-byte little endian),
 // which is the cell format of every advice / lookup stream this engine
-// writes. Montgomery form (x * 2^256 mod p) is used only inside products:
-// mont_mul(a_canonical, b_montgomery) == a*b canonical.
+// writes. Montgomery form (x * 2^256 mod p) is used inside products,
+// mont_mul(a_canonical, b_montgomery) == a*b canonical, and on request by the
+// read-out kernels (export.hip: halo2curves' in-memory Fr is that form).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -17,42 +17,12 @@
 
 #include "kernels.hpp"
 #include "crt_tables.hpp"
+#include "export.hpp"
 
 namespace svdw {
 
 // ----------------------------------------------------------------- helpers
-__device__ __forceinline__ Fr ld_fr(const Fr* p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    uint4 a = q[0], b = q[1];
-    Fr r;
-    r.w[0] = a.x; r.w[1] = a.y; r.w[2] = a.z; r.w[3] = a.w;
-    r.w[4] = b.x; r.w[5] = b.y; r.w[6] = b.z; r.w[7] = b.w;
-    return r;
-}
-__device__ __forceinline__ void st_fr(Fr* p, const Fr& v) {
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(v.w[0], v.w[1], v.w[2], v.w[3]);
-    q[1] = make_uint4(v.w[4], v.w[5], v.w[6], v.w[7]);
-}
-// ZkMatrix::new's quantization of one f64 (quantize_body's arithmetic):
-// x_q = round_half_away(|x| 2^P) as u128 (saturating, NaN -> 0), sign(x) < 0
-// (incl. -0.0) -> p - x_q.
-__device__ __forceinline__ Fr quantize_fr(double x, double scale) {
-    const bool neg = signbit(x) && !isnan(x);
-    const double s = round(fabs(x) * scale);
-    Fr q = fr_zero();
-    if (s >= 340282366920938463463374607431768211456.0) {
-        q.w[0] = q.w[1] = q.w[2] = q.w[3] = 0xffffffffu;
-    } else if (s > 0.0) {
-        const uint64_t bits = __double_as_longlong(s);
-        const int e = (int)((bits >> 52) & 0x7ff) - 1075;
-        const uint64_t mant = (bits & 0xfffffffffffffull) | (1ull << 52);
-        const unsigned __int128 v = e >= 0 ? ((unsigned __int128)mant << e) : (unsigned __int128)(mant >> -e);
-        q.w[0] = (uint32_t)v; q.w[1] = (uint32_t)(v >> 32);
-        q.w[2] = (uint32_t)(v >> 64); q.w[3] = (uint32_t)(v >> 96);
-    }
-    return neg ? fr_sub(fr_zero(), q) : q;
-}
+// (ld_fr, st_fr and quantize_fr: export.hpp, shared with the read-out kernels)
 __device__ __forceinline__ double f64_scale(const DView& v) { return ldexp(1.0, (int)v._r0); }
 // X(i, j) of a view; `pad` is the value outside the view (K[v.pad_k]).
 __device__ __forceinline__ Fr view_load(const DView v, const Fr pad, uint32_t i, uint32_t j) {

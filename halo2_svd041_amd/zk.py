@@ -28,7 +28,8 @@ P_MOD = 218882428718392752222464057452572750885483644004160343436982041865758084
 __all__ = ["Context", "ZkMatrix", "ZkVector", "honest_prover_mat_mul", "field_mat_vec_mul",
            "mat_times_diag_mat", "check_mat_diff", "check_mat_id", "check_mat_entries_bounded",
            "check_svd_phase0", "check_svd_phase1", "err_calc", "svd_witness", "plan_svd",
-           "SvdwError", "SvdPayload", "SvdConfigPy", "P_MOD", "int_to_words", "words_to_int"]
+           "SvdwError", "SvdPayload", "SvdConfigPy", "P_MOD", "int_to_words", "words_to_int",
+           "fr_convert", "quantization", "dequantization", "format_f64_debug"]
 
 
 def int_to_words(x: int) -> np.ndarray:
@@ -51,6 +52,73 @@ def _words_arg(x: int):
 def words_to_int(w) -> int:
     w = [int(v) for v in w]
     return w[0] | (w[1] << 64) | (w[2] << 128) | (w[3] << 192)
+
+
+FORMS = {"canonical": 0, "montgomery": 1}
+
+
+def _form(form) -> int:
+    try:
+        return FORMS[form]
+    except KeyError:
+        raise SvdwError(-1, f"unknown form {form!r} (canonical or montgomery)") from None
+
+
+def fr_convert(values, from_: str, to: str) -> np.ndarray:
+    """Field elements between the canonical (Fr::to_repr) and Montgomery
+    (halo2curves' in-memory [u64; 4], x * 2^256 mod p) forms on the host
+    (svdw_fr_convert): `values` is an (n, 4) uint64 array or a sequence of
+    ints; returns (n, 4) uint64. A value >= p raises SVDW_EINVAL."""
+    if isinstance(values, np.ndarray):
+        a = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
+    else:
+        a = np.array([int_to_words(v) for v in values], dtype=np.uint64).reshape(-1, 4)
+    out = np.empty_like(a)
+    check(lib().svdw_fr_convert(a.ctypes.data, a.shape[0], _form(from_), _form(to), out.ctypes.data))
+    return out
+
+
+def quantization(x: float, precision_bits: int) -> int:
+    """FixedPointChip041::quantization of one f64 (svdw_quantization)."""
+    w = (ct.c_uint64 * 4)()
+    check(lib().svdw_quantization(float(x), precision_bits, w))
+    return words_to_int(w)
+
+
+def dequantization(value: int, precision_bits: int) -> float:
+    """FixedPointChip041::dequantization of one field element
+    (svdw_dequantization; parity unpinned, include/svdw.h)."""
+    out = ct.c_double()
+    check(lib().svdw_dequantization(_words_arg(value), precision_bits, ct.byref(out)))
+    return out.value
+
+
+def format_f64_debug(x: float) -> str:
+    """Rust's `{:?}` of an f64: the shortest digits that round-trip, always
+    with a fractional part (1.0), exponent form below 1e-5 and from 1e16 on."""
+    x = float(x)
+    if x != x:
+        return "NaN"
+    if x in (float("inf"), float("-inf")):
+        return "inf" if x > 0 else "-inf"
+    sign = "-" if np.signbit(x) else ""
+    if x == 0:
+        return sign + "0.0"
+    import decimal
+    _, dig, exp = decimal.Decimal(repr(abs(x))).as_tuple()      # repr: shortest round-trip digits
+    digits = "".join(map(str, dig)).lstrip("0")
+    stripped = digits.rstrip("0")
+    exp += len(digits) - len(stripped)
+    digits = stripped
+    e10 = len(digits) - 1 + exp                                  # x = d.ddd * 10^e10
+    if abs(x) < 1e-5 or abs(x) >= 1e16:
+        frac = "." + digits[1:] if len(digits) > 1 else ""
+        return f"{sign}{digits[0]}{frac}e{e10}"
+    if exp >= 0:
+        return sign + digits + "0" * exp + ".0"
+    if -exp < len(digits):
+        return sign + digits[:exp] + "." + digits[exp:]
+    return sign + "0." + "0" * (-exp - len(digits)) + digits
 
 
 _torch = None
@@ -239,6 +307,30 @@ class Context:
         check(lib().svdw_copy_lookup(self._h, phase, off, n, out.ctypes.data))
         return out
 
+    def cells(self, phase: int, lookup: bool = False, off: int = 0, n: Optional[int] = None,
+              form: str = "canonical", device: bool = False):
+        """Cells [off, off + n) of a phase's advice (or lookup) stream in `form`
+        ("canonical": Fr::to_repr; "montgomery": halo2curves' in-memory
+        [u64; 4]), converted on the device. (n, 4) uint64 numpy array
+        (svdw_copy_cells), or with device=True a uint8 [n, 32] torch tensor on
+        the context's device (svdw_export_cells: queued, no host wait; torch's
+        current stream is ordered behind it)."""
+        f = _form(form)
+        total = self.lookup_len(phase) if lookup else self.advice_len(phase)
+        n = total - off if n is None else n
+        if n < 0 or off < 0:
+            raise SvdwError(-1, "cells: range outside the stream")
+        if device:
+            torch = _torch_mod()
+            out = torch.empty((n, 32), dtype=torch.uint8, device=torch.device("cuda", self.device))
+            _after_torch(self)
+            check(lib().svdw_export_cells(self._h, phase, int(bool(lookup)), off, n, f, out.data_ptr() or 1))
+            _before_torch(self)
+            return out
+        out = np.zeros((n, 4), dtype=np.uint64)
+        check(lib().svdw_copy_cells(self._h, phase, int(bool(lookup)), off, n, f, out.ctypes.data or 1))
+        return out
+
     def set_gemm_impl(self, impl: str) -> None:
         """'mfma' (matrix cores, default) or 'valu' (v_dot4): bit-identical GEMM paths."""
         check(lib().svdw_set_gemm_impl(self._h, {"mfma": 0, "valu": 1}[impl]))
@@ -318,9 +410,10 @@ class Context:
         check(lib().svdw_break_points(self._h, phase, buf, n.value, ct.byref(n)))
         return list(buf[:n.value])
 
-    def assign_columns(self, phase: int, device=None):
+    def assign_columns(self, phase: int, device=None, form: str = "canonical"):
         """(advice [cols, 2^k, 32] u8, selectors [cols, 2^k] u8, lookup [nl, 2^k, 32] u8)
-        torch tensors on the device, filled by svdw_assign_columns."""
+        torch tensors on the device, filled by svdw_assign_columns_form: the
+        advice and lookup cells in `form` ("canonical" | "montgomery")."""
         import torch
         p = self._phys
         if p is None:
@@ -332,8 +425,8 @@ class Context:
         sel = torch.empty((nc, rows), dtype=torch.uint8, device=dev)
         lk = torch.empty((nl, rows, 32), dtype=torch.uint8, device=dev)
         _after_torch(self)
-        check(lib().svdw_assign_columns(self._h, phase, adv.data_ptr() if nc else None,
-                                        sel.data_ptr() if nc else None, lk.data_ptr() if nl else None))
+        check(lib().svdw_assign_columns_form(self._h, phase, _form(form), adv.data_ptr() if nc else None,
+                                             sel.data_ptr() if nc else None, lk.data_ptr() if nl else None))
         _before_torch(self)
         return adv, sel, lk
 
@@ -402,6 +495,20 @@ class Context:
         return ZkVector(self, v)
 
 
+def _dequantize(ctx: Context, fn, view, shape, device: bool):
+    """fn = svdw_dequantize_mat / _vec of `view` into a new array of `shape`."""
+    if device:
+        torch = _torch_mod()
+        out = torch.empty(shape, dtype=torch.float64, device=torch.device("cuda", ctx.device))
+        _after_torch(ctx)
+        check(fn(ctx.handle, ct.byref(view), out.data_ptr() or 1, 1))
+        _before_torch(ctx)
+        return out
+    out = np.zeros(shape, dtype=np.float64)
+    check(fn(ctx.handle, ct.byref(view), out.ctypes.data or 1, 0))
+    return out
+
+
 class ZkMatrix:
     """src/matrix/mod.rs:219-420: a view (offset + strides) into a phase stream."""
 
@@ -459,12 +566,26 @@ class ZkMatrix:
         check(lib().svdw_rescale_matrix(ctx.handle, ct.byref(c_s.mat), ct.byref(cfg), ct.byref(out)))
         return ZkMatrix(ctx, out)
 
-    def values(self) -> np.ndarray:
-        """Cell values (rows, cols, 4) uint64 (host copy, for inspection)."""
-        cells = self.ctx.advice(self.mat.phase)
-        idx = (self.mat.off + np.arange(self.mat.rows)[:, None] * self.mat.rs
-               + np.arange(self.mat.cols)[None, :] * self.mat.cs)
-        return cells[idx]
+    def values(self, form: str = "canonical") -> np.ndarray:
+        """Cell values (rows, cols, 4) uint64 in `form` (host copy of the view's
+        cells alone, gathered on the device: svdw_export_mat)."""
+        out = np.zeros((self.mat.rows, self.mat.cols, 4), dtype=np.uint64)
+        check(lib().svdw_export_mat(self.ctx.handle, ct.byref(self.mat), _form(form), out.ctypes.data or 1, 0))
+        return out
+
+    def dequantize(self, device: bool = False):
+        """ZkMatrix::dequantize (src/matrix/mod.rs:257-270): (rows, cols) float64,
+        a numpy array or with device=True a torch tensor on the context's
+        device (svdw_dequantize_mat; parity unpinned, include/svdw.h)."""
+        return _dequantize(self.ctx, lib().svdw_dequantize_mat, self.mat, (self.mat.rows, self.mat.cols), device)
+
+    def print(self, file=None) -> None:
+        """ZkMatrix::print (src/matrix/mod.rs:272-284): the dequantized matrix in
+        the reference's layout, elements as Rust's {:?}."""
+        text = "[\n"
+        for row in self.dequantize():
+            text += "[\n" + "".join(format_f64_debug(x) + ", " for x in row) + "], \n"
+        print(text + "]", file=file)
 
 
 class ZkVector:
@@ -492,10 +613,22 @@ class ZkVector:
                                           ct.byref(out)))
         return cls(ctx, out)
 
-    def values(self) -> np.ndarray:
-        """Cell values (len, 4) uint64 (host copy, for inspection)."""
-        cells = self.ctx.advice(self.vec.phase)
-        return cells[self.vec.off + np.arange(self.vec.len) * self.vec.stride]
+    def values(self, form: str = "canonical") -> np.ndarray:
+        """Cell values (len, 4) uint64 in `form` (host copy of the view's cells
+        alone, gathered on the device: svdw_export_vec)."""
+        out = np.zeros((self.vec.len, 4), dtype=np.uint64)
+        check(lib().svdw_export_vec(self.ctx.handle, ct.byref(self.vec), _form(form), out.ctypes.data or 1, 0))
+        return out
+
+    def dequantize(self, device: bool = False):
+        """ZkVector::dequantize (src/matrix/mod.rs:50-56): (len,) float64, a numpy
+        array or with device=True a torch tensor (svdw_dequantize_vec)."""
+        return _dequantize(self.ctx, lib().svdw_dequantize_vec, self.vec, (self.vec.len,), device)
+
+    def print(self, file=None) -> None:
+        """ZkVector::print (src/matrix/mod.rs:61-68)."""
+        text = "[\n" + "".join(format_f64_debug(x) + ", \n" for x in self.dequantize())
+        print(text + "]", file=file)
 
     def inner_product(self, x: "ZkVector", phase: int = 0, shift_bits: int = 0,
                       num_bits: int = 0) -> "ZkVector":

@@ -138,6 +138,52 @@ const void* svdw_lookup_device_ptr(const svdw_ctx* ctx, uint32_t phase);
 int svdw_copy_advice(svdw_ctx* ctx, uint32_t phase, uint64_t off, uint64_t n, uint64_t* out);
 int svdw_copy_lookup(svdw_ctx* ctx, uint32_t phase, uint64_t off, uint64_t n, uint64_t* out);
 
+/* ------------------------------------------------------------- read-out
+ * Cells in the form the consumer holds them, converted on the device while
+ * they are read (no host pass over the witness). These calls read the cells
+ * the handle currently shows (the latest call's set under "pipeline", the
+ * latest state under "lanes"), as svdw_copy_advice does, and work on a
+ * row-sharded context (they export whatever the range holds). SVDW_EINVAL: a
+ * null pointer, an unknown form, a range outside the stream, a view outside its
+ * phase's stream, a planning context ("planning context has no cells"). */
+#define SVDW_FORM_CANONICAL  0   /* Fr::to_repr, what the streams hold */
+#define SVDW_FORM_MONTGOMERY 1   /* halo2curves' in-memory Fr([u64;4]): x * 2^256 mod p, 4 LE u64 */
+/* Cells [off, off+n) of the advice (lookup = 0) or lookup (1) stream of `phase`,
+ * in `form`, into DEVICE memory dst (n * 32 B). Queued on the context behind
+ * everything queued so far, no host wait; order the consumer with
+ * svdw_stream_signal or a mark. */
+int svdw_export_cells(svdw_ctx* ctx, uint32_t phase, int lookup, uint64_t off, uint64_t n, int form,
+                      void* dst);
+/* The same into HOST memory; waits. Staged through at most 2 x 64 MiB of device
+ * scratch whatever n is (chunk k + 1 converts while chunk k copies out); a
+ * canonical range is copied straight from the stream. */
+int svdw_copy_cells(svdw_ctx* ctx, uint32_t phase, int lookup, uint64_t off, uint64_t n, int form,
+                    uint64_t* out);
+/* Gather a view, row-major dense (rows*cols resp. len cells of 32 B), into
+ * device memory (on_device: queued, no host wait) or host memory (waits).
+ * Negative strides are allowed; a transpose is a stride swap. */
+int svdw_export_mat(svdw_ctx* ctx, const svdw_mat* a, int form, void* dst, int on_device);
+int svdw_export_vec(svdw_ctx* ctx, const svdw_vec* v, int form, void* dst, int on_device);
+/* ZkMatrix::dequantize / ZkVector::dequantize (src/matrix/mod.rs:50-58,257-270):
+ * rows*cols resp. len f64, row-major, FixedPointChip041::dequantization of every
+ * cell for the context's PRECISION_BITS. The chip's source (zk_fixed_point_chip,
+ * git HEAD) is not available offline, so the construction is PARITY UNPINNED:
+ *   x is negative iff x > (p-1)/2; mag = x, or p - x when negative;
+ *   m = mag mod 2^128 (get_lower_128); S = 2^P;
+ *   result = +-((m / S as f64) + (m % S as f64) / (S as f64)),
+ * every `as f64` being Rust's u128 -> f64 (round to nearest even), the sum one
+ * f64 addition; zero gives +0.0. Host and device agree bit for bit. */
+int svdw_dequantize_mat(svdw_ctx* ctx, const svdw_mat* a, double* out, int on_device);
+int svdw_dequantize_vec(svdw_ctx* ctx, const svdw_vec* v, double* out, int on_device);
+/* Host helpers, no context, no GPU: n values between forms (in may equal out;
+ * an input >= p in either form is SVDW_EINVAL and nothing is written), and the
+ * chip's scalar quantization (ZkMatrix::new's: round half away of |x| 2^P as
+ * u128, saturating, NaN -> 0, negative -> p - x_q) / dequantization (above) for
+ * P = precision_bits in [1, 63] (else SVDW_ERANGE). */
+int svdw_fr_convert(const uint64_t* in, uint64_t n, int from, int to, uint64_t* out);
+int svdw_quantization(double x, uint32_t precision_bits, uint64_t out[4]);
+int svdw_dequantization(const uint64_t value[4], uint32_t precision_bits, double* out);
+
 /* ------------------------------------------- ZkMatrix / ZkVector (matrix/mod.rs) */
 /* ZkMatrix::new (src/matrix/mod.rs:230-252): quantize + load_witness, row-major.
  * data: rows*cols f64 (host memory, or device memory if on_device). */
@@ -477,6 +523,12 @@ int svdw_break_points(const svdw_ctx* ctx, uint32_t phase, uint64_t* out, uint64
  * = columns_used x 2^k q_enable bytes, lookup = num_lookup_advice x 2^k cells;
  * any may be NULL. Fails with SVDW_ERANGE when columns_used > num_advice. */
 int svdw_assign_columns(svdw_ctx* ctx, uint32_t phase, void* advice, uint8_t* selectors, void* lookup);
+/* svdw_assign_columns with the advice and lookup columns in `form` (SVDW_FORM_*;
+ * selectors unchanged; padding rows stay zero, which is zero in both forms):
+ * Montgomery columns are converted while they are written, one pass over the
+ * cells. form 0 == svdw_assign_columns. */
+int svdw_assign_columns_form(svdw_ctx* ctx, uint32_t phase, int form, void* advice, uint8_t* selectors,
+                             void* lookup);
 /* The basic gate at every enabled (column, row) of assigned columns, and each
  * break cell against row 0 of the next column (copies_*). */
 int svdw_check_physical(svdw_ctx* ctx, uint32_t phase, const void* advice, const uint8_t* selectors,
