@@ -75,6 +75,17 @@ class CheckResult(ct.Structure):
                 ("copies_checked", ct.c_uint64), ("copy_failures", ct.c_uint64)]
 
 
+class LookupResult(ct.Structure):
+    _fields_ = [("columns", ct.c_uint32), ("_pad", ct.c_uint32), ("usable_rows", ct.c_uint64),
+                ("out_of_table", ct.c_uint64), ("distinct", ct.c_uint64)]
+
+
+class LookupCheck(ct.Structure):
+    _fields_ = [("adjacency_checked", ct.c_uint64), ("adjacency_failures", ct.c_uint64),
+                ("multiset_checked", ct.c_uint64), ("multiset_failures", ct.c_uint64),
+                ("padding_checked", ct.c_uint64), ("padding_failures", ct.c_uint64)]
+
+
 class PhysParams(ct.Structure):
     _fields_ = [("k", ct.c_uint32), ("minimum_rows", ct.c_uint32), ("max_rows", ct.c_uint64),
                 ("num_advice", ct.c_uint32 * 2), ("columns_used", ct.c_uint32 * 2),
@@ -199,6 +210,10 @@ SIGNATURES = {
     "svdw_quantization": (_i32, [_dbl, _u32, _P]),
     "svdw_dequantization": (_i32, [_P, _u32, ct.POINTER(_dbl)]),
     "svdw_plan_svd": (_i32, [_u32, _u32, _u32, _u32, ct.POINTER(SvdConfig), ct.POINTER(Counts)]),
+    "svdw_lookup_multiplicities": (_i32, [_P, _u32, _u32, _P, _u32, _P]),
+    "svdw_lookup_permute": (_i32, [_P, _u32, _u32, _i32, _P, _u32, _P, _P, ct.POINTER(LookupResult)]),
+    "svdw_check_lookup_argument": (_i32, [_P, _u32, _u32, _i32, _P, _u32, _P, _P,
+                                          ct.POINTER(LookupCheck)]),
 }
 
 _lib = None

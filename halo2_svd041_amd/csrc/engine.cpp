@@ -30,6 +30,7 @@
 #include "ingest_dev.hpp"
 #include "kernels.hpp"
 #include "export.hpp"
+#include "lookup.hpp"
 
 using namespace svdw;
 
@@ -670,6 +671,7 @@ struct svdw_ctx {
     // order them ([0..1] half converted, [2..3] half copied out, [4..5] the join
     // of st2 / st3 into st ahead of every read-out)
     DBuf exp_buf[2];
+    DBuf lkp;                               // lookup argument: histograms, scans, counters (lookup.hpp)
     hipEvent_t exp_ev[6] = {};
     // ---- captured verify_mul_witness ("graph", vm_graph): the launch sequence of
     // a device-input call is captured once into a HIP graph (the second call of
@@ -3273,7 +3275,7 @@ static std::vector<DBuf*> dbufs(svdw_ctx* c) {
                             &c->gtab_alt, &c->crtR, &c->gbits, &c->colpart, &c->qfold, &c->ing_x, &c->ing_e,
                             &c->ing_c, &c->ing_p10, &c->ing_val, &c->ing_npos, &c->ing_nd, &c->ing_rpos,
                             &c->ing_kpos, &c->ing_err, &c->ing_q, &c->eq_cp, &c->eq_ks, &c->eq_reg, &c->eq_w,
-                            &c->eq_k, &c->eq_err, &c->eq_st, &c->exp_buf[0], &c->exp_buf[1]};
+                            &c->eq_k, &c->eq_err, &c->eq_st, &c->exp_buf[0], &c->exp_buf[1], &c->lkp};
     for (int i = 0; i < kMaxScanJobs; ++i) {
         v.push_back(&c->wbc[i]);
         v.push_back(&c->wbt[i]);
@@ -4908,6 +4910,148 @@ int svdw_check_equalities(svdw_ctx* c, uint32_t phase, const void* columns0, con
         out->copy_failures = h[1];
         out->consts_checked = h[2];
         out->const_failures = h[3];
+    });
+}
+// ---- lookup argument: multiplicities, permuted columns, their check (lookup.hpp)
+namespace {
+struct LkArgs {
+    uint32_t lb = 0;
+    uint64_t rows = 0, usable = 0;
+    LkSrc src{};
+};
+}  // namespace
+// The argument checks the three entries share. False: no columns, nothing to do.
+static bool lk_args(svdw_ctx* c, const char* fn, uint32_t phase, uint32_t unusable_rows, const void* columns,
+                    uint32_t ncols, LkArgs* a) {
+    const std::string f(fn);
+    REQUIRE(c && phase < 2, "bad argument");
+    REQUIRE(!c->dry, f + " needs a device context");
+    REQUIRE(!sharded(c), f + ": the lookup stream of a row-sharded context is partial");
+    REQUIRE(c->phys.valid, f + ": call svdw_physical_layout after the witness");
+    const auto& P = c->phys;
+    if (P.k > 31) fail(SVDW_ERANGE, f + ": k > 31");
+    REQUIRE(unusable_rows <= P.min_rows, f + ": unusable_rows exceeds the layout's minimum_rows "
+                                             "(an assigned row would be a blinding row)");
+    const uint64_t TL = c->ph[phase].nl, nl = (TL + P.R - 1) / P.R;
+    REQUIRE(columns || ncols == nl, f + ": ncols differs from num_lookup_advice of the phase");
+    a->lb = c->LB;
+    a->rows = 1ull << P.k;
+    a->usable = a->rows - unusable_rows;
+    if (c->LB > 31 || (1ull << c->LB) > a->usable)
+        fail(SVDW_ERANGE, f + ": the 2^lookup_bits table does not fit the usable rows (not enough rows: raise k)");
+    if (ncols > 65535) fail(SVDW_ERANGE, f + ": more than 65535 columns");
+    a->src = columns ? LkSrc{(const Fr*)columns, a->rows, a->rows, (uint64_t)ncols * a->rows}
+                     : LkSrc{c->ph[phase].lk, P.R, P.R, TL};
+    return ncols != 0;
+}
+int svdw_lookup_multiplicities(svdw_ctx* c, uint32_t phase, uint32_t unusable_rows, const void* columns,
+                               uint32_t ncols, uint32_t* mult) {
+    return guarded([&] {
+        LkArgs a;
+        if (!lk_args(c, "svdw_lookup_multiplicities", phase, unusable_rows, columns, ncols, &a)) return;
+        REQUIRE(mult, "null output");
+        sync(c);
+        ensure_buf(c, c->lkp, 128);
+        unsigned long long* oot = (unsigned long long*)c->lkp.p;
+        hipck(hipMemsetAsync(oot, 0, 128, c->st), "hipMemsetAsync");
+        hipck(hipMemsetAsync(mult, 0, ((size_t)ncols << a.lb) * sizeof(uint32_t), c->st), "hipMemsetAsync");
+        {
+            ProfScope ps(c, c->st, "k_lk_hist", 32.0 * ncols * a.usable, 0);
+            hipck(launch_lk_hist(a.src, SVDW_FORM_CANONICAL, ncols, a.usable, a.lb, mult, oot, c->st), "k_lk_hist");
+        }
+        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+    });
+}
+int svdw_lookup_permute(svdw_ctx* c, uint32_t phase, uint32_t unusable_rows, int form, const void* columns,
+                        uint32_t ncols, void* permuted_input, void* permuted_table, svdw_lookup_result* result) {
+    return guarded([&] {
+        REQUIRE(result, "null argument");
+        check_form(form);
+        LkArgs a;
+        const bool any = lk_args(c, "svdw_lookup_permute", phase, unusable_rows, columns, ncols, &a);
+        memset(result, 0, sizeof *result);
+        result->usable_rows = a.usable;
+        if (!any) return;
+        REQUIRE(permuted_input && permuted_table, "null output");
+        sync(c);
+        const uint64_t B = 1ull << a.lb, nblk = lk_scan_blocks(B), bins = (uint64_t)ncols * B;
+        ensure_buf(c, c->lkp, 128 + (4 * bins + 2 * ncols * nblk + ncols) * sizeof(uint32_t));
+        unsigned long long* oot = (unsigned long long*)c->lkp.p;
+        LkScratch s;
+        s.cnt = (uint32_t*)((char*)c->lkp.p + 128);
+        s.start = s.cnt + bins;
+        s.pincl = s.start + bins;
+        s.absent = s.pincl + bins;
+        s.bsum = s.absent + bins;
+        s.tot = s.bsum + 2 * ncols * nblk;
+        hipck(hipMemsetAsync(c->lkp.p, 0, 128 + bins * sizeof(uint32_t), c->st), "hipMemsetAsync");
+        {
+            ProfScope ps(c, c->st, "k_lk_hist", 32.0 * ncols * a.usable, 0);
+            hipck(launch_lk_hist(a.src, SVDW_FORM_CANONICAL, ncols, a.usable, a.lb, s.cnt, oot, c->st), "k_lk_hist");
+        }
+        unsigned long long bad = 0;
+        hipck(hipMemcpyAsync(&bad, oot, sizeof bad, hipMemcpyDeviceToHost, c->st), "D2H");
+        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+        result->columns = ncols;
+        result->out_of_table = bad;
+        if (bad) return;                                    // ConstraintSystemFailure: the outputs stay as they are
+        {
+            ProfScope ps(c, c->st, "k_lk_scan", 20.0 * bins, 0);
+            hipck(launch_lk_scans(s, ncols, a.lb, c->st), "k_lk_scan");
+        }
+        {
+            ProfScope ps(c, c->st, "k_lk_fill", 64.0 * ncols * a.rows, 0);
+            hipck(launch_lk_fill(s, ncols, a.rows, a.usable, a.lb, form, (Fr*)permuted_input, (Fr*)permuted_table,
+                                 c->st), "k_lk_fill");
+        }
+        std::vector<uint32_t> tot(ncols);
+        hipck(hipMemcpyAsync(tot.data(), s.tot, ncols * sizeof(uint32_t), hipMemcpyDeviceToHost, c->st), "D2H");
+        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+        for (uint32_t d : tot) result->distinct += d;
+    });
+}
+int svdw_check_lookup_argument(svdw_ctx* c, uint32_t phase, uint32_t unusable_rows, int form, const void* columns,
+                               uint32_t ncols, const void* permuted_input, const void* permuted_table,
+                               svdw_lookup_check* result) {
+    return guarded([&] {
+        REQUIRE(result, "null argument");
+        check_form(form);
+        LkArgs a;
+        const bool any = lk_args(c, "svdw_check_lookup_argument", phase, unusable_rows, columns, ncols, &a);
+        memset(result, 0, sizeof *result);
+        if (!any) return;
+        REQUIRE(permuted_input && permuted_table, "null argument");
+        sync(c);
+        const uint64_t bins = (uint64_t)ncols << a.lb;
+        ensure_buf(c, c->lkp, 128 + 3 * bins * sizeof(uint32_t));
+        unsigned long long* cnt = (unsigned long long*)c->lkp.p;   // [0..3] rows, [4..5] bins, [8] cells outside the table
+        uint32_t* ha = (uint32_t*)((char*)c->lkp.p + 128);
+        uint32_t *hpin = ha + bins, *htab = hpin + bins;
+        hipck(hipMemsetAsync(c->lkp.p, 0, 128 + 3 * bins * sizeof(uint32_t), c->st), "hipMemsetAsync");
+        const uint64_t cells = (uint64_t)ncols * a.rows;
+        {
+            ProfScope ps(c, c->st, "k_lk_hist:check", 32.0 * ncols * 3 * a.usable, 0);
+            hipck(launch_lk_hist(a.src, SVDW_FORM_CANONICAL, ncols, a.usable, a.lb, ha, cnt + 8, c->st), "k_lk_hist");
+            hipck(launch_lk_hist(LkSrc{(const Fr*)permuted_input, a.rows, a.rows, cells}, form, ncols, a.usable,
+                                 a.lb, hpin, cnt + 8, c->st), "k_lk_hist");
+            hipck(launch_lk_hist(LkSrc{(const Fr*)permuted_table, a.rows, a.rows, cells}, form, ncols, a.usable,
+                                 a.lb, htab, cnt + 8, c->st), "k_lk_hist");
+            hipck(launch_lk_compare(ha, hpin, htab, ncols, a.usable, a.lb, cnt + 4, c->st), "k_lk_compare");
+        }
+        {
+            ProfScope ps(c, c->st, "k_lk_adjacent", 64.0 * ncols * a.rows, 0);
+            hipck(launch_lk_adjacent((const Fr*)permuted_input, (const Fr*)permuted_table, ncols, a.rows, a.usable,
+                                     cnt, c->st), "k_lk_adjacent");
+        }
+        unsigned long long h[9];
+        hipck(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, c->st), "D2H");
+        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+        result->adjacency_checked = h[0];
+        result->adjacency_failures = h[1];
+        result->padding_checked = h[2];
+        result->padding_failures = h[3];
+        result->multiset_checked = h[4];
+        result->multiset_failures = h[5] + h[8];           // a cell outside the table is in no bin
     });
 }
 int svdw_rlc_trace(const svdw_ctx* c, uint64_t* cells, uint64_t* copies, uint32_t* n) {

@@ -20,7 +20,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import (CheckResult, EqCheck, PhysParams, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SvdwError,
+from ._lib import (CheckResult, EqCheck, LookupCheck, LookupResult, PhysParams, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SvdwError,
                    Vec, check, lib)
 
 P_MOD = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -467,6 +467,77 @@ class Context:
         check(lib().svdw_check_equalities(self._h, phase, p0, p1, ct.byref(r)))
         return {"copies_checked": r.copies_checked, "copy_failures": r.copy_failures,
                 "consts_checked": r.consts_checked, "const_failures": r.const_failures}
+
+    # ---- lookup argument (include/svdw.h, "lookup argument"; parity unpinned)
+    def _lookup_cols(self, phase: int, columns):
+        """(pointer, ncols, 2^k, device) of a lookup-argument call's input columns."""
+        import torch
+        p = self._phys
+        if p is None:
+            raise RuntimeError("call physical_layout() after the witness first")
+        rows = 1 << p["k"]
+        if columns is None:
+            return None, p["num_lookup_advice"][phase], rows, torch.device("cuda", self.device)
+        if (not columns.is_cuda or columns.dtype != torch.uint8 or not columns.is_contiguous()
+                or columns.dim() != 3 or tuple(columns.shape[1:]) != (rows, 32)):
+            raise SvdwError(-1, "columns must be a contiguous uint8 device tensor [n, 2^k, 32]")
+        return (columns.data_ptr() if columns.shape[0] else None), columns.shape[0], rows, columns.device
+
+    def lookup_multiplicities(self, phase: int, unusable_rows: int = 6, columns=None):
+        """[nl, 2^lookup_bits] int32 device tensor: how often each table value occurs
+        in the usable rows of each lookup column (svdw_lookup_multiplicities).
+        columns: None (the lookup stream of `phase` through the physical layout)
+        or canonical columns [n, 2^k, 32] u8, e.g. assign_columns(...)[2]."""
+        import torch
+        ptr, nl, _, dev = self._lookup_cols(phase, columns)
+        mult = torch.empty((nl, 1 << self.lookup_bits), dtype=torch.int32, device=dev)
+        _after_torch(self)
+        check(lib().svdw_lookup_multiplicities(self._h, phase, unusable_rows, ptr, nl,
+                                               mult.data_ptr() if nl else None))
+        _before_torch(self)
+        return mult
+
+    def lookup_permute(self, phase: int, unusable_rows: int = 6, form: str = "canonical", columns=None,
+                       out=None):
+        """(A', S', result): the permuted input and table columns of the lookup
+        argument, [nl, 2^k, 32] u8 device tensors in `form`, rows >= 2^k -
+        unusable_rows zero (svdw_lookup_permute). result: columns, usable_rows,
+        out_of_table, distinct; with out_of_table > 0 the tensors are left as
+        allocated (or as `out` = (A', S') held them)."""
+        import torch
+        ptr, nl, rows, dev = self._lookup_cols(phase, columns)
+        if out is None:
+            out = (torch.empty((nl, rows, 32), dtype=torch.uint8, device=dev),
+                   torch.empty((nl, rows, 32), dtype=torch.uint8, device=dev))
+        a, s = out
+        for t in (a, s):
+            if (not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous()
+                    or tuple(t.shape) != (nl, rows, 32)):
+                raise SvdwError(-1, "out must be two contiguous uint8 device tensors [n, 2^k, 32]")
+        r = LookupResult()
+        _after_torch(self)
+        check(lib().svdw_lookup_permute(self._h, phase, unusable_rows, _form(form), ptr, nl,
+                                        a.data_ptr() if nl else None, s.data_ptr() if nl else None,
+                                        ct.byref(r)))
+        _before_torch(self)
+        return a, s, {"columns": r.columns, "usable_rows": r.usable_rows,
+                      "out_of_table": r.out_of_table, "distinct": r.distinct}
+
+    def check_lookup_argument(self, phase: int, permuted_input, permuted_table, unusable_rows: int = 6,
+                              form: str = "canonical", columns=None) -> dict:
+        """Device check of the lookup argument's constraints on (A', S') in `form`
+        (svdw_check_lookup_argument): checked / failure counts of the adjacency,
+        multiset and padding conditions."""
+        ptr, nl, rows, _ = self._lookup_cols(phase, columns)
+        for t in (permuted_input, permuted_table):
+            if not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (nl, rows, 32):
+                raise SvdwError(-1, "permuted columns must be contiguous uint8 device tensors [n, 2^k, 32]")
+        r = LookupCheck()
+        _after_torch(self)
+        check(lib().svdw_check_lookup_argument(self._h, phase, unusable_rows, _form(form), ptr, nl,
+                                               permuted_input.data_ptr() if nl else None,
+                                               permuted_table.data_ptr() if nl else None, ct.byref(r)))
+        return {k: getattr(r, k) for k, _ in LookupCheck._fields_}
 
     def profile(self, on: bool = True, prefix: str = "") -> None:
         """Record HIP events around kernel launches (names starting with `prefix`)."""

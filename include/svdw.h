@@ -557,6 +557,70 @@ typedef struct {
  * cell at its first placement. External sources compare with the last init_rand. */
 int svdw_check_equalities(svdw_ctx* ctx, uint32_t phase, const void* columns0, const void* columns1,
                           svdw_eq_check* out);
+/* ------------------------------------------------------ lookup argument
+ * What a halo2 prover computes next from a lookup advice column: the permuted
+ * input column A' and permuted table column S' of
+ * halo2_proofs' plonk::lookup::prover::permute_expression_pair, for RangeChip's
+ * table T = [0, 1, .., 2^lookup_bits - 1, 0, 0, ..] (padded with its first
+ * value), and the table-value multiplicities a logUp-style prover takes
+ * instead. halo2_proofs' source is not available offline, so the rule is
+ * restated from memory: PARITY UNPINNED. With usable = 2^k - unusable_rows
+ * (unusable_rows = halo2's blinding_factors + 1) and only rows [0, usable)
+ * taking part:
+ *   A' = A[:usable] sorted by the canonical integer;
+ *   walking A' in row order, the first row of each run of equal values gets
+ *   S' = A' (one copy of the value leaves the table multiset; a value not in
+ *   it fails the lookup), every other row is pushed on a list of repeated rows;
+ *   the table entries left over, ascending, each go to the row popped off the
+ *   END of that list (ascending leftovers fill the repeated rows in
+ *   descending row order);
+ *   rows >= usable are the prover's blinding rows: the engine writes zero.
+ * Every honest cell is < 2^lookup_bits, so the device does this with a
+ * histogram, scans over the 2^lookup_bits bins and a fill.
+ *
+ * Input columns: columns == NULL reads the lookup stream of `phase` through
+ * the physical layout (column c = stream cells [c max_rows, min((c + 1)
+ * max_rows, len)) then zeros; nothing is materialised; ncols must equal
+ * num_lookup_advice[phase]); else a canonical ncols x 2^k DEVICE array,
+ * column-major, e.g. svdw_assign_columns' lookup output. The calls need a prior
+ * svdw_physical_layout (k, max_rows) and return after the device has finished.
+ * SVDW_EINVAL: a planning or row-sharded context, no layout, unusable_rows >
+ * the layout's minimum_rows (an assigned row would be a blinding row), ncols
+ * mismatch. SVDW_ERANGE: k > 31, 2^lookup_bits > usable (the table does not
+ * fit: halo2's not-enough-rows), more than 65535 columns. ncols == 0: SVDW_OK,
+ * nothing is touched (phase 1 of an SVD witness has no lookup cells). */
+/* mult[c * 2^lookup_bits + v] = the cells equal to v in rows [0, usable) of
+ * column c (unassigned rows count as zeros); a cell >= 2^lookup_bits is counted
+ * nowhere. mult: DEVICE array of ncols x 2^lookup_bits uint32_t. */
+int svdw_lookup_multiplicities(svdw_ctx* ctx, uint32_t phase, uint32_t unusable_rows, const void* columns,
+                               uint32_t ncols, uint32_t* mult);
+typedef struct {
+    uint32_t columns, _pad;
+    uint64_t usable_rows;
+    uint64_t out_of_table;   /* cells >= 2^lookup_bits in usable rows */
+    uint64_t distinct;       /* distinct values per column, summed over the columns */
+} svdw_lookup_result;
+/* permuted_input / permuted_table: DEVICE arrays of ncols x 2^k cells,
+ * column-major as svdw_assign_columns, in `form` (SVDW_FORM_*). If any cell of a
+ * usable row is >= 2^lookup_bits (any bit above lookup_bits set, the test of
+ * svdw_check_gates' lookup check) the call returns SVDW_OK with out_of_table =
+ * their count and leaves the outputs untouched: halo2's ConstraintSystemFailure. */
+int svdw_lookup_permute(svdw_ctx* ctx, uint32_t phase, uint32_t unusable_rows, int form, const void* columns,
+                        uint32_t ncols, void* permuted_input, void* permuted_table, svdw_lookup_result* result);
+typedef struct {
+    uint64_t adjacency_checked, adjacency_failures;   /* usable rows */
+    uint64_t multiset_checked, multiset_failures;     /* 2 x 2^lookup_bits bins per column */
+    uint64_t padding_checked, padding_failures;       /* cells of A' and S' in rows >= usable */
+} svdw_lookup_check;
+/* The lookup argument's own constraints on permuted columns in `form`, on the
+ * device: adjacency (A'[0] == S'[0]; A'[r] == S'[r] or A'[r] == A'[r - 1] for
+ * 1 <= r < usable), multisets (the histogram of A' equals that of A[:usable],
+ * that of S' equals that of T[:usable]; a cell of A, A' or S' outside the table
+ * is a failure of its own), padding (rows >= usable are zero). `phase` selects
+ * the stream when columns == NULL. */
+int svdw_check_lookup_argument(svdw_ctx* ctx, uint32_t phase, uint32_t unusable_rows, int form,
+                               const void* columns, uint32_t ncols, const void* permuted_input,
+                               const void* permuted_table, svdw_lookup_check* result);
 /* Up to cap segments of the last witness into out; *n = total count. */
 int svdw_shard_segments(const svdw_ctx* ctx, svdw_segment* out, uint64_t cap, uint64_t* n);
 
