@@ -31,6 +31,7 @@
 #include "kernels.hpp"
 #include "export.hpp"
 #include "lookup.hpp"
+#include "lookup_product.hpp"
 
 using namespace svdw;
 
@@ -5052,6 +5053,102 @@ int svdw_check_lookup_argument(svdw_ctx* c, uint32_t phase, uint32_t unusable_ro
         result->padding_failures = h[3];
         result->multiset_checked = h[4];
         result->multiset_failures = h[5] + h[8];           // a cell outside the table is in no bin
+    });
+}
+// ---- lookup argument: the grand product Z and its check (lookup_product.hpp)
+// The argument checks of both entries; false: no columns, nothing to do.
+static bool lp_args(svdw_ctx* c, const char* fn, uint32_t phase, uint32_t unusable_rows, int form, const void* columns,
+                    uint32_t ncols, const uint64_t beta[4], const uint64_t gamma[4], LkArgs* a, LpChal* ch) {
+    const std::string f(fn);
+    REQUIRE(beta && gamma, "null argument");
+    check_form(form);
+    const Fr b = fr_raw_words(beta), g = fr_raw_words(gamma);
+    REQUIRE(fr_reduced(b) && fr_reduced(g), f + ": beta or gamma >= p");
+    if (!unusable_rows) fail(SVDW_ERANGE, f + ": unusable_rows == 0 leaves no row for Z[usable]");
+    if (!lk_args(c, fn, phase, unusable_rows, columns, ncols, a)) return false;
+    const bool mont = form == SVDW_FORM_MONTGOMERY;
+    ch->b0 = b;
+    ch->g0 = g;
+    ch->bx = mont ? fr_to_mont(b) : b;
+    ch->gx = mont ? fr_to_mont(g) : g;
+    ch->g2 = fr_to_mont(fr_to_mont(g));
+    ch->t2 = fr_to_mont(fr_to_mont(fr_from_u64(1ull << 32)));
+    ch->one = fr_to_mont(fr_from_u64(1));
+    return true;
+}
+int svdw_lookup_product(svdw_ctx* c, uint32_t phase, uint32_t unusable_rows, int form, const void* columns,
+                        uint32_t ncols, const void* permuted_input, const void* permuted_table,
+                        const uint64_t beta[4], const uint64_t gamma[4], void* z, svdw_lookup_product_result* result) {
+    return guarded([&] {
+        REQUIRE(result, "null argument");
+        LkArgs a;
+        LpChal ch;
+        const bool any = lp_args(c, "svdw_lookup_product", phase, unusable_rows, form, columns, ncols, beta, gamma,
+                                 &a, &ch);
+        memset(result, 0, sizeof *result);
+        result->usable_rows = a.usable;
+        if (!any) return;
+        REQUIRE(permuted_input && permuted_table && z, "null argument");
+        sync(c);
+        const uint64_t nt = lp_tiles(a.rows);
+        ensure_buf(c, c->lkp, 128 + 2 * ncols * nt * sizeof(Fr));
+        unsigned long long* cnt = (unsigned long long*)c->lkp.p;   // [0] zero denominators, [1] columns with Z[usable] != 1
+        Fr* tp = (Fr*)((char*)c->lkp.p + 128);
+        const Fr *pin = (const Fr*)permuted_input, *ptab = (const Fr*)permuted_table;
+        hipck(hipMemsetAsync(cnt, 0, 128, c->st), "hipMemsetAsync");
+        {
+            ProfScope ps(c, c->st, "k_lp_tiles", 96.0 * ncols * a.usable, 0);
+            hipck(launch_lp_tiles(a.src, pin, ptab, ch, form, ncols, a.rows, a.usable, a.lb, tp, cnt, c->st),
+                  "k_lp_tiles");
+        }
+        {
+            ProfScope ps(c, c->st, "k_lp_carry", 128.0 * ncols * nt, 0);
+            hipck(launch_lp_carry(tp, ch, form, ncols, a.rows, cnt, c->st), "k_lp_carry");
+        }
+        {
+            ProfScope ps(c, c->st, "k_lp_write", 96.0 * ncols * a.usable + 32.0 * ncols * a.rows, 0);
+            hipck(launch_lp_write(a.src, pin, ptab, ch, form, ncols, a.rows, a.usable, a.lb, tp, (Fr*)z, c->st),
+                  "k_lp_write");
+        }
+        unsigned long long h[2];
+        hipck(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, c->st), "D2H");
+        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+        result->columns = ncols;
+        result->zero_denominators = h[0];
+        result->final_not_one = h[1];
+    });
+}
+int svdw_check_lookup_product(svdw_ctx* c, uint32_t phase, uint32_t unusable_rows, int form, const void* columns,
+                              uint32_t ncols, const void* permuted_input, const void* permuted_table,
+                              const uint64_t beta[4], const uint64_t gamma[4], const void* z,
+                              svdw_lookup_product_check* result) {
+    return guarded([&] {
+        REQUIRE(result, "null argument");
+        LkArgs a;
+        LpChal ch;
+        const bool any = lp_args(c, "svdw_check_lookup_product", phase, unusable_rows, form, columns, ncols, beta,
+                                 gamma, &a, &ch);
+        memset(result, 0, sizeof *result);
+        if (!any) return;
+        REQUIRE(permuted_input && permuted_table && z, "null argument");
+        sync(c);
+        ensure_buf(c, c->lkp, 128);
+        unsigned long long* cnt = (unsigned long long*)c->lkp.p;
+        hipck(hipMemsetAsync(cnt, 0, 128, c->st), "hipMemsetAsync");
+        {
+            ProfScope ps(c, c->st, "k_lp_check", 96.0 * ncols * a.usable + 32.0 * ncols * a.rows, 0);
+            hipck(launch_lp_check(a.src, (const Fr*)permuted_input, (const Fr*)permuted_table, (const Fr*)z, ch, form,
+                                  ncols, a.rows, a.usable, a.lb, cnt, c->st), "k_lp_check");
+        }
+        unsigned long long h[6];
+        hipck(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, c->st), "D2H");
+        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+        result->recurrence_checked = h[0];
+        result->recurrence_failures = h[1];
+        result->boundary_checked = h[2];
+        result->boundary_failures = h[3];
+        result->padding_checked = h[4];
+        result->padding_failures = h[5];
     });
 }
 int svdw_rlc_trace(const svdw_ctx* c, uint64_t* cells, uint64_t* copies, uint32_t* n) {

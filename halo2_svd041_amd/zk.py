@@ -20,7 +20,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import (CheckResult, EqCheck, LookupCheck, LookupResult, PhysParams, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SvdwError,
+from ._lib import (CheckResult, EqCheck, LookupCheck, LookupProductCheck, LookupProductResult, LookupResult, PhysParams, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SvdwError,
                    Vec, check, lib)
 
 P_MOD = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -46,6 +46,15 @@ def _words_arg(x: int):
     """x mod p as the 4-word little-endian argument of the C calls (a ctypes
     array: no numpy round trip on the per-witness path)."""
     x = int(x) % P_MOD
+    return (ct.c_uint64 * 4)(x & _M64, (x >> 64) & _M64, (x >> 128) & _M64, x >> 192)
+
+
+def _challenge_arg(x: int):
+    """A challenge in [0, p) as the 4-word argument; unlike _words_arg it is not
+    reduced: a value outside the field is the caller's mistake."""
+    x = int(x)
+    if not 0 <= x < P_MOD:
+        raise SvdwError(-1, "challenge must be in [0, p)")
     return (ct.c_uint64 * 4)(x & _M64, (x >> 64) & _M64, (x >> 128) & _M64, x >> 192)
 
 
@@ -538,6 +547,55 @@ class Context:
                                                permuted_input.data_ptr() if nl else None,
                                                permuted_table.data_ptr() if nl else None, ct.byref(r)))
         return {k: getattr(r, k) for k, _ in LookupCheck._fields_}
+
+    def lookup_product(self, phase: int, permuted_input, permuted_table, beta: int, gamma: int,
+                       unusable_rows: int = 6, form: str = "canonical", columns=None, out=None):
+        """(Z, result): the lookup argument's grand-product column for the
+        challenges beta, gamma (ints below p) from (A', S') of lookup_permute in
+        the same `form`, a [nl, 2^k, 32] u8 device tensor in that form: Z[0] = 1,
+        Z[usable] = 1 for honest columns, rows above zero (svdw_lookup_product).
+        result: columns, usable_rows, zero_denominators, final_not_one."""
+        import torch
+        b, g = _challenge_arg(beta), _challenge_arg(gamma)
+        ptr, nl, rows, dev = self._lookup_cols(phase, columns)
+        for t in (permuted_input, permuted_table):
+            if (not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous()
+                    or tuple(t.shape) != (nl, rows, 32)):
+                raise SvdwError(-1, "permuted columns must be contiguous uint8 device tensors [n, 2^k, 32]")
+        if out is None:
+            out = torch.empty((nl, rows, 32), dtype=torch.uint8, device=dev)
+        if (not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous()
+                or tuple(out.shape) != (nl, rows, 32)):
+            raise SvdwError(-1, "out must be a contiguous uint8 device tensor [n, 2^k, 32]")
+        r = LookupProductResult()
+        _after_torch(self)
+        check(lib().svdw_lookup_product(self._h, phase, unusable_rows, _form(form), ptr, nl,
+                                        permuted_input.data_ptr() if nl else None,
+                                        permuted_table.data_ptr() if nl else None, b, g,
+                                        out.data_ptr() if nl else None, ct.byref(r)))
+        _before_torch(self)
+        return out, {"columns": r.columns, "usable_rows": r.usable_rows,
+                     "zero_denominators": r.zero_denominators, "final_not_one": r.final_not_one}
+
+    def check_lookup_product(self, phase: int, permuted_input, permuted_table, z, beta: int, gamma: int,
+                             unusable_rows: int = 6, form: str = "canonical", columns=None) -> dict:
+        """Device check of Z in `form` against (A', S'), the input columns and the
+        challenges, division-free (svdw_check_lookup_product): checked / failure
+        counts of the recurrence, the boundary rows and the padding."""
+        b, g = _challenge_arg(beta), _challenge_arg(gamma)
+        ptr, nl, rows, _ = self._lookup_cols(phase, columns)
+        import torch
+        for t in (permuted_input, permuted_table, z):
+            if (not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous()
+                    or tuple(t.shape) != (nl, rows, 32)):
+                raise SvdwError(-1, "permuted columns and z must be contiguous uint8 device tensors [n, 2^k, 32]")
+        r = LookupProductCheck()
+        _after_torch(self)
+        check(lib().svdw_check_lookup_product(self._h, phase, unusable_rows, _form(form), ptr, nl,
+                                              permuted_input.data_ptr() if nl else None,
+                                              permuted_table.data_ptr() if nl else None, b, g,
+                                              z.data_ptr() if nl else None, ct.byref(r)))
+        return {k: getattr(r, k) for k, _ in LookupProductCheck._fields_}
 
     def profile(self, on: bool = True, prefix: str = "") -> None:
         """Record HIP events around kernel launches (names starting with `prefix`)."""

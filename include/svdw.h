@@ -621,6 +621,55 @@ typedef struct {
 int svdw_check_lookup_argument(svdw_ctx* ctx, uint32_t phase, uint32_t unusable_rows, int form,
                                const void* columns, uint32_t ncols, const void* permuted_input,
                                const void* permuted_table, svdw_lookup_check* result);
+/* The lookup argument's grand-product column Z of halo2_proofs'
+ * plonk::lookup::prover::Permuted::commit_product, the one thing a prover
+ * computes from A' and S' after committing to them. Restated from memory like
+ * the permute: PARITY UNPINNED. One argument per lookup advice column, the
+ * compressed expressions are the columns themselves (no theta). With A the
+ * input column (zero where unassigned), T[r] = r for r < 2^lookup_bits, else 0,
+ * usable = 2^k - unusable_rows, inv0(x) = 1 / x and inv0(0) = 0 (ff's
+ * batch_invert leaves a zero zero):
+ *   f[r]     = (A[r] + beta)(T[r] + gamma) inv0((A'[r] + beta)(S'[r] + gamma))
+ *   Z[0]     = 1,  Z[r + 1] = Z[r] f[r]        0 <= r < usable
+ *   Z[r]     = 0                               usable < r < 2^k
+ * Rows above `usable` are the prover's random blinding rows: the engine writes
+ * zero. Z[usable] == 1 exactly when the two products agree, as they do for an
+ * honest (A', S'); Z is 0 from the row after the first zero denominator on.
+ * beta and gamma are inputs (canonical, 4 little-endian words, as gamma of
+ * svdw_svd_witness; >= p is SVDW_EINVAL): deriving them from the transcript,
+ * the commitments and the blinding rows' randomness stay with the prover.
+ * All arithmetic is exact mod p. columns / ncols / phase / unusable_rows as for
+ * svdw_lookup_permute, with the same errors, and SVDW_ERANGE for
+ * unusable_rows == 0 (Z[usable] would be row 2^k). The checks of the arguments
+ * alone come first, in this order: an unknown form (SVDW_EINVAL), beta or
+ * gamma >= p (SVDW_EINVAL), unusable_rows == 0 (SVDW_ERANGE); then those of the
+ * context as svdw_lookup_permute makes them. Cells are taken as field
+ * elements: the table range is svdw_lookup_permute's to validate.
+ * permuted_input, permuted_table, z: DEVICE arrays of ncols x 2^k cells,
+ * column-major, all in `form`. ncols == 0: SVDW_OK, nothing is touched. */
+typedef struct {
+    uint32_t columns, _pad;
+    uint64_t usable_rows;
+    uint64_t zero_denominators;   /* rows r < usable with (A'[r] + beta)(S'[r] + gamma) == 0, all columns */
+    uint64_t final_not_one;       /* columns with Z[usable] != 1 */
+} svdw_lookup_product_result;
+int svdw_lookup_product(svdw_ctx* ctx, uint32_t phase, uint32_t unusable_rows, int form, const void* columns,
+                        uint32_t ncols, const void* permuted_input, const void* permuted_table,
+                        const uint64_t beta[4], const uint64_t gamma[4], void* z,
+                        svdw_lookup_product_result* result);
+typedef struct {
+    uint64_t recurrence_checked, recurrence_failures;  /* rows r < usable, per column */
+    uint64_t boundary_checked, boundary_failures;      /* Z[0] == 1 and Z[usable] in {0, 1}: 2 per column */
+    uint64_t padding_checked, padding_failures;        /* Z rows > usable are zero */
+} svdw_lookup_product_check;
+/* The product's own constraints on a column Z in `form`, on the device, in the
+ * division-free form Z[r + 1] (A'[r] + beta)(S'[r] + gamma) ==
+ * Z[r] (A[r] + beta)(T[r] + gamma) for r < usable; it shares no inversion and no
+ * scan with svdw_lookup_product. */
+int svdw_check_lookup_product(svdw_ctx* ctx, uint32_t phase, uint32_t unusable_rows, int form, const void* columns,
+                              uint32_t ncols, const void* permuted_input, const void* permuted_table,
+                              const uint64_t beta[4], const uint64_t gamma[4], const void* z,
+                              svdw_lookup_product_check* result);
 /* Up to cap segments of the last witness into out; *n = total count. */
 int svdw_shard_segments(const svdw_ctx* ctx, svdw_segment* out, uint64_t cap, uint64_t* n);
 
