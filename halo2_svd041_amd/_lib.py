@@ -97,6 +97,17 @@ class LookupProductCheck(ct.Structure):
                 ("padding_checked", ct.c_uint64), ("padding_failures", ct.c_uint64)]
 
 
+class PermutationProductResult(ct.Structure):
+    _fields_ = [("columns", ct.c_uint32), ("sets", ct.c_uint32), ("usable_rows", ct.c_uint64),
+                ("zero_denominators", ct.c_uint64), ("final_not_one", ct.c_uint32), ("_pad", ct.c_uint32)]
+
+
+class PermutationProductCheck(ct.Structure):
+    _fields_ = [("recurrence_checked", ct.c_uint64), ("recurrence_failures", ct.c_uint64),
+                ("boundary_checked", ct.c_uint64), ("boundary_failures", ct.c_uint64),
+                ("padding_checked", ct.c_uint64), ("padding_failures", ct.c_uint64)]
+
+
 class PhysParams(ct.Structure):
     _fields_ = [("k", ct.c_uint32), ("minimum_rows", ct.c_uint32), ("max_rows", ct.c_uint64),
                 ("num_advice", ct.c_uint32 * 2), ("columns_used", ct.c_uint32 * 2),
@@ -229,6 +240,12 @@ SIGNATURES = {
                                    ct.POINTER(LookupProductResult)]),
     "svdw_check_lookup_product": (_i32, [_P, _u32, _u32, _i32, _P, _u32, _P, _P, _P, _P, _P,
                                          ct.POINTER(LookupProductCheck)]),
+    "svdw_permutation_constants": (_i32, [_u32, _P, _P]),
+    "svdw_permutation_values": (_i32, [_P, _u32, _i32, _P, _u32, _u32, _u32, _P, _u64p]),
+    "svdw_permutation_product": (_i32, [_P, _u32, _u32, _i32, _P, _P, _u32, _u32, _P, _P, _P,
+                                        ct.POINTER(PermutationProductResult)]),
+    "svdw_check_permutation_product": (_i32, [_P, _u32, _u32, _i32, _P, _P, _u32, _u32, _P, _P, _P,
+                                              ct.POINTER(PermutationProductCheck)]),
 }
 
 _lib = None

@@ -32,6 +32,7 @@
 #include "export.hpp"
 #include "lookup.hpp"
 #include "lookup_product.hpp"
+#include "permutation_product.hpp"
 
 using namespace svdw;
 
@@ -673,6 +674,9 @@ struct svdw_ctx {
     // of st2 / st3 into st ahead of every read-out)
     DBuf exp_buf[2];
     DBuf lkp;                               // lookup argument: histograms, scans, counters (lookup.hpp)
+    std::vector<Fr> pp_w;                   // permutation argument: the omega tables of pp_k (permutation_product.hpp)
+    uint32_t pp_k = 0;
+    std::vector<char> pp_up;                // its staged upload: pointer, delta and omega tables
     hipEvent_t exp_ev[6] = {};
     // ---- captured verify_mul_witness ("graph", vm_graph): the launch sequence of
     // a device-input call is captured once into a HIP graph (the second call of
@@ -5142,6 +5146,235 @@ int svdw_check_lookup_product(svdw_ctx* c, uint32_t phase, uint32_t unusable_row
         }
         unsigned long long h[6];
         hipck(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, c->st), "D2H");
+        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+        result->recurrence_checked = h[0];
+        result->recurrence_failures = h[1];
+        result->boundary_checked = h[2];
+        result->boundary_failures = h[3];
+        result->padding_checked = h[4];
+        result->padding_failures = h[5];
+    });
+}
+// ---- permutation argument: sigma values, the grand products Z and their check
+// (permutation_product.hpp)
+namespace {
+struct PpConsts {
+    Fr delta, omega28;                                     // canonical
+};
+struct PpDev {
+    PpArgs a{};
+    unsigned long long* cnt = nullptr;
+    Fr *sv = nullptr, *xs = nullptr, *tp = nullptr;
+};
+}  // namespace
+// delta = 7^(2^28) and omega_28 = 7^((p - 1) / 2^28), as halo2curves derives them.
+static const PpConsts& pp_consts() {
+    static const PpConsts k = [] {
+        Fr e = fr_p();
+        e.w[0] -= 1;
+        for (int i = 0; i < 8; ++i) e.w[i] = (e.w[i] >> 28) | (i < 7 ? e.w[i + 1] << 4 : 0u);
+        const Fr g = fr_to_mont(fr_from_u64(7));
+        Fr w = fr_to_mont(fr_from_u64(1)), d = g;
+        for (int i = 255; i >= 0; --i) {
+            w = mont_mul(w, w);
+            if ((e.w[i >> 5] >> (i & 31)) & 1) w = mont_mul(w, g);
+        }
+        for (int i = 0; i < 28; ++i) d = mont_mul(d, d);
+        return PpConsts{fr_from_mont(d), fr_from_mont(w)};
+    }();
+    return k;
+}
+// omega_k R for 1 <= k <= 28.
+static Fr pp_omega_mont(uint32_t k) {
+    Fr w = fr_to_mont(pp_consts().omega28);
+    for (uint32_t i = k; i < 28; ++i) w = mont_mul(w, w);
+    return w;
+}
+static uint32_t pp_split(uint32_t k) { return (k + 1) / 2; }
+// The context's omega tables for k: omega^i R for i < 2^h, then omega^(i 2^h) R for i < 2^(k - h).
+static const std::vector<Fr>& pp_tables(svdw_ctx* c, uint32_t k) {
+    if (c->pp_k == k && !c->pp_w.empty()) return c->pp_w;
+    const uint32_t h = pp_split(k);
+    const size_t nlo = (size_t)1 << h, nhi = (size_t)1 << (k - h);
+    std::vector<Fr> t(nlo + nhi);
+    const Fr w = pp_omega_mont(k), one = fr_to_mont(fr_from_u64(1));
+    t[0] = one;
+    for (size_t i = 1; i < nlo; ++i) t[i] = mont_mul(t[i - 1], w);
+    const Fr wh = mont_mul(t[nlo - 1], w);
+    t[nlo] = one;
+    for (size_t i = 1; i < nhi; ++i) t[nlo + i] = mont_mul(t[nlo + i - 1], wh);
+    c->pp_w.swap(t);
+    c->pp_k = k;
+    return c->pp_w;
+}
+// x delta^j phi for j < n (phi = 1 canonical, R Montgomery), x canonical.
+static void pp_delta_powers(const Fr& x, int form, uint32_t n, Fr* out) {
+    const Fr dm = fr_to_mont(pp_consts().delta);
+    Fr v = form == SVDW_FORM_MONTGOMERY ? fr_to_mont(x) : x;
+    for (uint32_t j = 0; j < n; ++j) {
+        out[j] = v;
+        v = mont_mul(v, dm);
+    }
+}
+int svdw_permutation_constants(uint32_t k, uint64_t delta[4], uint64_t omega[4]) {
+    return guarded([&] {
+        REQUIRE(delta && omega, "null argument");
+        if (k < 1 || k > 28) fail(SVDW_ERANGE, "svdw_permutation_constants: k must be in [1, 28]");
+        fr_store_words(pp_consts().delta, delta);
+        fr_store_words(fr_from_mont(pp_omega_mont(k)), omega);
+    });
+}
+int svdw_permutation_values(svdw_ctx* c, uint32_t k, int form, const uint64_t* mapping, uint32_t first_col,
+                            uint32_t ncols, uint32_t total_cols, void* out, uint64_t* out_of_range) {
+    return guarded([&] {
+        REQUIRE(c && out_of_range, "null argument");
+        check_form(form);
+        if (k < 1 || k > 28) fail(SVDW_ERANGE, "svdw_permutation_values: k must be in [1, 28]");
+        REQUIRE(!c->dry, "svdw_permutation_values needs a device context");
+        if (ncols > 65535 || total_cols > 65535) fail(SVDW_ERANGE, "svdw_permutation_values: more than 65535 columns");
+        *out_of_range = 0;
+        if (!ncols) return;
+        REQUIRE(out, "null output");
+        sync(c);
+        const std::vector<Fr>& w = pp_tables(c, k);
+        const uint32_t h = pp_split(k);
+        const size_t nd = std::max(total_cols, 1u), bytes = (nd + w.size()) * sizeof(Fr);
+        c->pp_up.resize(bytes);
+        pp_delta_powers(fr_from_u64(1), form, total_cols, (Fr*)c->pp_up.data());
+        memcpy(c->pp_up.data() + nd * sizeof(Fr), w.data(), w.size() * sizeof(Fr));
+        ensure_buf(c, c->lkp, 128 + bytes);
+        unsigned long long* cnt = (unsigned long long*)c->lkp.p;
+        const Fr* dl = (const Fr*)((char*)c->lkp.p + 128);
+        hipck(hipMemsetAsync(cnt, 0, 128, c->st), "hipMemsetAsync");
+        hipck(hipMemcpyAsync((void*)dl, c->pp_up.data(), bytes, hipMemcpyHostToDevice, c->st), "H2D");
+        {
+            ProfScope ps(c, c->st, "k_pp_values", (mapping ? 40.0 : 32.0) * ncols * (double)(1ull << k), 0);
+            hipck(launch_pp_values(mapping, dl, dl + nd, dl + nd + ((size_t)1 << h), h, first_col, ncols, total_cols,
+                                   1ull << k, (Fr*)out, cnt, c->st), "k_pp_values");
+        }
+        unsigned long long bad = 0;
+        hipck(hipMemcpyAsync(&bad, cnt, sizeof bad, hipMemcpyDeviceToHost, c->st), "D2H");
+        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+        *out_of_range = bad;
+    });
+}
+// The argument checks of both entries, in the order include/svdw.h gives, and
+// the device tables; false: no columns, nothing to do.
+static bool pp_args(svdw_ctx* c, const char* fn, uint32_t k, uint32_t unusable_rows, int form,
+                    const void* const* columns, const void* const* sigma, uint32_t ncols, uint32_t chunk_len,
+                    const uint64_t beta[4], const uint64_t gamma[4], const void* z, bool scratch, PpDev* d) {
+    const std::string f(fn);
+    REQUIRE(c && beta && gamma, "null argument");
+    check_form(form);
+    const Fr b = fr_raw_words(beta), g = fr_raw_words(gamma);
+    REQUIRE(fr_reduced(b) && fr_reduced(g), f + ": beta or gamma >= p");
+    const uint64_t rows = k < 63 ? 1ull << k : ~0ull;
+    if (!unusable_rows) fail(SVDW_ERANGE, f + ": unusable_rows == 0 leaves no row for Z[usable]");
+    if (unusable_rows >= rows) fail(SVDW_ERANGE, f + ": unusable_rows leaves no usable row");
+    REQUIRE(chunk_len, f + ": chunk_len == 0");
+    if (k < 1 || k > 28) fail(SVDW_ERANGE, f + ": k must be in [1, 28]");
+    REQUIRE(!c->dry, f + " needs a device context");
+    PpArgs& a = d->a;
+    a.rows = rows;
+    a.usable = rows - unusable_rows;
+    a.ncols = ncols;
+    a.chunk = chunk_len;
+    a.nsets = ncols ? pp_sets(ncols, chunk_len) : 0;
+    if (!ncols) return false;
+    if (ncols > 65535) fail(SVDW_ERANGE, f + ": more than 65535 columns");
+    REQUIRE(columns && sigma && z, "null argument");
+    for (uint32_t j = 0; j < ncols; ++j) REQUIRE(columns[j] && sigma[j], f + ": null column pointer");
+    sync(c);
+    const bool mont = form == SVDW_FORM_MONTGOMERY;
+    const std::vector<Fr>& w = pp_tables(c, k);
+    a.h = pp_split(k);
+    a.bR = fr_to_mont(b);
+    a.g = mont ? fr_to_mont(g) : g;
+    a.one = fr_to_mont(fr_from_u64(1));
+    const size_t pbytes = ((size_t)2 * ncols * sizeof(void*) + 31) / 32 * 32;
+    const size_t up = pbytes + ((size_t)ncols + w.size()) * sizeof(Fr);
+    c->pp_up.assign(up, 0);
+    memcpy(c->pp_up.data(), columns, ncols * sizeof(void*));
+    memcpy(c->pp_up.data() + ncols * sizeof(void*), sigma, ncols * sizeof(void*));
+    pp_delta_powers(b, form, ncols, (Fr*)(c->pp_up.data() + pbytes));
+    memcpy(c->pp_up.data() + pbytes + ncols * sizeof(Fr), w.data(), w.size() * sizeof(Fr));
+    const uint64_t cells = scratch ? pp_scratch_cells(a.nsets, rows) : 0;
+    ensure_buf(c, c->lkp, 128 + up + cells * sizeof(Fr));
+    char* base = (char*)c->lkp.p;
+    d->cnt = (unsigned long long*)base;
+    a.cols = (const Fr* const*)(base + 128);
+    a.sig = a.cols + ncols;
+    a.bd = (const Fr*)(base + 128 + pbytes);
+    a.wlo = a.bd + ncols;
+    a.whi = a.wlo + ((size_t)1 << a.h);
+    d->sv = (Fr*)(base + 128 + up);
+    d->xs = d->sv + 2 * (uint64_t)a.nsets;
+    d->tp = d->xs + 2 * (uint64_t)kPpCarryThreads * a.nsets;
+    hipck(hipMemsetAsync(d->cnt, 0, 128, c->st), "hipMemsetAsync");
+    hipck(hipMemcpyAsync(base + 128, c->pp_up.data(), up, hipMemcpyHostToDevice, c->st), "H2D");
+    return true;
+}
+int svdw_permutation_product(svdw_ctx* c, uint32_t k, uint32_t unusable_rows, int form, const void* const* columns,
+                             const void* const* sigma, uint32_t ncols, uint32_t chunk_len, const uint64_t beta[4],
+                             const uint64_t gamma[4], void* z, svdw_permutation_product_result* result) {
+    return guarded([&] {
+        REQUIRE(result, "null argument");
+        PpDev d;
+        const bool any = pp_args(c, "svdw_permutation_product", k, unusable_rows, form, columns, sigma, ncols,
+                                 chunk_len, beta, gamma, z, true, &d);
+        memset(result, 0, sizeof *result);
+        result->usable_rows = d.a.usable;
+        if (!any) return;
+        const PpArgs& a = d.a;
+        const double cells = (double)ncols * a.usable, nt = (double)lp_tiles(a.rows);
+        {
+            ProfScope ps(c, c->st, "k_pp_tiles", 64.0 * cells, 0);
+            hipck(launch_pp_tiles(a, form, d.tp, d.cnt, c->st), "k_pp_tiles");
+        }
+        {
+            ProfScope ps(c, c->st, "k_pp_totals", 64.0 * a.nsets * nt, 0);
+            hipck(launch_pp_totals(a, form, d.tp, d.xs, d.sv, c->st), "k_pp_totals");
+        }
+        {
+            ProfScope ps(c, c->st, "k_pp_chain", 128.0 * a.nsets, 0);
+            hipck(launch_pp_chain(a, d.sv, d.cnt, c->st), "k_pp_chain");
+        }
+        {
+            ProfScope ps(c, c->st, "k_pp_fold", 128.0 * a.nsets * nt, 0);
+            hipck(launch_pp_fold(a, form, d.tp, d.xs, d.sv, c->st), "k_pp_fold");
+        }
+        {
+            ProfScope ps(c, c->st, "k_pp_write", 64.0 * cells + 32.0 * a.nsets * a.rows, 0);
+            hipck(launch_pp_write(a, form, d.tp, (Fr*)z, c->st), "k_pp_write");
+        }
+        unsigned long long h[2];
+        hipck(hipMemcpyAsync(h, d.cnt, sizeof h, hipMemcpyDeviceToHost, c->st), "D2H");
+        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+        result->columns = ncols;
+        result->sets = a.nsets;
+        result->zero_denominators = h[0];
+        result->final_not_one = (uint32_t)h[1];
+    });
+}
+int svdw_check_permutation_product(svdw_ctx* c, uint32_t k, uint32_t unusable_rows, int form,
+                                   const void* const* columns, const void* const* sigma, uint32_t ncols,
+                                   uint32_t chunk_len, const uint64_t beta[4], const uint64_t gamma[4], const void* z,
+                                   svdw_permutation_product_check* result) {
+    return guarded([&] {
+        REQUIRE(result, "null argument");
+        PpDev d;
+        const bool any = pp_args(c, "svdw_check_permutation_product", k, unusable_rows, form, columns, sigma, ncols,
+                                 chunk_len, beta, gamma, z, false, &d);
+        memset(result, 0, sizeof *result);
+        if (!any) return;
+        const PpArgs& a = d.a;
+        const Fr wstep = fr_to_mont(fr_pow_u64(fr_from_mont(pp_omega_mont(k)), pp_check_stride(a.rows)));
+        {
+            ProfScope ps(c, c->st, "k_pp_check", 64.0 * ncols * a.usable + 32.0 * a.nsets * a.rows, 0);
+            hipck(launch_pp_check(a, form, (const Fr*)z, wstep, d.cnt, c->st), "k_pp_check");
+        }
+        unsigned long long h[6];
+        hipck(hipMemcpyAsync(h, d.cnt, sizeof h, hipMemcpyDeviceToHost, c->st), "D2H");
         hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
         result->recurrence_checked = h[0];
         result->recurrence_failures = h[1];

@@ -20,7 +20,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import (CheckResult, EqCheck, LookupCheck, LookupProductCheck, LookupProductResult, LookupResult, PhysParams, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SvdwError,
+from ._lib import (CheckResult, EqCheck, LookupCheck, LookupProductCheck, LookupProductResult, LookupResult, PermutationProductCheck, PermutationProductResult, PhysParams, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SvdwError,
                    Vec, check, lib)
 
 P_MOD = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -29,7 +29,7 @@ __all__ = ["Context", "ZkMatrix", "ZkVector", "honest_prover_mat_mul", "field_ma
            "mat_times_diag_mat", "check_mat_diff", "check_mat_id", "check_mat_entries_bounded",
            "check_svd_phase0", "check_svd_phase1", "err_calc", "svd_witness", "plan_svd",
            "SvdwError", "SvdPayload", "SvdConfigPy", "P_MOD", "int_to_words", "words_to_int",
-           "fr_convert", "quantization", "dequantization", "format_f64_debug"]
+           "fr_convert", "quantization", "dequantization", "format_f64_debug", "permutation_constants"]
 
 
 def int_to_words(x: int) -> np.ndarray:
@@ -85,6 +85,14 @@ def fr_convert(values, from_: str, to: str) -> np.ndarray:
     out = np.empty_like(a)
     check(lib().svdw_fr_convert(a.ctypes.data, a.shape[0], _form(from_), _form(to), out.ctypes.data))
     return out
+
+
+def permutation_constants(k: int):
+    """(delta, omega_k) of BN254 Fr as ints: delta = 7^(2^28), omega_k =
+    7^((p - 1) / 2^k) generates the 2^k rows (svdw_permutation_constants)."""
+    d, w = (ct.c_uint64 * 4)(), (ct.c_uint64 * 4)()
+    check(lib().svdw_permutation_constants(k, d, w))
+    return words_to_int(d), words_to_int(w)
 
 
 def quantization(x: float, precision_bits: int) -> int:
@@ -596,6 +604,106 @@ class Context:
                                               permuted_table.data_ptr() if nl else None, b, g,
                                               z.data_ptr() if nl else None, ct.byref(r)))
         return {k: getattr(r, k) for k, _ in LookupProductCheck._fields_}
+
+    # ---- permutation argument (include/svdw.h, "permutation argument"; parity unpinned)
+    def permutation_values(self, k: int, mapping=None, first_col: int = 0, ncols: Optional[int] = None,
+                           total_cols: Optional[int] = None, form: str = "canonical"):
+        """(sigma, out_of_range): [ncols, 2^k, 32] u8 device cells delta^col omega^row
+        in `form` (svdw_permutation_values). mapping: an int64 device tensor
+        [ncols, 2^k] of col << 32 | row entries, the cell each (column, row) maps
+        to, or None for the identity of the columns first_col .. first_col + ncols.
+        total_cols defaults to first_col + ncols; an entry outside it or outside
+        the 2^k rows is written as zero and counted."""
+        import torch
+        rows = 1 << k if 0 <= k < 32 else 0
+        if mapping is not None:
+            if (not mapping.is_cuda or mapping.dtype != torch.int64 or not mapping.is_contiguous()
+                    or mapping.dim() != 2 or mapping.shape[1] != rows):
+                raise SvdwError(-1, "mapping must be a contiguous int64 device tensor [n, 2^k]")
+            if ncols is not None and ncols != mapping.shape[0]:
+                raise SvdwError(-1, "ncols differs from the mapping's columns")
+            ncols = mapping.shape[0]
+        elif ncols is None:
+            raise SvdwError(-1, "ncols is required without a mapping")
+        if total_cols is None:
+            total_cols = first_col + ncols
+        dev = mapping.device if mapping is not None else torch.device("cuda", self.device)
+        out = torch.empty((ncols, rows, 32), dtype=torch.uint8, device=dev)
+        bad = ct.c_uint64()
+        _after_torch(self)
+        check(lib().svdw_permutation_values(self._h, k, _form(form),
+                                            mapping.data_ptr() if mapping is not None and ncols else None,
+                                            first_col, ncols, total_cols, out.data_ptr() if ncols else None,
+                                            ct.byref(bad)))
+        _before_torch(self)
+        return out, bad.value
+
+    @staticmethod
+    def _column_pointers(what: str, cols, rows: int):
+        """(ctypes array of one device pointer per column, count, device) of a
+        tensor [n, 2^k, 32] u8 or a list of such tensors, concatenated in order."""
+        import torch
+        ptrs, dev = [], None
+        for t in ([cols] if isinstance(cols, torch.Tensor) else list(cols)):
+            if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous()
+                    or t.dim() != 3 or tuple(t.shape[1:]) != (rows, 32)):
+                raise SvdwError(-1, f"{what} must be contiguous uint8 device tensors [n, 2^k, 32]")
+            dev = dev or t.device
+            ptrs += [t.data_ptr() + i * rows * 32 for i in range(t.shape[0])]
+        return (ct.c_void_p * max(len(ptrs), 1))(*ptrs), len(ptrs), dev
+
+    def _permutation_args(self, columns, sigma, k: int):
+        rows = 1 << k if 0 <= k < 32 else 0
+        cp, n, dev = self._column_pointers("columns", columns, rows)
+        sp, ns, _ = self._column_pointers("sigma", sigma, rows)
+        if n != ns:
+            raise SvdwError(-1, "columns and sigma differ in their number of columns")
+        return cp, sp, n, rows, dev
+
+    def permutation_product(self, columns, sigma, beta: int, gamma: int, chunk_len: int, k: int,
+                            unusable_rows: int = 6, form: str = "canonical", out=None):
+        """(Z, result): the permutation argument's grand-product columns for the
+        challenges beta, gamma (ints below p), one per set of chunk_len columns, a
+        [nsets, 2^k, 32] u8 device tensor in `form`: Z_0[0] = 1, each set starts
+        where the one before ended, the last Z[usable] = 1 for an honest sigma,
+        rows above zero (svdw_permutation_product). columns, sigma: a tensor
+        [n, 2^k, 32] u8 in `form` or a list of such tensors, concatenated in order.
+        result: columns, sets, usable_rows, zero_denominators, final_not_one."""
+        import torch
+        b, g = _challenge_arg(beta), _challenge_arg(gamma)
+        cp, sp, n, rows, dev = self._permutation_args(columns, sigma, k)
+        nsets = -(-n // chunk_len) if chunk_len > 0 else 0
+        if out is None:
+            out = torch.empty((nsets, rows, 32), dtype=torch.uint8, device=dev or torch.device("cuda", self.device))
+        if (not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous()
+                or tuple(out.shape) != (nsets, rows, 32)):
+            raise SvdwError(-1, "out must be a contiguous uint8 device tensor [nsets, 2^k, 32]")
+        r = PermutationProductResult()
+        _after_torch(self)
+        check(lib().svdw_permutation_product(self._h, k, unusable_rows, _form(form), cp, sp, n, chunk_len, b, g,
+                                             out.data_ptr() if nsets else None, ct.byref(r)))
+        _before_torch(self)
+        return out, {"columns": r.columns, "sets": r.sets, "usable_rows": r.usable_rows,
+                     "zero_denominators": r.zero_denominators, "final_not_one": r.final_not_one}
+
+    def check_permutation_product(self, columns, sigma, z, beta: int, gamma: int, chunk_len: int, k: int,
+                                  unusable_rows: int = 6, form: str = "canonical") -> dict:
+        """Device check of Z in `form` against the columns, sigma and the
+        challenges, division-free (svdw_check_permutation_product): checked /
+        failure counts of the recurrence, the chain and boundary rows and the
+        padding."""
+        import torch
+        b, g = _challenge_arg(beta), _challenge_arg(gamma)
+        cp, sp, n, rows, _ = self._permutation_args(columns, sigma, k)
+        nsets = -(-n // chunk_len) if chunk_len > 0 else 0
+        if (not isinstance(z, torch.Tensor) or not z.is_cuda or z.dtype != torch.uint8 or not z.is_contiguous()
+                or tuple(z.shape) != (nsets, rows, 32)):
+            raise SvdwError(-1, "z must be a contiguous uint8 device tensor [nsets, 2^k, 32]")
+        r = PermutationProductCheck()
+        _after_torch(self)
+        check(lib().svdw_check_permutation_product(self._h, k, unusable_rows, _form(form), cp, sp, n, chunk_len,
+                                                   b, g, z.data_ptr() if nsets else None, ct.byref(r)))
+        return {k_: getattr(r, k_) for k_, _ in PermutationProductCheck._fields_}
 
     def profile(self, on: bool = True, prefix: str = "") -> None:
         """Record HIP events around kernel launches (names starting with `prefix`)."""

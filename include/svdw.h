@@ -670,6 +670,78 @@ int svdw_check_lookup_product(svdw_ctx* ctx, uint32_t phase, uint32_t unusable_r
                               uint32_t ncols, const void* permuted_input, const void* permuted_table,
                               const uint64_t beta[4], const uint64_t gamma[4], const void* z,
                               svdw_lookup_product_check* result);
+/* ----------------------------------------------------- permutation argument
+ * The copy-constraint argument's grand-product columns Z of halo2_proofs'
+ * plonk::permutation::prover::Argument::commit. Restated from memory like the
+ * two lookup steps: PARITY UNPINNED. These calls need no witness and no
+ * physical layout; k is an argument, 1 <= k <= 28.
+ *
+ * Constants of BN254 Fr as in halo2curves: delta = 7^(2^28), omega_k =
+ * 7^((p - 1) / 2^k), the generator of the 2^k rows. Inputs: ncols columns v_j
+ * of 2^k cells in the order of cs.permutation.columns (the caller's business),
+ * their permutation columns sigma_j (pk.permutation.permutations in Lagrange
+ * form: sigma_j[r] = delta^j' omega^r' of the cell that (j, r) maps to), beta,
+ * gamma, chunk_len = cs_degree - 2 >= 1 and unusable_rows >= 1, usable =
+ * 2^k - unusable_rows. Set s holds the columns [s chunk_len, min((s + 1)
+ * chunk_len, ncols)), nsets = ceil(ncols / chunk_len); j counts over all
+ * columns, not within the set; inv0(0) = 0 (ff's batch_invert):
+ *   D_s[r]   = prod_{j in set s} (v_j[r] + beta sigma_j[r] + gamma)
+ *   N_s[r]   = prod_{j in set s} (v_j[r] + beta delta^j omega^r + gamma)
+ *   Z_0[0]   = 1,  Z_s[0] = Z_{s-1}[usable]                 s > 0
+ *   Z_s[r+1] = Z_s[r] N_s[r] inv0(D_s[r])                   0 <= r < usable
+ *   Z_s[r]   = 0                                            usable < r < 2^k
+ * Rows above `usable` are the prover's random blinding rows: the engine writes
+ * zero. For an honest sigma only the last set ends at 1. A zero denominator
+ * makes Z zero from the next row on, and in every later set. Deriving beta and
+ * gamma, the blinding randomness, the commitments and building sigma from
+ * equality records (keygen's cycle merge) stay with the caller. */
+/* delta and omega_k, canonical, 4 little-endian words each. Host only.
+ * k outside 1..28: SVDW_ERANGE. */
+int svdw_permutation_constants(uint32_t k, uint64_t delta[4], uint64_t omega[4]);
+/* Sigma cells on the device: out (DEVICE, ncols x 2^k cells in `form`,
+ * column-major) cell i = delta^col omega^row of mapping[i] = col << 32 | row
+ * (DEVICE array of ncols x 2^k uint64_t, the entries of the columns written).
+ * mapping == NULL: the identity for the columns first_col .. first_col + ncols.
+ * An entry with col >= total_cols or row >= 2^k is written as zero and counted
+ * in *out_of_range. Checks in this order: form (SVDW_EINVAL), k outside 1..28
+ * (SVDW_ERANGE), a planning context (SVDW_EINVAL), ncols or total_cols > 65535
+ * (SVDW_ERANGE); ncols == 0: SVDW_OK, nothing is touched. */
+int svdw_permutation_values(svdw_ctx* ctx, uint32_t k, int form, const uint64_t* mapping, uint32_t first_col,
+                            uint32_t ncols, uint32_t total_cols, void* out, uint64_t* out_of_range);
+typedef struct {
+    uint32_t columns, sets;
+    uint64_t usable_rows;
+    uint64_t zero_denominators;   /* rows r < usable with D_s[r] == 0, all sets */
+    uint32_t final_not_one, _pad; /* 1: the last set's Z[usable] != 1 */
+} svdw_permutation_product_result;
+/* columns, sigma: HOST arrays of ncols DEVICE pointers, each to 2^k cells in
+ * `form` (the caller's columns live in several allocations). z: DEVICE array
+ * of nsets x 2^k cells, column-major, in `form`. All arithmetic is exact mod p;
+ * cells are taken as field elements below p. The checks of the arguments come
+ * first, before anything touches the device, in this order: an unknown form
+ * (SVDW_EINVAL), beta or gamma >= p (SVDW_EINVAL), unusable_rows == 0 or
+ * >= 2^k (SVDW_ERANGE), chunk_len == 0 (SVDW_EINVAL), k outside 1..28
+ * (SVDW_ERANGE), a planning context (SVDW_EINVAL), more than 65535 columns
+ * (SVDW_ERANGE), null pointers (SVDW_EINVAL). ncols == 0: SVDW_OK, sets = 0,
+ * nothing is touched. */
+int svdw_permutation_product(svdw_ctx* ctx, uint32_t k, uint32_t unusable_rows, int form,
+                             const void* const* columns, const void* const* sigma, uint32_t ncols,
+                             uint32_t chunk_len, const uint64_t beta[4], const uint64_t gamma[4], void* z,
+                             svdw_permutation_product_result* result);
+typedef struct {
+    uint64_t recurrence_checked, recurrence_failures;  /* rows r < usable, per set: nsets * usable */
+    uint64_t boundary_checked, boundary_failures;      /* Z_0[0] == 1, Z_s[0] == Z_{s-1}[usable], the last
+                                                          Z[usable] in {0, 1}: nsets + 1 */
+    uint64_t padding_checked, padding_failures;        /* Z rows > usable are zero: nsets * (unusable_rows - 1) */
+} svdw_permutation_product_check;
+/* The product's own constraints on Z in `form`, on the device, in the
+ * division-free form Z_s[r + 1] D_s[r] == Z_s[r] N_s[r] for r < usable with the
+ * raw N and D; it shares no inversion and no scan with
+ * svdw_permutation_product. Arguments and their checks as for the product. */
+int svdw_check_permutation_product(svdw_ctx* ctx, uint32_t k, uint32_t unusable_rows, int form,
+                                   const void* const* columns, const void* const* sigma, uint32_t ncols,
+                                   uint32_t chunk_len, const uint64_t beta[4], const uint64_t gamma[4],
+                                   const void* z, svdw_permutation_product_check* result);
 /* Up to cap segments of the last witness into out; *n = total count. */
 int svdw_shard_segments(const svdw_ctx* ctx, svdw_segment* out, uint64_t cap, uint64_t* n);
 
