@@ -4949,6 +4949,24 @@ static bool lk_args(svdw_ctx* c, const char* fn, uint32_t phase, uint32_t unusab
                      : LkSrc{c->ph[phase].lk, P.R, P.R, TL};
     return ncols != 0;
 }
+// The 128-byte counter block at the head of the lookup scratch (which the caller
+// has sized), zeroed on the stream.
+static unsigned long long* zero_counters(svdw_ctx* c) {
+    unsigned long long* cnt = (unsigned long long*)c->lkp.p;
+    hipck(hipMemsetAsync(cnt, 0, 128, c->st), "hipMemsetAsync");
+    return cnt;
+}
+// h[0..n) = the counters, once the stream has run dry.
+static void read_counters(svdw_ctx* c, const unsigned long long* cnt, unsigned long long* h, size_t n) {
+    hipck(hipMemcpyAsync(h, cnt, n * sizeof *h, hipMemcpyDeviceToHost, c->st), "D2H");
+    hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+}
+// One launch on the context's stream under its profile label.
+extern "C++" template <class Launch>
+static void profiled(svdw_ctx* c, const char* label, double bytes, Launch&& launch) {
+    ProfScope ps(c, c->st, label, bytes, 0);
+    hipck(launch(), label);
+}
 int svdw_lookup_multiplicities(svdw_ctx* c, uint32_t phase, uint32_t unusable_rows, const void* columns,
                                uint32_t ncols, uint32_t* mult) {
     return guarded([&] {
@@ -4957,13 +4975,10 @@ int svdw_lookup_multiplicities(svdw_ctx* c, uint32_t phase, uint32_t unusable_ro
         REQUIRE(mult, "null output");
         sync(c);
         ensure_buf(c, c->lkp, 128);
-        unsigned long long* oot = (unsigned long long*)c->lkp.p;
-        hipck(hipMemsetAsync(oot, 0, 128, c->st), "hipMemsetAsync");
+        unsigned long long* oot = zero_counters(c);
         hipck(hipMemsetAsync(mult, 0, ((size_t)ncols << a.lb) * sizeof(uint32_t), c->st), "hipMemsetAsync");
-        {
-            ProfScope ps(c, c->st, "k_lk_hist", 32.0 * ncols * a.usable, 0);
-            hipck(launch_lk_hist(a.src, SVDW_FORM_CANONICAL, ncols, a.usable, a.lb, mult, oot, c->st), "k_lk_hist");
-        }
+        profiled(c, "k_lk_hist", 32.0 * ncols * a.usable,
+                 [&] { return launch_lk_hist(a.src, SVDW_FORM_CANONICAL, ncols, a.usable, a.lb, mult, oot, c->st); });
         hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
     });
 }
@@ -4990,25 +5005,18 @@ int svdw_lookup_permute(svdw_ctx* c, uint32_t phase, uint32_t unusable_rows, int
         s.bsum = s.absent + bins;
         s.tot = s.bsum + 2 * ncols * nblk;
         hipck(hipMemsetAsync(c->lkp.p, 0, 128 + bins * sizeof(uint32_t), c->st), "hipMemsetAsync");
-        {
-            ProfScope ps(c, c->st, "k_lk_hist", 32.0 * ncols * a.usable, 0);
-            hipck(launch_lk_hist(a.src, SVDW_FORM_CANONICAL, ncols, a.usable, a.lb, s.cnt, oot, c->st), "k_lk_hist");
-        }
+        profiled(c, "k_lk_hist", 32.0 * ncols * a.usable,
+                 [&] { return launch_lk_hist(a.src, SVDW_FORM_CANONICAL, ncols, a.usable, a.lb, s.cnt, oot, c->st); });
         unsigned long long bad = 0;
-        hipck(hipMemcpyAsync(&bad, oot, sizeof bad, hipMemcpyDeviceToHost, c->st), "D2H");
-        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+        read_counters(c, oot, &bad, 1);
         result->columns = ncols;
         result->out_of_table = bad;
         if (bad) return;                                    // ConstraintSystemFailure: the outputs stay as they are
-        {
-            ProfScope ps(c, c->st, "k_lk_scan", 20.0 * bins, 0);
-            hipck(launch_lk_scans(s, ncols, a.lb, c->st), "k_lk_scan");
-        }
-        {
-            ProfScope ps(c, c->st, "k_lk_fill", 64.0 * ncols * a.rows, 0);
-            hipck(launch_lk_fill(s, ncols, a.rows, a.usable, a.lb, form, (Fr*)permuted_input, (Fr*)permuted_table,
-                                 c->st), "k_lk_fill");
-        }
+        profiled(c, "k_lk_scan", 20.0 * bins, [&] { return launch_lk_scans(s, ncols, a.lb, c->st); });
+        profiled(c, "k_lk_fill", 64.0 * ncols * a.rows, [&] {
+            return launch_lk_fill(s, ncols, a.rows, a.usable, a.lb, form, (Fr*)permuted_input, (Fr*)permuted_table,
+                                  c->st);
+        });
         std::vector<uint32_t> tot(ncols);
         hipck(hipMemcpyAsync(tot.data(), s.tot, ncols * sizeof(uint32_t), hipMemcpyDeviceToHost, c->st), "D2H");
         hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
@@ -5043,14 +5051,12 @@ int svdw_check_lookup_argument(svdw_ctx* c, uint32_t phase, uint32_t unusable_ro
                                  a.lb, htab, cnt + 8, c->st), "k_lk_hist");
             hipck(launch_lk_compare(ha, hpin, htab, ncols, a.usable, a.lb, cnt + 4, c->st), "k_lk_compare");
         }
-        {
-            ProfScope ps(c, c->st, "k_lk_adjacent", 64.0 * ncols * a.rows, 0);
-            hipck(launch_lk_adjacent((const Fr*)permuted_input, (const Fr*)permuted_table, ncols, a.rows, a.usable,
-                                     cnt, c->st), "k_lk_adjacent");
-        }
+        profiled(c, "k_lk_adjacent", 64.0 * ncols * a.rows, [&] {
+            return launch_lk_adjacent((const Fr*)permuted_input, (const Fr*)permuted_table, ncols, a.rows, a.usable,
+                                      cnt, c->st);
+        });
         unsigned long long h[9];
-        hipck(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, c->st), "D2H");
-        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+        read_counters(c, cnt, h, 9);
         result->adjacency_checked = h[0];
         result->adjacency_failures = h[1];
         result->padding_checked = h[2];
@@ -5059,64 +5065,82 @@ int svdw_check_lookup_argument(svdw_ctx* c, uint32_t phase, uint32_t unusable_ro
         result->multiset_failures = h[5] + h[8];           // a cell outside the table is in no bin
     });
 }
-// ---- lookup argument: the grand product Z and its check (lookup_product.hpp)
-// The argument checks of both entries; false: no columns, nothing to do.
-static bool lp_args(svdw_ctx* c, const char* fn, uint32_t phase, uint32_t unusable_rows, int form, const void* columns,
-                    uint32_t ncols, const uint64_t beta[4], const uint64_t gamma[4], LkArgs* a, LpChal* ch) {
+// ---- the grand products Z and their checks (grand_product.hpp)
+// What the lookup's and the permutation's entries check first, in this order:
+// the form, beta and gamma (to b, g), a row for Z[usable].
+static void gp_challenges(const char* fn, int form, const uint64_t beta[4], const uint64_t gamma[4],
+                          uint32_t unusable_rows, Fr* b, Fr* g) {
     const std::string f(fn);
     REQUIRE(beta && gamma, "null argument");
     check_form(form);
-    const Fr b = fr_raw_words(beta), g = fr_raw_words(gamma);
-    REQUIRE(fr_reduced(b) && fr_reduced(g), f + ": beta or gamma >= p");
+    *b = fr_raw_words(beta);
+    *g = fr_raw_words(gamma);
+    REQUIRE(fr_reduced(*b) && fr_reduced(*g), f + ": beta or gamma >= p");
     if (!unusable_rows) fail(SVDW_ERANGE, f + ": unusable_rows == 0 leaves no row for Z[usable]");
-    if (!lk_args(c, fn, phase, unusable_rows, columns, ncols, a)) return false;
+}
+// The six counters of a check kernel into either argument's check result.
+extern "C++" template <class Check>
+static void gp_check_result(svdw_ctx* c, const unsigned long long* cnt, Check* result) {
+    unsigned long long h[6];
+    read_counters(c, cnt, h, 6);
+    result->recurrence_checked = h[0];
+    result->recurrence_failures = h[1];
+    result->boundary_checked = h[2];
+    result->boundary_failures = h[3];
+    result->padding_checked = h[4];
+    result->padding_failures = h[5];
+}
+// ---- lookup argument: the grand product Z and its check (lookup_product.hpp)
+// The argument checks of both entries and what the kernels read (a->usable also
+// without columns); false: no columns, nothing to do.
+static bool lp_args(svdw_ctx* c, const char* fn, uint32_t phase, uint32_t unusable_rows, int form, const void* columns,
+                    uint32_t ncols, const void* permuted_input, const void* permuted_table, const uint64_t beta[4],
+                    const uint64_t gamma[4], LpArgs* a) {
+    Fr b, g;
+    gp_challenges(fn, form, beta, gamma, unusable_rows, &b, &g);
+    LkArgs lk;
+    const bool any = lk_args(c, fn, phase, unusable_rows, columns, ncols, &lk);
     const bool mont = form == SVDW_FORM_MONTGOMERY;
-    ch->b0 = b;
-    ch->g0 = g;
-    ch->bx = mont ? fr_to_mont(b) : b;
-    ch->gx = mont ? fr_to_mont(g) : g;
-    ch->g2 = fr_to_mont(fr_to_mont(g));
-    ch->t2 = fr_to_mont(fr_to_mont(fr_from_u64(1ull << 32)));
-    ch->one = fr_to_mont(fr_from_u64(1));
-    return true;
+    a->src = lk.src;
+    a->pin = (const Fr*)permuted_input;
+    a->ptab = (const Fr*)permuted_table;
+    a->ncols = ncols;
+    a->lb = lk.lb;
+    a->rows = lk.rows;
+    a->usable = lk.usable;
+    a->ch.b0 = b;
+    a->ch.g0 = g;
+    a->ch.bx = mont ? fr_to_mont(b) : b;
+    a->ch.gx = mont ? fr_to_mont(g) : g;
+    a->ch.g2 = fr_to_mont(fr_to_mont(g));
+    a->ch.t2 = fr_to_mont(fr_to_mont(fr_from_u64(1ull << 32)));
+    a->ch.one = fr_to_mont(fr_from_u64(1));
+    return any;
 }
 int svdw_lookup_product(svdw_ctx* c, uint32_t phase, uint32_t unusable_rows, int form, const void* columns,
                         uint32_t ncols, const void* permuted_input, const void* permuted_table,
                         const uint64_t beta[4], const uint64_t gamma[4], void* z, svdw_lookup_product_result* result) {
     return guarded([&] {
         REQUIRE(result, "null argument");
-        LkArgs a;
-        LpChal ch;
-        const bool any = lp_args(c, "svdw_lookup_product", phase, unusable_rows, form, columns, ncols, beta, gamma,
-                                 &a, &ch);
+        LpArgs a;
+        const bool any = lp_args(c, "svdw_lookup_product", phase, unusable_rows, form, columns, ncols, permuted_input,
+                                 permuted_table, beta, gamma, &a);
         memset(result, 0, sizeof *result);
         result->usable_rows = a.usable;
         if (!any) return;
         REQUIRE(permuted_input && permuted_table && z, "null argument");
         sync(c);
-        const uint64_t nt = lp_tiles(a.rows);
+        const uint64_t nt = gp_tiles(a.rows);
         ensure_buf(c, c->lkp, 128 + 2 * ncols * nt * sizeof(Fr));
-        unsigned long long* cnt = (unsigned long long*)c->lkp.p;   // [0] zero denominators, [1] columns with Z[usable] != 1
+        unsigned long long* cnt = zero_counters(c);        // [0] zero denominators, [1] columns with Z[usable] != 1
         Fr* tp = (Fr*)((char*)c->lkp.p + 128);
-        const Fr *pin = (const Fr*)permuted_input, *ptab = (const Fr*)permuted_table;
-        hipck(hipMemsetAsync(cnt, 0, 128, c->st), "hipMemsetAsync");
-        {
-            ProfScope ps(c, c->st, "k_lp_tiles", 96.0 * ncols * a.usable, 0);
-            hipck(launch_lp_tiles(a.src, pin, ptab, ch, form, ncols, a.rows, a.usable, a.lb, tp, cnt, c->st),
-                  "k_lp_tiles");
-        }
-        {
-            ProfScope ps(c, c->st, "k_lp_carry", 128.0 * ncols * nt, 0);
-            hipck(launch_lp_carry(tp, ch, form, ncols, a.rows, cnt, c->st), "k_lp_carry");
-        }
-        {
-            ProfScope ps(c, c->st, "k_lp_write", 96.0 * ncols * a.usable + 32.0 * ncols * a.rows, 0);
-            hipck(launch_lp_write(a.src, pin, ptab, ch, form, ncols, a.rows, a.usable, a.lb, tp, (Fr*)z, c->st),
-                  "k_lp_write");
-        }
+        const double cells = (double)ncols * a.usable;
+        profiled(c, "k_lp_tiles", 96.0 * cells, [&] { return launch_lp_tiles(a, form, tp, cnt, c->st); });
+        profiled(c, "k_lp_carry", 128.0 * ncols * nt, [&] { return launch_lp_carry(a, form, tp, cnt, c->st); });
+        profiled(c, "k_lp_write", 96.0 * cells + 32.0 * ncols * a.rows,
+                 [&] { return launch_lp_write(a, form, tp, (Fr*)z, c->st); });
         unsigned long long h[2];
-        hipck(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, c->st), "D2H");
-        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+        read_counters(c, cnt, h, 2);
         result->columns = ncols;
         result->zero_denominators = h[0];
         result->final_not_one = h[1];
@@ -5128,31 +5152,18 @@ int svdw_check_lookup_product(svdw_ctx* c, uint32_t phase, uint32_t unusable_row
                               svdw_lookup_product_check* result) {
     return guarded([&] {
         REQUIRE(result, "null argument");
-        LkArgs a;
-        LpChal ch;
-        const bool any = lp_args(c, "svdw_check_lookup_product", phase, unusable_rows, form, columns, ncols, beta,
-                                 gamma, &a, &ch);
+        LpArgs a;
+        const bool any = lp_args(c, "svdw_check_lookup_product", phase, unusable_rows, form, columns, ncols,
+                                 permuted_input, permuted_table, beta, gamma, &a);
         memset(result, 0, sizeof *result);
         if (!any) return;
         REQUIRE(permuted_input && permuted_table && z, "null argument");
         sync(c);
         ensure_buf(c, c->lkp, 128);
-        unsigned long long* cnt = (unsigned long long*)c->lkp.p;
-        hipck(hipMemsetAsync(cnt, 0, 128, c->st), "hipMemsetAsync");
-        {
-            ProfScope ps(c, c->st, "k_lp_check", 96.0 * ncols * a.usable + 32.0 * ncols * a.rows, 0);
-            hipck(launch_lp_check(a.src, (const Fr*)permuted_input, (const Fr*)permuted_table, (const Fr*)z, ch, form,
-                                  ncols, a.rows, a.usable, a.lb, cnt, c->st), "k_lp_check");
-        }
-        unsigned long long h[6];
-        hipck(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, c->st), "D2H");
-        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
-        result->recurrence_checked = h[0];
-        result->recurrence_failures = h[1];
-        result->boundary_checked = h[2];
-        result->boundary_failures = h[3];
-        result->padding_checked = h[4];
-        result->padding_failures = h[5];
+        unsigned long long* cnt = zero_counters(c);
+        profiled(c, "k_lp_check", 96.0 * ncols * a.usable + 32.0 * ncols * a.rows,
+                 [&] { return launch_lp_check(a, form, (const Fr*)z, cnt, c->st); });
+        gp_check_result(c, cnt, result);
     });
 }
 // ---- permutation argument: sigma values, the grand products Z and their check
@@ -5243,18 +5254,15 @@ int svdw_permutation_values(svdw_ctx* c, uint32_t k, int form, const uint64_t* m
         pp_delta_powers(fr_from_u64(1), form, total_cols, (Fr*)c->pp_up.data());
         memcpy(c->pp_up.data() + nd * sizeof(Fr), w.data(), w.size() * sizeof(Fr));
         ensure_buf(c, c->lkp, 128 + bytes);
-        unsigned long long* cnt = (unsigned long long*)c->lkp.p;
+        unsigned long long* cnt = zero_counters(c);
         const Fr* dl = (const Fr*)((char*)c->lkp.p + 128);
-        hipck(hipMemsetAsync(cnt, 0, 128, c->st), "hipMemsetAsync");
         hipck(hipMemcpyAsync((void*)dl, c->pp_up.data(), bytes, hipMemcpyHostToDevice, c->st), "H2D");
-        {
-            ProfScope ps(c, c->st, "k_pp_values", (mapping ? 40.0 : 32.0) * ncols * (double)(1ull << k), 0);
-            hipck(launch_pp_values(mapping, dl, dl + nd, dl + nd + ((size_t)1 << h), h, first_col, ncols, total_cols,
-                                   1ull << k, (Fr*)out, cnt, c->st), "k_pp_values");
-        }
+        profiled(c, "k_pp_values", (mapping ? 40.0 : 32.0) * ncols * (double)(1ull << k), [&] {
+            return launch_pp_values(mapping, dl, dl + nd, dl + nd + ((size_t)1 << h), h, first_col, ncols, total_cols,
+                                    1ull << k, (Fr*)out, cnt, c->st);
+        });
         unsigned long long bad = 0;
-        hipck(hipMemcpyAsync(&bad, cnt, sizeof bad, hipMemcpyDeviceToHost, c->st), "D2H");
-        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+        read_counters(c, cnt, &bad, 1);
         *out_of_range = bad;
     });
 }
@@ -5264,12 +5272,10 @@ static bool pp_args(svdw_ctx* c, const char* fn, uint32_t k, uint32_t unusable_r
                     const void* const* columns, const void* const* sigma, uint32_t ncols, uint32_t chunk_len,
                     const uint64_t beta[4], const uint64_t gamma[4], const void* z, bool scratch, PpDev* d) {
     const std::string f(fn);
-    REQUIRE(c && beta && gamma, "null argument");
-    check_form(form);
-    const Fr b = fr_raw_words(beta), g = fr_raw_words(gamma);
-    REQUIRE(fr_reduced(b) && fr_reduced(g), f + ": beta or gamma >= p");
+    REQUIRE(c, "null argument");
+    Fr b, g;
+    gp_challenges(fn, form, beta, gamma, unusable_rows, &b, &g);
     const uint64_t rows = k < 63 ? 1ull << k : ~0ull;
-    if (!unusable_rows) fail(SVDW_ERANGE, f + ": unusable_rows == 0 leaves no row for Z[usable]");
     if (unusable_rows >= rows) fail(SVDW_ERANGE, f + ": unusable_rows leaves no usable row");
     REQUIRE(chunk_len, f + ": chunk_len == 0");
     if (k < 1 || k > 28) fail(SVDW_ERANGE, f + ": k must be in [1, 28]");
@@ -5301,7 +5307,7 @@ static bool pp_args(svdw_ctx* c, const char* fn, uint32_t k, uint32_t unusable_r
     const uint64_t cells = scratch ? pp_scratch_cells(a.nsets, rows) : 0;
     ensure_buf(c, c->lkp, 128 + up + cells * sizeof(Fr));
     char* base = (char*)c->lkp.p;
-    d->cnt = (unsigned long long*)base;
+    d->cnt = zero_counters(c);
     a.cols = (const Fr* const*)(base + 128);
     a.sig = a.cols + ncols;
     a.bd = (const Fr*)(base + 128 + pbytes);
@@ -5309,8 +5315,7 @@ static bool pp_args(svdw_ctx* c, const char* fn, uint32_t k, uint32_t unusable_r
     a.whi = a.wlo + ((size_t)1 << a.h);
     d->sv = (Fr*)(base + 128 + up);
     d->xs = d->sv + 2 * (uint64_t)a.nsets;
-    d->tp = d->xs + 2 * (uint64_t)kPpCarryThreads * a.nsets;
-    hipck(hipMemsetAsync(d->cnt, 0, 128, c->st), "hipMemsetAsync");
+    d->tp = d->xs + 2 * (uint64_t)kGpThreads * a.nsets;
     hipck(hipMemcpyAsync(base + 128, c->pp_up.data(), up, hipMemcpyHostToDevice, c->st), "H2D");
     return true;
 }
@@ -5326,30 +5331,17 @@ int svdw_permutation_product(svdw_ctx* c, uint32_t k, uint32_t unusable_rows, in
         result->usable_rows = d.a.usable;
         if (!any) return;
         const PpArgs& a = d.a;
-        const double cells = (double)ncols * a.usable, nt = (double)lp_tiles(a.rows);
-        {
-            ProfScope ps(c, c->st, "k_pp_tiles", 64.0 * cells, 0);
-            hipck(launch_pp_tiles(a, form, d.tp, d.cnt, c->st), "k_pp_tiles");
-        }
-        {
-            ProfScope ps(c, c->st, "k_pp_totals", 64.0 * a.nsets * nt, 0);
-            hipck(launch_pp_totals(a, form, d.tp, d.xs, d.sv, c->st), "k_pp_totals");
-        }
-        {
-            ProfScope ps(c, c->st, "k_pp_chain", 128.0 * a.nsets, 0);
-            hipck(launch_pp_chain(a, d.sv, d.cnt, c->st), "k_pp_chain");
-        }
-        {
-            ProfScope ps(c, c->st, "k_pp_fold", 128.0 * a.nsets * nt, 0);
-            hipck(launch_pp_fold(a, form, d.tp, d.xs, d.sv, c->st), "k_pp_fold");
-        }
-        {
-            ProfScope ps(c, c->st, "k_pp_write", 64.0 * cells + 32.0 * a.nsets * a.rows, 0);
-            hipck(launch_pp_write(a, form, d.tp, (Fr*)z, c->st), "k_pp_write");
-        }
+        const double cells = (double)ncols * a.usable, nt = (double)gp_tiles(a.rows);
+        profiled(c, "k_pp_tiles", 64.0 * cells, [&] { return launch_pp_tiles(a, form, d.tp, d.cnt, c->st); });
+        profiled(c, "k_pp_totals", 64.0 * a.nsets * nt,
+                 [&] { return launch_pp_totals(a, form, d.tp, d.xs, d.sv, c->st); });
+        profiled(c, "k_pp_chain", 128.0 * a.nsets, [&] { return launch_pp_chain(a, d.sv, d.cnt, c->st); });
+        profiled(c, "k_pp_fold", 128.0 * a.nsets * nt,
+                 [&] { return launch_pp_fold(a, form, d.tp, d.xs, d.sv, c->st); });
+        profiled(c, "k_pp_write", 64.0 * cells + 32.0 * a.nsets * a.rows,
+                 [&] { return launch_pp_write(a, form, d.tp, (Fr*)z, c->st); });
         unsigned long long h[2];
-        hipck(hipMemcpyAsync(h, d.cnt, sizeof h, hipMemcpyDeviceToHost, c->st), "D2H");
-        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+        read_counters(c, d.cnt, h, 2);
         result->columns = ncols;
         result->sets = a.nsets;
         result->zero_denominators = h[0];
@@ -5369,19 +5361,9 @@ int svdw_check_permutation_product(svdw_ctx* c, uint32_t k, uint32_t unusable_ro
         if (!any) return;
         const PpArgs& a = d.a;
         const Fr wstep = fr_to_mont(fr_pow_u64(fr_from_mont(pp_omega_mont(k)), pp_check_stride(a.rows)));
-        {
-            ProfScope ps(c, c->st, "k_pp_check", 64.0 * ncols * a.usable + 32.0 * a.nsets * a.rows, 0);
-            hipck(launch_pp_check(a, form, (const Fr*)z, wstep, d.cnt, c->st), "k_pp_check");
-        }
-        unsigned long long h[6];
-        hipck(hipMemcpyAsync(h, d.cnt, sizeof h, hipMemcpyDeviceToHost, c->st), "D2H");
-        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
-        result->recurrence_checked = h[0];
-        result->recurrence_failures = h[1];
-        result->boundary_checked = h[2];
-        result->boundary_failures = h[3];
-        result->padding_checked = h[4];
-        result->padding_failures = h[5];
+        profiled(c, "k_pp_check", 64.0 * ncols * a.usable + 32.0 * a.nsets * a.rows,
+                 [&] { return launch_pp_check(a, form, (const Fr*)z, wstep, d.cnt, c->st); });
+        gp_check_result(c, d.cnt, result);
     });
 }
 int svdw_rlc_trace(const svdw_ctx* c, uint64_t* cells, uint64_t* copies, uint32_t* n) {

@@ -7,15 +7,12 @@
 //
 //   Z[i] = prod_{r < i} N[r] * prod_{r >= i} D[r] * (prod_r D[r])^-1,
 //
-// a prefix product, a suffix product and one inversion per column:
+// a prefix product, a suffix product and one inversion per column: the passes
+// of grand_product.hpp (profiled as k_lp_tiles, k_lp_write, k_lp_check) over
+// this argument's leaf, with one carry kernel between tiles and write:
 //
-//  k_lp_tiles   the products of N and of D over each tile of kLpTile rows
 //  k_lp_carry   one block per column: exclusive prefix (N) and suffix (D) of
 //               the tile products, the inverse, Z[usable] against 1
-//  k_lp_write   the tile again: local prefix / suffix products, a block scan,
-//               Z written in `form`
-//  k_lp_check   the division-free recurrence, the boundary rows and the padding
-//               (shares no scan and no inversion with the three above)
 //
 // Factors are multiplied with mont_mul in whatever power of 2^256 the form
 // hands them over in (canonical cells: 2^-256 per factor pair, Montgomery
@@ -28,12 +25,10 @@
 #include <stdint.h>
 
 #include "fr.hpp"
+#include "grand_product.hpp"
 #include "lookup.hpp"
 
 namespace svdw {
-
-static constexpr uint32_t kLpTile = 1024;   // rows per tile
-inline uint64_t lp_tiles(uint64_t rows) { return (rows + kLpTile - 1) / kLpTile; }
 
 // The challenges as the kernels add them: to the canonical input column (b0,
 // g0), to the permuted columns in their form (bx, gx), to T 2^512 (g2 = gamma
@@ -42,23 +37,26 @@ inline uint64_t lp_tiles(uint64_t rows) { return (rows + kLpTile - 1) / kLpTile;
 struct LpChal {
     Fr b0, g0, bx, gx, g2, t2, one;
 };
+// What the row kernels read: the input columns (src), the permuted columns A',
+// S' (pin, ptab: ncols x rows cells in `form`, device memory), the challenges.
+struct LpArgs {
+    LkSrc src;
+    const Fr *pin, *ptab;
+    LpChal ch;
+    uint32_t ncols, lb;
+    uint64_t rows, usable;
+};
 
 // tp[(c * ntiles + t) * 2 + {0, 1}] = the products of N, of D over tile t of
 // column c; cnt[0] += rows with a zero denominator.
-hipError_t launch_lp_tiles(const LkSrc& src, const Fr* pin, const Fr* ptab, const LpChal& ch, int form,
-                           uint32_t ncols, uint64_t rows, uint64_t usable, uint32_t lb, Fr* tp,
-                           unsigned long long* cnt, hipStream_t st);
+hipError_t launch_lp_tiles(const LpArgs& a, int form, Fr* tp, unsigned long long* cnt, hipStream_t st);
 // tp in place: the carries k_lp_write multiplies in; cnt[1] += columns with Z[usable] != 1.
-hipError_t launch_lp_carry(Fr* tp, const LpChal& ch, int form, uint32_t ncols, uint64_t rows, unsigned long long* cnt,
-                           hipStream_t st);
+hipError_t launch_lp_carry(const LpArgs& a, int form, Fr* tp, unsigned long long* cnt, hipStream_t st);
 // z (ncols x rows cells in `form`): rows [0, usable] the product, rows above zero.
-hipError_t launch_lp_write(const LkSrc& src, const Fr* pin, const Fr* ptab, const LpChal& ch, int form,
-                           uint32_t ncols, uint64_t rows, uint64_t usable, uint32_t lb, const Fr* tp, Fr* z,
-                           hipStream_t st);
+hipError_t launch_lp_write(const LpArgs& a, int form, const Fr* tp, Fr* z, hipStream_t st);
 // cnt[0..1] += recurrence rows checked / failed, cnt[2..3] += boundary rows,
 // cnt[4..5] += padding cells.
-hipError_t launch_lp_check(const LkSrc& src, const Fr* pin, const Fr* ptab, const Fr* z, const LpChal& ch, int form,
-                           uint32_t ncols, uint64_t rows, uint64_t usable, uint32_t lb, unsigned long long* cnt,
-                           hipStream_t st);
+hipError_t launch_lp_check(const LpArgs& a, int form, const Fr* z, unsigned long long* cnt, hipStream_t st);
 
 }  // namespace svdw
+

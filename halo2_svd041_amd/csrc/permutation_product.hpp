@@ -12,18 +12,16 @@
 //   start_0 = 1,  start_{s+1} = start_s * prod_r N_s[r] * (prod_r D_s[r])^-1 = Z_s[usable]
 //
 // a prefix product, a suffix product and one inversion per set, the sets of one
-// call in the same launches (a set per blockIdx.y):
+// call in the same launches (a set per blockIdx.y): the passes of
+// grand_product.hpp (profiled as k_pp_tiles, k_pp_write, k_pp_check) over this
+// argument's leaf, with a carry stage of three kernels between tiles and write,
+// as only it sees the chain, and
 //
-//  k_pp_tiles   the products of N_s and of D_s over each tile of kLpTile rows
 //  k_pp_totals  one block per set: exclusive prefix (N) and suffix (D) of the
 //               tile products per thread, the set's totals, the inverse
 //  k_pp_chain   one thread: the nsets starts, each folded into its set's
 //               inverse; the last Z[usable] against 1
 //  k_pp_fold    one block per set: the tile carries k_pp_write multiplies in
-//  k_pp_write   the tile again: local prefix / suffix products, a block scan,
-//               Z written in `form`
-//  k_pp_check   the division-free recurrence, the chain and boundary rows, the
-//               padding (shares no scan and no inversion with those above)
 //  k_pp_values  sigma cells delta^col omega^row from a (col, row) mapping
 //
 // Powers of 2^256 (R), phi = 1 for canonical and R for Montgomery cells: a cell
@@ -46,11 +44,9 @@
 #include <stdint.h>
 
 #include "fr.hpp"
-#include "lookup_product.hpp"
+#include "grand_product.hpp"
 
 namespace svdw {
-
-static constexpr unsigned kPpCarryThreads = 256;             // the threads of k_pp_totals / k_pp_fold (kLpThreads)
 
 // What the row kernels read, all in device memory. cols / sig: ncols column
 // base pointers each; bd[j] = beta delta^j phi; wlo[i] = omega^i R for
@@ -67,9 +63,9 @@ struct PpArgs {
     Fr bR, g, one;
 };
 inline uint32_t pp_sets(uint32_t ncols, uint32_t chunk) { return (ncols + chunk - 1) / chunk; }
-// Cells of scratch behind tp: per set kPpCarryThreads x 2 thread carries, 2 set values.
+// Cells of scratch behind tp: per set kGpThreads x 2 thread carries, 2 set values.
 inline uint64_t pp_scratch_cells(uint32_t nsets, uint64_t rows) {
-    return (uint64_t)nsets * (2 * lp_tiles(rows) + 2 * kPpCarryThreads + 2);
+    return (uint64_t)nsets * (2 * gp_tiles(rows) + 2 * kGpThreads + 2);
 }
 
 // tp[(s * ntiles + t) * 2 + {0, 1}] = the products of N_s, of D_s over tile t;
