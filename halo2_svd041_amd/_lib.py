@@ -108,6 +108,15 @@ class PermutationProductCheck(ct.Structure):
                 ("padding_checked", ct.c_uint64), ("padding_failures", ct.c_uint64)]
 
 
+class NttResult(ct.Structure):
+    _fields_ = [("columns", ct.c_uint32), ("passes", ct.c_uint32), ("rows_in", ct.c_uint64),
+                ("rows_out", ct.c_uint64)]
+
+
+class NttCheck(ct.Structure):
+    _fields_ = [("rows_checked", ct.c_uint64), ("row_failures", ct.c_uint64)]
+
+
 class PhysParams(ct.Structure):
     _fields_ = [("k", ct.c_uint32), ("minimum_rows", ct.c_uint32), ("max_rows", ct.c_uint64),
                 ("num_advice", ct.c_uint32 * 2), ("columns_used", ct.c_uint32 * 2),
@@ -246,6 +255,10 @@ SIGNATURES = {
                                         ct.POINTER(PermutationProductResult)]),
     "svdw_check_permutation_product": (_i32, [_P, _u32, _u32, _i32, _P, _P, _u32, _u32, _P, _P, _P,
                                               ct.POINTER(PermutationProductCheck)]),
+    "svdw_ntt_passes": (_u32, [_u32]),
+    "svdw_ntt": (_i32, [_P, _u32, _u32, _i32, _i32, _P, _P, _u32, _P, ct.POINTER(NttResult)]),
+    "svdw_eval_polynomial": (_i32, [_P, _u32, _i32, _P, _u32, _P, _u32, _P]),
+    "svdw_check_ntt": (_i32, [_P, _u32, _u32, _i32, _i32, _P, _P, _u32, _P, _u32, _u64, ct.POINTER(NttCheck)]),
 }
 
 _lib = None

@@ -32,6 +32,7 @@
 #include "export.hpp"
 #include "lookup.hpp"
 #include "lookup_product.hpp"
+#include "ntt.hpp"
 #include "permutation_product.hpp"
 
 using namespace svdw;
@@ -677,6 +678,8 @@ struct svdw_ctx {
     std::vector<Fr> pp_w;                   // permutation argument: the omega tables of pp_k (permutation_product.hpp)
     uint32_t pp_k = 0;
     std::vector<char> pp_up;                // its staged upload: pointer, delta and omega tables
+    DBuf ntt_tab, ntt_tmp;                  // transforms (ntt.hpp): the stage and omega tables of ntt_k; the buffer
+    uint32_t ntt_k = 0;                     // between passes
     hipEvent_t exp_ev[6] = {};
     // ---- captured verify_mul_witness ("graph", vm_graph): the launch sequence of
     // a device-input call is captured once into a HIP graph (the second call of
@@ -3280,7 +3283,8 @@ static std::vector<DBuf*> dbufs(svdw_ctx* c) {
                             &c->gtab_alt, &c->crtR, &c->gbits, &c->colpart, &c->qfold, &c->ing_x, &c->ing_e,
                             &c->ing_c, &c->ing_p10, &c->ing_val, &c->ing_npos, &c->ing_nd, &c->ing_rpos,
                             &c->ing_kpos, &c->ing_err, &c->ing_q, &c->eq_cp, &c->eq_ks, &c->eq_reg, &c->eq_w,
-                            &c->eq_k, &c->eq_err, &c->eq_st, &c->exp_buf[0], &c->exp_buf[1], &c->lkp};
+                            &c->eq_k, &c->eq_err, &c->eq_st, &c->exp_buf[0], &c->exp_buf[1], &c->lkp, &c->ntt_tab,
+                            &c->ntt_tmp};
     for (int i = 0; i < kMaxScanJobs; ++i) {
         v.push_back(&c->wbc[i]);
         v.push_back(&c->wbt[i]);
@@ -5364,6 +5368,246 @@ int svdw_check_permutation_product(svdw_ctx* c, uint32_t k, uint32_t unusable_ro
         profiled(c, "k_pp_check", 64.0 * ncols * a.usable + 32.0 * a.nsets * a.rows,
                  [&] { return launch_pp_check(a, form, (const Fr*)z, wstep, d.cnt, c->st); });
         gp_check_result(c, d.cnt, result);
+    });
+}
+// ---- transforms between Lagrange, coefficient and extended form, evaluation at
+// points and the transform's check (ntt.hpp)
+namespace {
+struct NttCall {
+    uint32_t k_in = 0, k = 0, ncols = 0;
+    int form = 0, inverse = 0;
+    bool shifted = false;
+    Fr shift;                                              // canonical
+};
+struct NttDev {                                            // what a call staged behind the counters of c->lkp
+    const Fr* const* cols = nullptr;
+    const Fr* cells = nullptr;                             // the Fr cells staged after the pointers
+    char* free = nullptr;                                  // scratch from here on
+};
+}  // namespace
+// The argument checks of svdw_ntt and svdw_check_ntt (log_samples: the latter's,
+// else 0), in the order include/svdw.h gives; false: no columns, nothing to do.
+static bool ntt_args(svdw_ctx* c, const char* fn, uint32_t k_in, uint32_t k, int form, int inverse,
+                     const uint64_t shift[4], const void* const* in, uint32_t ncols, const void* out,
+                     uint32_t log_samples, NttCall* a) {
+    const std::string f(fn);
+    REQUIRE(c, "null argument");
+    check_form(form);
+    a->shift = fr_from_u64(1);
+    if (shift) {
+        a->shift = fr_raw_words(shift);
+        REQUIRE(fr_reduced(a->shift) && !fr_is_zero(a->shift), f + ": shift >= p or shift == 0");
+    }
+    a->shifted = !fr_eq(a->shift, fr_from_u64(1));
+    REQUIRE(inverse == 0 || inverse == 1, f + ": inverse must be 0 or 1");
+    if (k < 1 || k > 28) fail(SVDW_ERANGE, f + ": k must be in [1, 28]");
+    if (k_in < 1 || k_in > k) fail(SVDW_ERANGE, f + ": k_in must be in [1, k]");
+    if (inverse && k_in != k) fail(SVDW_ERANGE, f + ": an inverse transform needs k_in == k");
+    if (log_samples > k) fail(SVDW_ERANGE, f + ": log_samples must be in [0, k]");
+    REQUIRE(!c->dry, f + " needs a device context");
+    a->k_in = k_in;
+    a->k = k;
+    a->ncols = ncols;
+    a->form = form;
+    a->inverse = inverse;
+    if (!ncols) return false;
+    if (ncols > 65535) fail(SVDW_ERANGE, f + ": more than 65535 columns");
+    REQUIRE(in && out, "null argument");
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (((uintptr_t)ncols << k) * sizeof(Fr));
+    for (uint32_t j = 0; j < ncols; ++j) {
+        REQUIRE(in[j], f + ": null column pointer");
+        const uintptr_t i0 = (uintptr_t)in[j], i1 = i0 + (((uintptr_t)1 << k_in) * sizeof(Fr));
+        REQUIRE(i1 <= o0 || o1 <= i0, f + ": out overlaps an input column");
+    }
+    return true;
+}
+// The device tables of k, made once per k: omega_1024^j R and omega_1024^-j R
+// for j < 512, then the two-level omega_k tables of pp_tables.
+static const Fr* ntt_tables(svdw_ctx* c, uint32_t k) {
+    const std::vector<Fr>& w = pp_tables(c, k);
+    const size_t cells = 1024 + w.size();
+    const bool grown = c->ntt_tab.cap < cells * sizeof(Fr);
+    ensure_buf(c, c->ntt_tab, cells * sizeof(Fr));
+    if (grown || c->ntt_k != k) {
+        std::vector<Fr> t(cells);
+        const Fr w10 = pp_omega_mont(10);
+        t[0] = t[512] = fr_to_mont(fr_from_u64(1));
+        for (size_t j = 1; j < 512; ++j) t[j] = mont_mul(t[j - 1], w10);
+        for (size_t j = 1; j < 512; ++j) t[512 + j] = fr_neg(t[512 - j]);   // omega^-j = -omega^(512 - j)
+        memcpy(t.data() + 1024, w.data(), w.size() * sizeof(Fr));
+        hipck(hipMemcpyAsync(c->ntt_tab.p, t.data(), cells * sizeof(Fr), hipMemcpyHostToDevice, c->st), "H2D");
+        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+        c->ntt_k = k;
+    }
+    return (const Fr*)c->ntt_tab.p;
+}
+// base^i R for i < 2^fh, then top base^(i 2^fh) R for i < 2^(kk - fh): the
+// two-level table of a call's shift, top = the scale times R.
+static void ntt_factor_tables(const Fr& base, const Fr& top, uint32_t kk, Fr* out) {
+    const uint32_t fh = pp_split(kk);
+    const size_t nlo = (size_t)1 << fh, nhi = (size_t)1 << (kk - fh);
+    const Fr b = fr_to_mont(base);
+    out[0] = fr_to_mont(fr_from_u64(1));
+    for (size_t i = 1; i < nlo; ++i) out[i] = mont_mul(out[i - 1], b);
+    const Fr bh = mont_mul(out[nlo - 1], b);
+    out[nlo] = top;
+    for (size_t i = 1; i < nhi; ++i) out[nlo + i] = mont_mul(out[nlo + i - 1], bh);
+}
+// Stage the ncols column pointers and `cells` Fr cells (filled by `fill`) behind
+// the zeroed counters of c->lkp, with `scratch` bytes after them.
+extern "C++" template <class Fill>
+static NttDev ntt_stage(svdw_ctx* c, const void* const* ptrs, uint32_t ncols, size_t cells, size_t scratch,
+                        Fill&& fill) {
+    const size_t pbytes = ((size_t)ncols * sizeof(void*) + 31) / 32 * 32, up = pbytes + cells * sizeof(Fr);
+    c->pp_up.assign(up, 0);
+    if (ncols) memcpy(c->pp_up.data(), ptrs, ncols * sizeof(void*));
+    fill((Fr*)(c->pp_up.data() + pbytes));
+    ensure_buf(c, c->lkp, 128 + up + scratch);
+    char* base = (char*)c->lkp.p;
+    (void)zero_counters(c);
+    hipck(hipMemcpyAsync(base + 128, c->pp_up.data(), up, hipMemcpyHostToDevice, c->st), "H2D");
+    return NttDev{(const Fr* const*)(base + 128), (const Fr*)(base + 128 + pbytes), base + 128 + up};
+}
+uint32_t svdw_ntt_passes(uint32_t k) { return ntt_passes(k); }
+int svdw_ntt(svdw_ctx* c, uint32_t k_in, uint32_t k, int form, int inverse, const uint64_t shift[4],
+             const void* const* in, uint32_t ncols, void* out, svdw_ntt_result* result) {
+    return guarded([&] {
+        REQUIRE(result, "null argument");
+        NttCall a;
+        const bool any = ntt_args(c, "svdw_ntt", k_in, k, form, inverse, shift, in, ncols, out, 0, &a);
+        memset(result, 0, sizeof *result);
+        result->passes = ntt_passes(k);
+        result->rows_in = 1ull << k_in;
+        result->rows_out = 1ull << k;
+        if (!any) return;
+        sync(c);
+        const uint32_t P = ntt_passes(k), h = pp_split(k), kk = inverse ? k : k_in, fh = pp_split(kk);
+        const uint64_t N = 1ull << k;
+        const Fr* tab = ntt_tables(c, k);
+        const Fr scale = inverse ? fr_to_mont(fr_inv(fr_from_u64(N))) : fr_to_mont(fr_from_u64(1));   // 2^-k R
+        const size_t fcells = a.shifted ? ((size_t)1 << fh) + ((size_t)1 << (kk - fh)) : 0;
+        if (P > 1) ensure_buf(c, c->ntt_tmp, (size_t)ncols * N * sizeof(Fr));
+        const NttDev d = ntt_stage(c, in, ncols, fcells, 0, [&](Fr* t) {
+            if (a.shifted) ntt_factor_tables(a.shift, scale, kk, t);
+        });
+        Fr* tmp = (Fr*)c->ntt_tmp.p;
+        uint32_t ls = 0;
+        for (uint32_t i = 0; i < P; ++i) {
+            NttPass p{};
+            p.cols = i ? nullptr : d.cols;
+            // the buffers alternate so that the last pass writes out
+            p.src = i ? ((P - i) % 2 ? tmp : (const Fr*)out) : nullptr;
+            p.dst = (P - 1 - i) % 2 ? tmp : (Fr*)out;
+            p.tw = tab + (inverse ? 512 : 0);
+            p.wlo = tab + 1024;
+            p.whi = p.wlo + ((size_t)1 << h);
+            p.flo = a.shifted ? d.cells : nullptr;
+            p.fhi = a.shifted ? d.cells + ((size_t)1 << fh) : nullptr;
+            p.fc = scale;
+            p.k = k;
+            p.kin = i ? k : k_in;
+            p.b = ntt_pass_bits(k, i);
+            p.ls = ls;
+            p.h = h;
+            p.fh = fh;
+            p.ncols = ncols;
+            p.inverse = (uint32_t)inverse;
+            p.last = i + 1 == P;
+            p.pre = !inverse && a.shifted && i == 0;
+            p.post = inverse && p.last ? (a.shifted ? 2u : 1u) : 0u;
+            ls += p.b;
+            const char* label = i == 0 ? "k_ntt_pass1" : i == 1 ? "k_ntt_pass2" : "k_ntt_pass3";
+            profiled(c, label, 32.0 * ncols * ((double)(1ull << p.kin) + (double)N),
+                     [&] { return launch_ntt_pass(p, c->st); });
+        }
+        result->columns = ncols;
+    });
+}
+// The evaluations of ncols polynomials of n coefficients (cols or src, as the
+// kernels take them) at the npoints points dpts (device, x R), in chunks of at
+// most `chunk` points through part; then(q0, nq) after each chunk's sums.
+extern "C++" template <class Then>
+static void ntt_eval_chunks(svdw_ctx* c, const Fr* const* cols, const Fr* src, uint64_t n, uint32_t ncols,
+                            const Fr* dpts, uint64_t npoints, uint32_t chunk, Fr* part, uint64_t out_stride, Fr* out,
+                            bool advance_out, Then&& then) {
+    const uint32_t nb = ntt_eval_blocks(n);
+    for (uint64_t q0 = 0; q0 < npoints; q0 += chunk) {
+        const uint32_t nq = (uint32_t)std::min<uint64_t>(chunk, npoints - q0);
+        profiled(c, "k_ntt_eval", 32.0 * ncols * (double)n * nq,
+                 [&] { return launch_ntt_eval(cols, src, n, ncols, dpts + q0, nq, part, c->st); });
+        profiled(c, "k_ntt_eval_sum", 32.0 * ncols * (double)nq * (nb + 1), [&] {
+            return launch_ntt_eval_sum(part, nb, ncols, nq, out_stride, out + (advance_out ? q0 : 0), c->st);
+        });
+        then(q0, nq);
+    }
+}
+static constexpr uint32_t kNttPointChunk = 32768;          // points per launch of k_ntt_eval
+int svdw_eval_polynomial(svdw_ctx* c, uint32_t k, int form, const void* const* coeffs, uint32_t ncols,
+                         const uint64_t* points, uint32_t npoints, void* out) {
+    return guarded([&] {
+        const std::string f("svdw_eval_polynomial");
+        REQUIRE(c && (points || !npoints), "null argument");
+        check_form(form);
+        for (uint32_t q = 0; q < npoints; ++q)
+            REQUIRE(fr_reduced(fr_raw_words(points + 4 * (size_t)q)), f + ": point >= p");
+        if (k < 1 || k > 28) fail(SVDW_ERANGE, f + ": k must be in [1, 28]");
+        REQUIRE(!c->dry, f + " needs a device context");
+        if (!ncols || !npoints) return;
+        if (ncols > 65535) fail(SVDW_ERANGE, f + ": more than 65535 columns");
+        REQUIRE(coeffs && out, "null argument");
+        for (uint32_t j = 0; j < ncols; ++j) REQUIRE(coeffs[j], f + ": null column pointer");
+        sync(c);
+        const uint64_t n = 1ull << k;
+        const uint32_t chunk = std::min(npoints, kNttPointChunk);
+        const size_t part = (size_t)ncols * chunk * ntt_eval_blocks(n) * sizeof(Fr);
+        const NttDev d = ntt_stage(c, coeffs, ncols, npoints, part, [&](Fr* t) {
+            for (uint32_t q = 0; q < npoints; ++q) t[q] = fr_to_mont(fr_raw_words(points + 4 * (size_t)q));
+        });
+        ntt_eval_chunks(c, d.cols, nullptr, n, ncols, d.cells, npoints, chunk, (Fr*)d.free, npoints, (Fr*)out, true,
+                        [](uint64_t, uint32_t) {});
+    });
+}
+int svdw_check_ntt(svdw_ctx* c, uint32_t k_in, uint32_t k, int form, int inverse, const uint64_t shift[4],
+                   const void* const* in, uint32_t ncols, const void* out, uint32_t log_samples, uint64_t seed,
+                   svdw_ntt_check* result) {
+    return guarded([&] {
+        REQUIRE(result, "null argument");
+        NttCall a;
+        const bool any = ntt_args(c, "svdw_check_ntt", k_in, k, form, inverse, shift, in, ncols, out, log_samples, &a);
+        memset(result, 0, sizeof *result);
+        if (!any) return;
+        sync(c);
+        // the points: shift omega^j (forward), omega^j / shift (inverse), as x R
+        const std::vector<Fr>& w = pp_tables(c, k);
+        const uint32_t h = pp_split(k);
+        const uint64_t S = 1ull << log_samples, n = 1ull << (inverse ? k : k_in);
+        const Fr sR = fr_to_mont(inverse ? fr_inv(a.shift) : a.shift);
+        const uint32_t chunk = (uint32_t)std::min<uint64_t>(S, kNttPointChunk);
+        const size_t vals = (size_t)ncols * chunk * sizeof(Fr), part = vals * ntt_eval_blocks(n);
+        const NttDev d = ntt_stage(c, in, ncols, S, vals + part, [&](Fr* t) {
+            for (uint64_t s = 0; s < S; ++s) {
+                const uint64_t j = ntt_sample_row(k, log_samples, seed, s);
+                const Fr wj = mont_mul(w[((size_t)1 << h) + (j >> h)], w[j & (((size_t)1 << h) - 1)]);
+                t[s] = mont_mul(wj, sR);
+            }
+        });
+        unsigned long long* cnt = (unsigned long long*)c->lkp.p;
+        Fr* dv = (Fr*)d.free;
+        // forward: the input's polynomial against the cells of out; inverse: the other way round
+        const Fr* const* pcols = inverse ? nullptr : d.cols;
+        const Fr* psrc = inverse ? (const Fr*)out : nullptr;
+        ntt_eval_chunks(c, pcols, psrc, n, ncols, d.cells, S, chunk, dv + (size_t)ncols * chunk, chunk, dv, false,
+                        [&](uint64_t s0, uint32_t ns) {       // ns == chunk: both are powers of two
+                            profiled(c, "k_ntt_compare", 64.0 * ncols * ns, [&] {
+                                return launch_ntt_compare(inverse ? d.cols : nullptr,
+                                                          inverse ? nullptr : (const Fr*)out, k, log_samples, seed,
+                                                          s0, ns, ncols, dv, cnt, c->st);
+                            });
+                        });
+        unsigned long long hc[2];
+        read_counters(c, cnt, hc, 2);
+        result->rows_checked = hc[0];
+        result->row_failures = hc[1];
     });
 }
 int svdw_rlc_trace(const svdw_ctx* c, uint64_t* cells, uint64_t* copies, uint32_t* n) {

@@ -20,7 +20,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import (CheckResult, EqCheck, LookupCheck, LookupProductCheck, LookupProductResult, LookupResult, PermutationProductCheck, PermutationProductResult, PhysParams, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SvdwError,
+from ._lib import (CheckResult, EqCheck, LookupCheck, LookupProductCheck, LookupProductResult, LookupResult, NttCheck, NttResult, PermutationProductCheck, PermutationProductResult, PhysParams, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SvdwError,
                    Vec, check, lib)
 
 P_MOD = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -704,6 +704,98 @@ class Context:
         check(lib().svdw_check_permutation_product(self._h, k, unusable_rows, _form(form), cp, sp, n, chunk_len,
                                                    b, g, z.data_ptr() if nsets else None, ct.byref(r)))
         return {k_: getattr(r, k_) for k_, _ in PermutationProductCheck._fields_}
+
+    # ---- domain transforms (include/svdw.h, "domain transforms"; parity unpinned)
+    @staticmethod
+    def _shift_arg(shift):
+        """None, or a shift in [1, p) as the 4-word argument."""
+        if shift is None:
+            return None
+        if int(shift) == 0:
+            raise SvdwError(-1, "shift must be in [1, p)")
+        return _challenge_arg(shift)
+
+    def _ntt_args(self, columns, k: int, k_in):
+        k_in = k if k_in is None else k_in
+        rows_in = 1 << k_in if 0 <= k_in < 32 else 0
+        rows = 1 << k if 0 <= k < 32 else 0
+        cp, n, dev = self._column_pointers("columns", columns, rows_in)
+        return k_in, rows, cp, n, dev
+
+    def ntt(self, columns, k: int, k_in: Optional[int] = None, inverse: bool = False, shift: Optional[int] = None,
+            form: str = "canonical", out=None):
+        """(out, result): the transform of include/svdw.h's "domain transforms"
+        (svdw_ntt) of columns of 2^k_in cells (k_in defaults to k) into a
+        [n, 2^k, 32] u8 device tensor in `form`, natural order on both sides.
+        Forward: out[j] = sum_i in[i] shift^i omega_k^(i j), the input zero from
+        row 2^k_in on; inverse: out[i] = shift^i 2^-k sum_j in[j] omega_k^(-i j).
+        columns: a tensor [n, 2^k_in, 32] u8 in `form` or a list of such tensors.
+        result: columns, passes, rows_in, rows_out."""
+        import torch
+        sh = self._shift_arg(shift)
+        k_in, rows, cp, n, dev = self._ntt_args(columns, k, k_in)
+        if out is None:
+            out = torch.empty((n, rows, 32), dtype=torch.uint8, device=dev or torch.device("cuda", self.device))
+        if (not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous()
+                or tuple(out.shape) != (n, rows, 32)):
+            raise SvdwError(-1, "out must be a contiguous uint8 device tensor [n, 2^k, 32]")
+        r = NttResult()
+        _after_torch(self)
+        check(lib().svdw_ntt(self._h, k_in, k, _form(form), 1 if inverse else 0, sh, cp, n,
+                             out.data_ptr() if n else None, ct.byref(r)))
+        _before_torch(self)
+        return out, {k_: getattr(r, k_) for k_, _ in NttResult._fields_}
+
+    def lagrange_to_coeff(self, columns, k: int, form: str = "canonical", out=None):
+        """EvaluationDomain::lagrange_to_coeff of every column."""
+        return self.ntt(columns, k, inverse=True, form=form, out=out)
+
+    def coeff_to_lagrange(self, columns, k: int, form: str = "canonical", out=None):
+        """EvaluationDomain::coeff_to_lagrange of every column."""
+        return self.ntt(columns, k, form=form, out=out)
+
+    def coeff_to_extended(self, columns, k: int, extended_k: int, zeta: int, form: str = "canonical", out=None):
+        """EvaluationDomain::coeff_to_extended: 2^k coefficients to 2^extended_k
+        evaluations on the coset zeta * <omega_extended_k>; zeta = Fr::ZETA."""
+        return self.ntt(columns, extended_k, k_in=k, shift=zeta, form=form, out=out)
+
+    def extended_to_coeff(self, columns, extended_k: int, zeta_inv: int, form: str = "canonical", out=None):
+        """EvaluationDomain::extended_to_coeff: 2^extended_k coset evaluations to
+        coefficients (the caller keeps the prefix it needs); zeta_inv = ZETA^2."""
+        return self.ntt(columns, extended_k, inverse=True, shift=zeta_inv, form=form, out=out)
+
+    def eval_polynomial(self, columns, k: int, points, form: str = "canonical"):
+        """[ncols, npoints, 32] u8 device cells in `form`: the polynomials whose
+        2^k coefficients the columns hold, at the points (ints in [0, p)), as
+        halo2's eval_polynomial (svdw_eval_polynomial)."""
+        import torch
+        rows = 1 << k if 0 <= k < 32 else 0
+        pts = [_challenge_arg(x) for x in points]
+        cp, n, dev = self._column_pointers("columns", columns, rows)
+        buf = (ct.c_uint64 * max(4 * len(pts), 1))(*[w for p in pts for w in p])
+        out = torch.empty((n, len(pts), 32), dtype=torch.uint8, device=dev or torch.device("cuda", self.device))
+        _after_torch(self)
+        check(lib().svdw_eval_polynomial(self._h, k, _form(form), cp, n, buf, len(pts),
+                                         out.data_ptr() if n and pts else None))
+        _before_torch(self)
+        return out
+
+    def check_ntt(self, columns, out, k: int, k_in: Optional[int] = None, inverse: bool = False,
+                  shift: Optional[int] = None, form: str = "canonical", log_samples: int = 10, seed: int = 0) -> dict:
+        """Device check of a transform's `out` against its input columns on
+        2^log_samples stratified rows per column, by direct evaluation
+        (svdw_check_ntt): rows_checked, row_failures, summed over the columns."""
+        import torch
+        sh = self._shift_arg(shift)
+        k_in, rows, cp, n, _ = self._ntt_args(columns, k, k_in)
+        if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.uint8
+                or not out.is_contiguous() or tuple(out.shape) != (n, rows, 32)):
+            raise SvdwError(-1, "out must be a contiguous uint8 device tensor [n, 2^k, 32]")
+        r = NttCheck()
+        _after_torch(self)
+        check(lib().svdw_check_ntt(self._h, k_in, k, _form(form), 1 if inverse else 0, sh, cp, n,
+                                   out.data_ptr() if n else None, log_samples, seed & _M64, ct.byref(r)))
+        return {"rows_checked": r.rows_checked, "row_failures": r.row_failures}
 
     def profile(self, on: bool = True, prefix: str = "") -> None:
         """Record HIP events around kernel launches (names starting with `prefix`)."""

@@ -742,6 +742,79 @@ int svdw_check_permutation_product(svdw_ctx* ctx, uint32_t k, uint32_t unusable_
                                    const void* const* columns, const void* const* sigma, uint32_t ncols,
                                    uint32_t chunk_len, const uint64_t beta[4], const uint64_t gamma[4],
                                    const void* z, svdw_permutation_product_check* result);
+/* ------------------------------------------------------ domain transforms
+ * halo2_proofs' poly::EvaluationDomain conversions of columns of BN254 Fr cells
+ * on the device, eval_polynomial for a batch, and a check of a transform by
+ * direct evaluation. Restated from memory like the lookup and permutation
+ * steps: PARITY UNPINNED. These calls need no witness and no physical layout.
+ * omega = omega_k of svdw_permutation_constants; all arithmetic is exact mod p;
+ * cells are taken as field elements below p. Indices are in natural order on
+ * both sides: the caller never sees a bit reversal.
+ *
+ * One transform, svdw_ntt, of ncols columns of 2^k_in cells into ncols columns
+ * of 2^k cells, 1 <= k_in <= k <= 28, shift != 0 (NULL: 1):
+ *   forward (inverse == 0):  b[i] = in[i] shift^i for i < 2^k_in, 0 above;
+ *                            out[j] = sum_i b[i] omega^(i j)
+ *   inverse (inverse == 1, k_in == k):
+ *                            c[i] = 2^-k sum_j in[j] omega^(-i j);
+ *                            out[i] = c[i] shift^i
+ * EvaluationDomain's calls are
+ *   lagrange_to_coeff   inverse, shift NULL
+ *   coeff_to_lagrange   forward, shift NULL
+ *   coeff_to_extended   forward, k = extended_k, shift = Fr::ZETA
+ *                       (distribute_powers_zeta: g^i with g^3 = 1)
+ *   extended_to_coeff   inverse, k_in = k = extended_k, shift = ZETA^2 =
+ *                       ZETA^-1; the caller keeps the prefix it needs
+ * ZETA is the caller's input: the engine bakes in no cube root. The gates'
+ * expressions on the extended domain, the commitments and deriving the
+ * evaluation point stay with the caller. */
+typedef struct {
+    uint32_t columns, passes;     /* passes: svdw_ntt_passes(k) */
+    uint64_t rows_in, rows_out;   /* 2^k_in, 2^k */
+} svdw_ntt_result;
+/* Host only: the passes over global memory of a size-2^k transform (1 for
+ * k <= 10, 2 for k <= 20, 3 above). */
+uint32_t svdw_ntt_passes(uint32_t k);
+/* in: HOST array of ncols DEVICE pointers, each to 2^k_in cells in `form`. out:
+ * DEVICE array of ncols x 2^k cells, column-major, in `form`. shift: 4
+ * little-endian words, canonical. The checks of the arguments come first,
+ * before anything touches the device, in this order: an unknown form
+ * (SVDW_EINVAL), shift >= p or shift == 0 (SVDW_EINVAL), inverse not 0 or 1
+ * (SVDW_EINVAL), k outside 1..28 (SVDW_ERANGE), k_in outside 1..k or an inverse
+ * with k_in != k (SVDW_ERANGE), a planning context (SVDW_EINVAL), more than
+ * 65535 columns (SVDW_ERANGE), null pointers or an out that overlaps an input
+ * column (SVDW_EINVAL). ncols == 0: SVDW_OK, nothing is touched. The call is
+ * queued on the context's streams like svdw_permutation_product, with no host
+ * wait; scratch (a second buffer of ncols x 2^k cells for k > 10) is the
+ * engine's. */
+int svdw_ntt(svdw_ctx* ctx, uint32_t k_in, uint32_t k, int form, int inverse, const uint64_t shift[4],
+             const void* const* in, uint32_t ncols, void* out, svdw_ntt_result* result);
+/* eval_polynomial for a batch: out (DEVICE, ncols x npoints cells in `form`)
+ * cell c npoints + q = sum_i coeffs_c[i] x_q^i over the 2^k coefficients of
+ * column c (coeffs: HOST array of ncols DEVICE pointers, cells in `form`).
+ * points: HOST, npoints x 4 words, canonical; no relation between x_q and omega
+ * is needed. Checks in this order: form (SVDW_EINVAL), a point >= p
+ * (SVDW_EINVAL), k outside 1..28 (SVDW_ERANGE), a planning context
+ * (SVDW_EINVAL), more than 65535 columns (SVDW_ERANGE), null pointers
+ * (SVDW_EINVAL). ncols == 0 or npoints == 0: SVDW_OK, nothing is touched. */
+int svdw_eval_polynomial(svdw_ctx* ctx, uint32_t k, int form, const void* const* coeffs, uint32_t ncols,
+                         const uint64_t* points, uint32_t npoints, void* out);
+typedef struct {
+    uint64_t rows_checked, row_failures;   /* summed over the columns */
+} svdw_ntt_check;
+/* A transform's output against its input on S = 2^log_samples sampled rows per
+ * column, each re-derived by direct evaluation with the kernels of
+ * svdw_eval_polynomial; it shares no butterfly and no twiddle schedule with
+ * svdw_ntt.
+ *   forward:  out[j] == sum_i in[i] (shift omega^j)^i
+ *   inverse:  in[j] == sum_i out[i] (omega^j shift^-1)^i   (this pins 2^-k too)
+ * The rows are stratified: with q = 2^k / S, sample s < S is row
+ *   j_s = s q + ((seed + s 0x9E3779B1) mod q);
+ * log_samples == k checks every row. Arguments and their checks as for
+ * svdw_ntt, log_samples > k with rule 5 (SVDW_ERANGE). */
+int svdw_check_ntt(svdw_ctx* ctx, uint32_t k_in, uint32_t k, int form, int inverse, const uint64_t shift[4],
+                   const void* const* in, uint32_t ncols, const void* out, uint32_t log_samples, uint64_t seed,
+                   svdw_ntt_check* result);
 /* Up to cap segments of the last witness into out; *n = total count. */
 int svdw_shard_segments(const svdw_ctx* ctx, svdw_segment* out, uint64_t cap, uint64_t* n);
 
