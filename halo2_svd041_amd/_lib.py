@@ -117,6 +117,27 @@ class NttCheck(ct.Structure):
     _fields_ = [("rows_checked", ct.c_uint64), ("row_failures", ct.c_uint64)]
 
 
+class QuotientArgs(ct.Structure):
+    _fields_ = [("k", ct.c_uint32), ("extended_k", ct.c_uint32), ("unusable_rows", ct.c_uint32), ("form", ct.c_int),
+                ("shift", ct.c_uint64 * 4), ("beta", ct.c_uint64 * 4), ("gamma", ct.c_uint64 * 4),
+                ("y", ct.c_uint64 * 4), ("advice", ct.c_void_p), ("selectors", ct.c_void_p),
+                ("n_gate", ct.c_uint32), ("n_perm", ct.c_uint32), ("chunk_len", ct.c_uint32),
+                ("n_lookup", ct.c_uint32), ("perm_columns", ct.c_void_p), ("sigma", ct.c_void_p),
+                ("perm_z", ct.c_void_p), ("lookup_input", ct.c_void_p), ("lookup_table", ct.c_void_p),
+                ("permuted_input", ct.c_void_p), ("permuted_table", ct.c_void_p), ("lookup_z", ct.c_void_p)]
+
+
+class QuotientResult(ct.Structure):
+    _fields_ = [("gate_expressions", ct.c_uint64), ("permutation_expressions", ct.c_uint64),
+                ("lookup_expressions", ct.c_uint64), ("rows", ct.c_uint64), ("extension", ct.c_uint32),
+                ("degree", ct.c_uint32)]
+
+
+class QuotientCheck(ct.Structure):
+    _fields_ = [("lhs", ct.c_uint64 * 4), ("rhs", ct.c_uint64 * 4), ("identity_failures", ct.c_uint64),
+                ("tail_checked", ct.c_uint64), ("tail_nonzero", ct.c_uint64)]
+
+
 class PhysParams(ct.Structure):
     _fields_ = [("k", ct.c_uint32), ("minimum_rows", ct.c_uint32), ("max_rows", ct.c_uint64),
                 ("num_advice", ct.c_uint32 * 2), ("columns_used", ct.c_uint32 * 2),
@@ -259,6 +280,8 @@ SIGNATURES = {
     "svdw_ntt": (_i32, [_P, _u32, _u32, _i32, _i32, _P, _P, _u32, _P, ct.POINTER(NttResult)]),
     "svdw_eval_polynomial": (_i32, [_P, _u32, _i32, _P, _u32, _P, _u32, _P]),
     "svdw_check_ntt": (_i32, [_P, _u32, _u32, _i32, _i32, _P, _P, _u32, _P, _u32, _u64, ct.POINTER(NttCheck)]),
+    "svdw_quotient": (_i32, [_P, ct.POINTER(QuotientArgs), _P, ct.POINTER(QuotientResult)]),
+    "svdw_check_quotient": (_i32, [_P, ct.POINTER(QuotientArgs), _P, _P, ct.POINTER(QuotientCheck)]),
 }
 
 _lib = None

@@ -33,6 +33,7 @@
 #include "lookup.hpp"
 #include "lookup_product.hpp"
 #include "ntt.hpp"
+#include "quotient.hpp"
 #include "permutation_product.hpp"
 
 using namespace svdw;
@@ -680,6 +681,11 @@ struct svdw_ctx {
     std::vector<char> pp_up;                // its staged upload: pointer, delta and omega tables
     DBuf ntt_tab, ntt_tmp;                  // transforms (ntt.hpp): the stage and omega tables of ntt_k; the buffer
     uint32_t ntt_k = 0;                     // between passes
+    // quotient (quotient.hpp): the extended columns of l_0, l_last, l_active (R form) of the key below, and the
+    // scratch they are built in
+    DBuf q_l, q_tmp;
+    uint32_t q_k = 0, q_ek = 0, q_unusable = 0;
+    Fr q_shift{};
     hipEvent_t exp_ev[6] = {};
     // ---- captured verify_mul_witness ("graph", vm_graph): the launch sequence of
     // a device-input call is captured once into a HIP graph (the second call of
@@ -3284,7 +3290,7 @@ static std::vector<DBuf*> dbufs(svdw_ctx* c) {
                             &c->ing_c, &c->ing_p10, &c->ing_val, &c->ing_npos, &c->ing_nd, &c->ing_rpos,
                             &c->ing_kpos, &c->ing_err, &c->ing_q, &c->eq_cp, &c->eq_ks, &c->eq_reg, &c->eq_w,
                             &c->eq_k, &c->eq_err, &c->eq_st, &c->exp_buf[0], &c->exp_buf[1], &c->lkp, &c->ntt_tab,
-                            &c->ntt_tmp};
+                            &c->ntt_tmp, &c->q_l, &c->q_tmp};
     for (int i = 0; i < kMaxScanJobs; ++i) {
         v.push_back(&c->wbc[i]);
         v.push_back(&c->wbt[i]);
@@ -5608,6 +5614,319 @@ int svdw_check_ntt(svdw_ctx* c, uint32_t k_in, uint32_t k, int form, int inverse
         read_counters(c, cnt, hc, 2);
         result->rows_checked = hc[0];
         result->row_failures = hc[1];
+    });
+}
+// ---- the quotient polynomial on the extended domain and the verifier's identity
+// at a point (quotient.hpp)
+namespace {
+struct QCall {
+    Fr shift, beta, gamma, y, x;                           // canonical
+    uint32_t k = 0, ek = 0, le = 0, D = 0, nsets = 0;
+    uint64_t n = 0, N = 0, usable = 0;
+    std::vector<const void*> ptrs;                         // every column, in the order QuotientArgs::ptrs gives
+};
+}  // namespace
+// The argument checks of svdw_quotient and svdw_check_quotient (x: the latter's,
+// else null; out: the former's), in the order include/svdw.h gives; false: no
+// family, nothing to do.
+static bool q_args(svdw_ctx* c, const char* fn, const svdw_quotient_args* a, const void* out, const uint64_t* x,
+                   QCall* q) {
+    const std::string f(fn);
+    REQUIRE(c && a, "null argument");
+    check_form(a->form);
+    q->shift = fr_raw_words(a->shift);
+    q->beta = fr_raw_words(a->beta);
+    q->gamma = fr_raw_words(a->gamma);
+    q->y = fr_raw_words(a->y);
+    q->x = x ? fr_raw_words(x) : fr_zero();
+    REQUIRE(fr_reduced(q->shift) && !fr_is_zero(q->shift), f + ": shift >= p or shift == 0");
+    REQUIRE(fr_reduced(q->beta) && fr_reduced(q->gamma) && fr_reduced(q->y) && fr_reduced(q->x),
+            f + ": beta, gamma, y or x >= p");
+    const uint64_t rows = a->k < 63 ? 1ull << a->k : ~0ull;
+    if (!a->unusable_rows || a->unusable_rows >= rows) fail(SVDW_ERANGE, f + ": unusable_rows must be in [1, 2^k)");
+    REQUIRE(a->chunk_len || !a->n_perm, f + ": chunk_len == 0");
+    if (a->k < 1 || a->k > 28) fail(SVDW_ERANGE, f + ": k must be in [1, 28]");
+    if (a->extended_k < a->k || a->extended_k > 28) fail(SVDW_ERANGE, f + ": extended_k must be in [k, 28]");
+    q->k = a->k;
+    q->ek = a->extended_k;
+    q->le = q->ek - q->k;
+    q->n = rows;
+    q->N = 1ull << q->ek;
+    q->usable = rows - a->unusable_rows;
+    q->nsets = a->n_perm ? pp_sets(a->n_perm, a->chunk_len) : 0;
+    q->D = std::max({a->n_gate ? 3u : 0u, a->n_lookup ? 4u : 0u,
+                     a->n_perm ? 2u + std::min(a->chunk_len, a->n_perm) : 0u});
+    if (q->D > (1ull << q->le) + 1) fail(SVDW_ERANGE, f + ": the degree does not fit the extended domain (D > E + 1)");
+    {
+        Fr t = fr_to_mont(q->shift);                       // shift^N == 1: shift^n is an E-th root of unity
+        for (uint32_t i = 0; i < q->ek; ++i) t = mont_mul(t, t);
+        REQUIRE(!fr_eq(t, fr_to_mont(fr_from_u64(1))), f + ": shift^n is an E-th root of unity (a zero divisor)");
+    }
+    REQUIRE(!c->dry, f + " needs a device context");
+    if (a->n_gate > 65535 || a->n_perm > 65535 || a->n_lookup > 65535)
+        fail(SVDW_ERANGE, f + ": more than 65535 columns in a family");
+    if (!a->n_gate && !a->n_perm && !a->n_lookup) return false;
+    REQUIRE(out || x, "null argument");
+    const struct {
+        const void* const* p;
+        uint32_t n;
+    } fam[] = {{a->advice, a->n_gate},          {a->selectors, a->n_gate},       {a->perm_columns, a->n_perm},
+               {a->sigma, a->n_perm},           {a->perm_z, q->nsets},           {a->lookup_input, a->n_lookup},
+               {a->lookup_table, a->n_lookup},  {a->permuted_input, a->n_lookup}, {a->permuted_table, a->n_lookup},
+               {a->lookup_z, a->n_lookup}};
+    for (const auto& fm : fam) {
+        REQUIRE(fm.p || !fm.n, "null argument");
+        for (uint32_t j = 0; j < fm.n; ++j) {
+            REQUIRE(fm.p[j], f + ": null column pointer");
+            q->ptrs.push_back(fm.p[j]);
+        }
+    }
+    if (out) {
+        const uintptr_t o0 = (uintptr_t)out, o1 = o0 + q->N * sizeof(Fr);
+        for (const void* p : q->ptrs) {
+            const uintptr_t i0 = (uintptr_t)p, i1 = i0 + q->N * sizeof(Fr);
+            REQUIRE(i1 <= o0 || o1 <= i0, f + ": h_ext overlaps an input column");
+        }
+    }
+    return true;
+}
+// The extended columns of l_0, l_last, l_active (R form, 3 x N cells) for the
+// call's key: three Lagrange columns through the engine's own inverse and coset
+// transforms, kept on the context until the key changes.
+static const Fr* q_basis(svdw_ctx* c, const QCall& q, uint32_t unusable_rows) {
+    const size_t need = 3 * q.N * sizeof(Fr);
+    if (c->q_l.cap >= need && c->q_k == q.k && c->q_ek == q.ek && c->q_unusable == unusable_rows &&
+        fr_eq(c->q_shift, q.shift))
+        return (const Fr*)c->q_l.p;
+    c->q_k = 0;                                            // no key while the columns are rebuilt
+    ensure_buf(c, c->q_l, need);
+    ensure_buf(c, c->q_tmp, 6 * q.n * sizeof(Fr));
+    Fr* lag = (Fr*)c->q_tmp.p;
+    Fr* cf = lag + 3 * q.n;
+    profiled(c, "k_quotient_basis", 96.0 * q.n, [&] {
+        return launch_quotient_basis(lag, q.n, q.usable, fr_to_mont(fr_from_u64(1)), c->st);
+    });
+    const void* in[3] = {lag, lag + q.n, lag + 2 * q.n};
+    const void* mid[3] = {cf, cf + q.n, cf + 2 * q.n};
+    uint64_t sh[4];
+    fr_store_words(q.shift, sh);
+    svdw_ntt_result r;
+    int rc = svdw_ntt(c, q.k, q.k, SVDW_FORM_MONTGOMERY, 1, nullptr, in, 3, cf, &r);
+    if (rc == SVDW_OK) rc = svdw_ntt(c, q.k, q.ek, SVDW_FORM_MONTGOMERY, 0, sh, mid, 3, c->q_l.p, &r);
+    if (rc != SVDW_OK) fail(rc, g_err);
+    c->q_k = q.k;
+    c->q_ek = q.ek;
+    c->q_unusable = unusable_rows;
+    c->q_shift = q.shift;
+    return (const Fr*)c->q_l.p;
+}
+int svdw_quotient(svdw_ctx* c, const svdw_quotient_args* args, void* h_ext, svdw_quotient_result* result) {
+    return guarded([&] {
+        REQUIRE(result, "null argument");
+        QCall q;
+        const bool any = q_args(c, "svdw_quotient", args, h_ext, nullptr, &q);
+        memset(result, 0, sizeof *result);
+        result->rows = q.N;
+        result->extension = 1u << q.le;
+        result->degree = q.D;
+        if (!any) return;
+        REQUIRE(h_ext, "null output");
+        sync(c);
+        const bool mont = args->form == SVDW_FORM_MONTGOMERY;
+        const uint32_t ng = args->n_gate, np = args->n_perm, nl = args->n_lookup, E = 1u << q.le;
+        const Fr* l = (np | nl) ? q_basis(c, q, args->unusable_rows) : nullptr;
+        const uint32_t h = pp_split(q.ek);
+        const Fr* tab = ntt_tables(c, q.ek);
+        const Fr one = fr_to_mont(fr_from_u64(1));
+        // the staged cells: beta delta^j phi for j < np, then the E inverses of the divisor as c R
+        const NttDev d = ntt_stage(c, q.ptrs.data(), (uint32_t)q.ptrs.size(), (size_t)np + E, 0, [&](Fr* t) {
+            pp_delta_powers(q.beta, args->form, np, t);
+            Fr* inv = t + np;
+            Fr sn = fr_to_mont(q.shift), wn = pp_omega_mont(q.ek);   // shift^n R, omega_e^n R
+            for (uint32_t i = 0; i < q.k; ++i) {
+                sn = mont_mul(sn, sn);
+                wn = mont_mul(wn, wn);
+            }
+            // batch inversion: prefix products, one inverse, back substitution
+            std::vector<Fr> dv(E), pre(E);
+            Fr acc = one;
+            for (uint32_t i = 0; i < E; ++i) {
+                dv[i] = fr_sub(sn, one);                   // (shift^n omega_e^(n i) - 1) R, not zero (q_args)
+                pre[i] = acc;
+                acc = mont_mul(acc, dv[i]);
+                sn = mont_mul(sn, wn);
+            }
+            Fr ia = fr_to_mont(fr_to_mont(fr_inv(acc)));    // acc = P R: (P R)^-1 R^2 = P^-1 R
+            for (uint32_t i = E; i-- > 0;) {
+                inv[i] = mont_mul(ia, pre[i]);
+                ia = mont_mul(ia, dv[i]);
+            }
+        });
+        QuotientArgs a{};
+        a.ptrs = d.cols;
+        a.bd = d.cells;
+        a.inv = d.cells + np;
+        a.wlo = tab + 1024;
+        a.whi = a.wlo + ((size_t)1 << h);
+        a.l0 = l;
+        a.llast = l ? l + q.N : nullptr;
+        a.lact = l ? l + 2 * q.N : nullptr;
+        a.out = (Fr*)h_ext;
+        a.y = fr_to_mont(q.y);
+        a.beta = fr_to_mont(q.beta);
+        a.shift = fr_to_mont(q.shift);
+        a.gamma = mont ? fr_to_mont(q.gamma) : q.gamma;
+        a.betaf = mont ? a.beta : q.beta;
+        a.one = mont ? one : fr_from_u64(1);
+        a.ek = q.ek;
+        a.le = q.le;
+        a.h = h;
+        a.ng = ng;
+        a.np = np;
+        a.chunk = args->chunk_len;
+        a.nsets = q.nsets;
+        a.nl = nl;
+        a.usable = q.usable;
+        const double cols = 5.0 * ng + 2.0 * np + 3.0 * q.nsets + 7.0 * nl + ((np | nl) ? 3.0 : 0.0) + 1.0;
+        profiled(c, "k_quotient", 32.0 * cols * (double)q.N, [&] { return launch_quotient(a, args->form, c->st); });
+        result->gate_expressions = ng;
+        result->permutation_expressions = np ? 1 + 2 * (uint64_t)q.nsets : 0;
+        result->lookup_expressions = 5 * (uint64_t)nl;
+    });
+}
+// l_i(x) R for x^n != 1: omega^i (x^n - 1) / (n (x - omega^i)); t = (x^n - 1) / n as t R.
+static Fr q_lagrange_at(const Fr& xR, const Fr& wiR, const Fr& tR) {
+    const Fr inv = fr_to_mont(fr_inv(fr_from_mont(fr_sub(xR, wiR))));
+    return mont_mul(mont_mul(wiR, tR), inv);
+}
+int svdw_check_quotient(svdw_ctx* c, const svdw_quotient_args* args, const void* h_coeffs, const uint64_t x[4],
+                        svdw_quotient_check* result) {
+    return guarded([&] {
+        REQUIRE(result && x, "null argument");
+        QCall q;
+        const bool any = q_args(c, "svdw_check_quotient", args, nullptr, x, &q);
+        memset(result, 0, sizeof *result);
+        if (!any) return;
+        REQUIRE(h_coeffs, "null argument");
+        sync(c);
+        const bool mont = args->form == SVDW_FORM_MONTGOMERY;
+        const uint32_t ng = args->n_gate, np = args->n_perm, nl = args->n_lookup, ns = q.nsets;
+        const Fr one = fr_to_mont(fr_from_u64(1));
+        // the points x omega^r R, r in {0, 1, 2, 3, -1, usable}
+        constexpr uint32_t kPts = 6;
+        const Fr xR = fr_to_mont(q.x), w = pp_omega_mont(q.k);
+        const Fr wu = fr_to_mont(fr_pow_u64(fr_from_mont(w), q.usable)), wm = fr_to_mont(fr_pow_u64(fr_from_mont(w), q.n - 1));
+        const Fr w2 = mont_mul(w, w);
+        const Fr pts[kPts] = {xR, mont_mul(xR, w), mont_mul(xR, w2), mont_mul(xR, mont_mul(w2, w)), mont_mul(xR, wm),
+                              mont_mul(xR, wu)};
+        // every column at every point, in chunks of columns; the values as v R
+        const size_t total = q.ptrs.size();
+        std::vector<Fr> vals(total * kPts);
+        constexpr size_t kColChunk = 16384;
+        for (size_t c0 = 0; c0 < total; c0 += kColChunk) {
+            const uint32_t nc = (uint32_t)std::min(kColChunk, total - c0);
+            const size_t part = (size_t)nc * kPts * ntt_eval_blocks(q.n) * sizeof(Fr), outb = (size_t)nc * kPts * sizeof(Fr);
+            const NttDev d = ntt_stage(c, q.ptrs.data() + c0, nc, kPts, part + outb, [&](Fr* t) {
+                for (uint32_t i = 0; i < kPts; ++i) t[i] = pts[i];
+            });
+            Fr* dout = (Fr*)(d.free + part);
+            ntt_eval_chunks(c, d.cols, nullptr, q.n, nc, d.cells, kPts, kPts, (Fr*)d.free, kPts, dout, true,
+                            [](uint64_t, uint32_t) {});
+            hipck(hipMemcpyAsync(vals.data() + c0 * kPts, dout, outb, hipMemcpyDeviceToHost, c->st), "D2H");
+            hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+        }
+        // h at x, and its tail counted on the device
+        Fr hx;
+        unsigned long long tail[2];
+        {
+            const size_t part = (size_t)ntt_eval_blocks(q.N) * sizeof(Fr);
+            const NttDev d = ntt_stage(c, &h_coeffs, 1, 1, part + sizeof(Fr), [&](Fr* t) { t[0] = xR; });
+            Fr* dout = (Fr*)(d.free + part);
+            ntt_eval_chunks(c, d.cols, nullptr, q.N, 1, d.cells, 1, 1, (Fr*)d.free, 1, dout, true,
+                            [](uint64_t, uint32_t) {});
+            unsigned long long* cnt = (unsigned long long*)c->lkp.p;
+            const uint64_t from = (uint64_t)q.D * (q.n - 1) + 1 - q.n;   // D >= 2: not negative
+            profiled(c, "k_quotient_tail", 32.0 * (double)(q.N - from),
+                     [&] { return launch_quotient_tail((const Fr*)h_coeffs, from, q.N, cnt, c->st); });
+            hipck(hipMemcpyAsync(&hx, dout, sizeof(Fr), hipMemcpyDeviceToHost, c->st), "D2H");
+            read_counters(c, cnt, tail, 2);
+        }
+        if (!mont) {
+            for (Fr& v : vals) v = fr_to_mont(v);
+            hx = fr_to_mont(hx);
+        }
+        // l_0, l_last, l_active at x by the closed form
+        Fr xn = xR;
+        for (uint32_t i = 0; i < q.k; ++i) xn = mont_mul(xn, xn);
+        const Fr xn1 = fr_sub(xn, one);
+        Fr l0, ll, la = one;
+        {
+            const bool on_domain = fr_is_zero(xn1);       // x = omega^i: l_i(x) = 1 there and 0 elsewhere
+            const Fr t = mont_mul(xn1, fr_to_mont(fr_inv(fr_from_u64(q.n))));
+            l0 = on_domain ? (fr_eq(xR, one) ? one : fr_zero()) : q_lagrange_at(xR, one, t);
+            ll = fr_zero();
+            Fr wi = wu;
+            for (uint64_t i = q.usable; i < q.n; ++i) {
+                const Fr li = on_domain ? (fr_eq(xR, wi) ? one : fr_zero()) : q_lagrange_at(xR, wi, t);
+                if (i == q.usable) ll = li;
+                la = fr_sub(la, li);
+                wi = mont_mul(wi, w);
+            }
+        }
+        // the fold, include/svdw.h's list in its order
+        const Fr b = fr_to_mont(q.beta), g = fr_to_mont(q.gamma), y = fr_to_mont(q.y);
+        size_t base[10];
+        {
+            const uint32_t cnt[10] = {ng, ng, np, np, ns, nl, nl, nl, nl, nl};
+            size_t at = 0;
+            for (int i = 0; i < 10; ++i) {
+                base[i] = at;
+                at += cnt[i];
+            }
+        }
+        enum { ADV, SEL, PV, SIG, PZ, LA, LT, LAP, LSP, LZ };
+        enum { X0, X1, X2, X3, XM, XU };
+        auto val = [&](int fam, size_t i, int pt) { return vals[(base[fam] + i) * kPts + pt]; };
+        Fr h = fr_zero();
+        auto push = [&](const Fr& e) { h = fr_add(mont_mul(h, y), e); };
+        for (uint32_t i = 0; i < ng; ++i)
+            push(mont_mul(val(SEL, i, X0),
+                          fr_sub(fr_add(val(ADV, i, X0), mont_mul(val(ADV, i, X1), val(ADV, i, X2))), val(ADV, i, X3))));
+        if (np) {
+            push(mont_mul(l0, fr_sub(one, val(PZ, 0, X0))));
+            const Fr zl = val(PZ, ns - 1, X0);
+            push(mont_mul(ll, fr_sub(mont_mul(zl, zl), zl)));
+            for (uint32_t s = 1; s < ns; ++s) push(mont_mul(l0, fr_sub(val(PZ, s, X0), val(PZ, s - 1, XU))));
+            Fr bd = b;                                     // beta delta^j R
+            const Fr dl = fr_to_mont(pp_consts().delta);
+            for (uint32_t s = 0; s < ns; ++s) {
+                Fr left = val(PZ, s, X1), right = val(PZ, s, X0);
+                for (uint32_t j = s * args->chunk_len; j < std::min<uint64_t>((uint64_t)(s + 1) * args->chunk_len, np); ++j) {
+                    const Fr v = fr_add(val(PV, j, X0), g);
+                    left = mont_mul(left, fr_add(v, mont_mul(b, val(SIG, j, X0))));
+                    right = mont_mul(right, fr_add(v, mont_mul(bd, xR)));
+                    bd = mont_mul(bd, dl);
+                }
+                push(mont_mul(la, fr_sub(left, right)));
+            }
+        }
+        for (uint32_t i = 0; i < nl; ++i) {
+            const Fr z = val(LZ, i, X0), ap = val(LAP, i, X0), sp = val(LSP, i, X0);
+            push(mont_mul(l0, fr_sub(one, z)));
+            push(mont_mul(ll, fr_sub(mont_mul(z, z), z)));
+            const Fr left = mont_mul(val(LZ, i, X1), mont_mul(fr_add(ap, b), fr_add(sp, g)));
+            const Fr right = mont_mul(z, mont_mul(fr_add(val(LA, i, X0), b), fr_add(val(LT, i, X0), g)));
+            push(mont_mul(la, fr_sub(left, right)));
+            const Fr d = fr_sub(ap, sp);
+            push(mont_mul(l0, d));
+            push(mont_mul(la, mont_mul(d, fr_sub(ap, val(LAP, i, XM)))));
+        }
+        const Fr lhs = fr_from_mont(mont_mul(hx, xn1)), rhs = fr_from_mont(h);
+        fr_store_words(lhs, result->lhs);
+        fr_store_words(rhs, result->rhs);
+        result->identity_failures = !fr_eq(lhs, rhs);
+        result->tail_checked = tail[0];
+        result->tail_nonzero = tail[1];
     });
 }
 int svdw_rlc_trace(const svdw_ctx* c, uint64_t* cells, uint64_t* copies, uint32_t* n) {

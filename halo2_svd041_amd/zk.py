@@ -20,7 +20,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import (CheckResult, EqCheck, LookupCheck, LookupProductCheck, LookupProductResult, LookupResult, NttCheck, NttResult, PermutationProductCheck, PermutationProductResult, PhysParams, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SvdwError,
+from ._lib import (CheckResult, EqCheck, LookupCheck, LookupProductCheck, LookupProductResult, LookupResult, NttCheck, NttResult, PermutationProductCheck, PermutationProductResult, PhysParams, QuotientArgs, QuotientCheck, QuotientResult, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SvdwError,
                    Vec, check, lib)
 
 P_MOD = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -796,6 +796,92 @@ class Context:
         check(lib().svdw_check_ntt(self._h, k_in, k, _form(form), 1 if inverse else 0, sh, cp, n,
                                    out.data_ptr() if n else None, log_samples, seed & _M64, ct.byref(r)))
         return {"rows_checked": r.rows_checked, "row_failures": r.row_failures}
+
+    # ---- quotient polynomial (include/svdw.h, "quotient"; parity unpinned)
+    _QUOTIENT_FAMILIES = ("advice", "selectors", "perm_columns", "sigma", "perm_z", "lookup_input", "lookup_table",
+                          "permuted_input", "permuted_table", "lookup_z")
+
+    def _quotient_args(self, rows: int, k: int, extended_k: int, shift: int, beta: int, gamma: int, y: int,
+                       chunk_len: int, unusable_rows: int, form: str, families: dict):
+        """(QuotientArgs, what keeps its pointer arrays alive, the columns' device)
+        from the keyword arguments of quotient / check_quotient; every column of
+        every family has `rows` cells."""
+        a = QuotientArgs()
+        a.shift, a.beta, a.gamma, a.y = (self._shift_arg(shift), _challenge_arg(beta), _challenge_arg(gamma),
+                                         _challenge_arg(y))
+        unknown = set(families) - set(self._QUOTIENT_FAMILIES)
+        if unknown:
+            raise TypeError(f"unknown column family {sorted(unknown)[0]!r}")
+        a.k, a.extended_k, a.unusable_rows, a.form, a.chunk_len = k, extended_k, unusable_rows, _form(form), chunk_len
+        keep, count, dev = [], {}, None
+        for name in self._QUOTIENT_FAMILIES:
+            ptrs, count[name], d = self._column_pointers(name, families.get(name, ()), rows)
+            dev = dev or d
+            keep.append(ptrs)
+            setattr(a, name, ct.cast(ptrs, ct.c_void_p))
+        if count["advice"] != count["selectors"]:
+            raise SvdwError(-1, "advice and selectors differ in their number of columns")
+        if count["perm_columns"] != count["sigma"]:
+            raise SvdwError(-1, "perm_columns and sigma differ in their number of columns")
+        if chunk_len > 0 and count["perm_z"] != -(-count["perm_columns"] // chunk_len):
+            raise SvdwError(-1, "perm_z must hold one column per set of chunk_len columns")
+        if len({count[f] for f in self._QUOTIENT_FAMILIES[5:]}) != 1:
+            raise SvdwError(-1, "the lookup families differ in their number of columns")
+        a.n_gate, a.n_perm, a.n_lookup = count["advice"], count["perm_columns"], count["lookup_z"]
+        return a, keep, dev
+
+    def quotient(self, k: int, extended_k: int, shift: int, beta: int, gamma: int, y: int, chunk_len: int = 0,
+                 unusable_rows: int = 6, form: str = "canonical", out=None, **families):
+        """(h_ext, result): the quotient polynomial on the extended domain
+        (svdw_quotient), a [1, 2^extended_k, 32] u8 device tensor in `form`: the
+        gates, the permutation argument and the lookup arguments folded with
+        powers of y in the header's order and divided by X^n - 1. The families
+        are keyword arguments named as the struct's fields (advice, selectors;
+        perm_columns, sigma, perm_z with chunk_len; lookup_input, lookup_table,
+        permuted_input, permuted_table, lookup_z), each a tensor
+        [n, 2^extended_k, 32] u8 in `form` or a list of such tensors, already on
+        the coset of `shift` (coeff_to_extended); any family may be left out.
+        result: gate_expressions, permutation_expressions, lookup_expressions,
+        rows, extension, degree."""
+        import torch
+        rows = 1 << extended_k if 0 <= extended_k < 32 else 0
+        a, _keep, dev = self._quotient_args(rows, k, extended_k, shift, beta, gamma, y, chunk_len, unusable_rows, form,
+                                           families)
+        if out is None:
+            out = torch.empty((1, rows, 32), dtype=torch.uint8, device=dev or torch.device("cuda", self.device))
+        if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.uint8
+                or not out.is_contiguous() or tuple(out.shape) != (1, rows, 32)):
+            raise SvdwError(-1, "out must be a contiguous uint8 device tensor [1, 2^extended_k, 32]")
+        r = QuotientResult()
+        _after_torch(self)
+        check(lib().svdw_quotient(self._h, ct.byref(a), out.data_ptr(), ct.byref(r)))
+        _before_torch(self)
+        return out, {k_: getattr(r, k_) for k_, _ in QuotientResult._fields_}
+
+    def check_quotient(self, h_coeffs, x: int, k: int, extended_k: int, shift: int, beta: int, gamma: int, y: int,
+                       chunk_len: int = 0, unusable_rows: int = 6, form: str = "canonical", **families) -> dict:
+        """The verifier's identity h(x) (x^n - 1) == fold(x) at the point x
+        (svdw_check_quotient). The families as for quotient, but every column in
+        coefficient form, [n, 2^k, 32] u8; h_coeffs: [1, 2^extended_k, 32] u8, the
+        coefficients of h. Returns lhs and rhs as ints, identity_failures (0 or
+        1), tail_checked and tail_nonzero (the coefficients of h above
+        D (n - 1) - n)."""
+        import torch
+        xa = _challenge_arg(x)
+        rows = 1 << k if 0 <= k < 32 else 0
+        a, _keep, _ = self._quotient_args(rows, k, extended_k, shift, beta, gamma, y, chunk_len, unusable_rows, form,
+                                         families)
+        ext_rows = 1 << extended_k if 0 <= extended_k < 32 else 0
+        if h_coeffs is not None and (not isinstance(h_coeffs, torch.Tensor) or not h_coeffs.is_cuda
+                                     or h_coeffs.dtype != torch.uint8 or not h_coeffs.is_contiguous()
+                                     or tuple(h_coeffs.shape) != (1, ext_rows, 32)):
+            raise SvdwError(-1, "h_coeffs must be a contiguous uint8 device tensor [1, 2^extended_k, 32]")
+        r = QuotientCheck()
+        _after_torch(self)
+        check(lib().svdw_check_quotient(self._h, ct.byref(a), h_coeffs.data_ptr() if h_coeffs is not None else None,
+                                        xa, ct.byref(r)))
+        return {"lhs": words_to_int(r.lhs), "rhs": words_to_int(r.rhs), "identity_failures": r.identity_failures,
+                "tail_checked": r.tail_checked, "tail_nonzero": r.tail_nonzero}
 
     def profile(self, on: bool = True, prefix: str = "") -> None:
         """Record HIP events around kernel launches (names starting with `prefix`)."""

@@ -815,6 +815,115 @@ typedef struct {
 int svdw_check_ntt(svdw_ctx* ctx, uint32_t k_in, uint32_t k, int form, int inverse, const uint64_t shift[4],
                    const void* const* in, uint32_t ncols, const void* out, uint32_t log_samples, uint64_t seed,
                    svdw_ntt_check* result);
+/* ---------------------------------------------------------------- quotient
+ * The quotient polynomial h(X) of halo2_proofs' plonk::evaluation::evaluate_h
+ * on the extended domain, for the circuit shape this engine assigns:
+ * halo2-base's vertical gate per advice column, the permutation argument and
+ * one lookup argument per lookup column. Restated from memory like the steps
+ * above: PARITY UNPINNED. These calls need no witness and no physical layout.
+ *
+ * n = 2^k, N = 2^extended_k, E = N / n, omega = omega_k, omega_e =
+ * omega_extended_k, usable = n - unusable_rows. l_0, l_last and l_active are the
+ * polynomials whose Lagrange columns are e_0, e_usable and (1 on the rows below
+ * usable, 0 from usable on) = 1 - (l_last + l_blind). Extended row j is the
+ * point X_j = shift omega_e^j, shift the caller's ZETA as for coeff_to_extended;
+ * a rotation by r rows of the original domain, f(omega^r X), is extended row
+ * (j + r E) mod N. With y the caller's challenge, h starts at 0 and every
+ * expression e below does h <- h y + e, in this order:
+ *
+ *  1. Gates, one per (advice column a_i, its selector q_i), i < n_gate:
+ *       q_i(X) (a_i(X) + a_i(omega X) a_i(omega^2 X) - a_i(omega^3 X))
+ *  2. Permutation (n_perm > 0), sets of chunk_len columns; Z_s, sigma_j, delta,
+ *     the set layout and j counting over all columns exactly as in the
+ *     permutation section above, last = nsets - 1:
+ *       l_0 (1 - Z_0)
+ *       l_last (Z_last^2 - Z_last)
+ *       for s = 1 .. nsets - 1:  l_0 (Z_s(X) - Z_{s-1}(omega^usable X))
+ *       for every set s:         l_active (Z_s(omega X) prod_{j in s} (v_j + beta sigma_j + gamma)
+ *                                          - Z_s(X) prod_{j in s} (v_j + beta delta^j X + gamma))
+ *  3. Lookups, per argument i < n_lookup with the input column A and the table
+ *     column T given as columns:
+ *       l_0 (1 - Z)
+ *       l_last (Z^2 - Z)
+ *       l_active (Z(omega X) (A' + beta) (S' + gamma) - Z(X) (A + beta) (T + gamma))
+ *       l_0 (A' - S')
+ *       l_active (A' - S') (A'(X) - A'(omega^-1 X))
+ *
+ * Finally h_ext[j] = h (X_j^n - 1)^-1. The divisor takes E distinct values,
+ * shift^n (omega_e^n)^(j mod E) - 1, inverted once per call. For an honest
+ * witness with the zero blinding rows the engine writes every expression
+ * vanishes on all n rows, the division is exact, and the coefficients of h
+ * (extended_to_coeff of h_ext) are zero above index D (n - 1) - n, D = max(3
+ * with gates, 4 with lookups, 2 + the columns of the largest set), 0 without
+ * any family. Deriving y, beta, gamma, the blinding rows' randomness, cutting h
+ * into pieces and the commitments stay with the caller.
+ *
+ * Every array is a HOST array of DEVICE column pointers (as svdw_ntt takes
+ * them). For svdw_quotient each column is 2^extended_k cells in `form`, already
+ * on the coset (the caller ran coeff_to_extended with the same shift); for
+ * svdw_check_quotient each is the 2^k coefficients of the same polynomial. */
+typedef struct {
+    uint32_t k, extended_k, unusable_rows;
+    int form;
+    uint64_t shift[4], beta[4], gamma[4], y[4];   /* canonical */
+    const void* const* advice;                    /* [n_gate] */
+    const void* const* selectors;                 /* [n_gate], cells */
+    uint32_t n_gate;
+    uint32_t n_perm, chunk_len, n_lookup;
+    const void* const* perm_columns;              /* [n_perm], the v_j */
+    const void* const* sigma;                     /* [n_perm] */
+    const void* const* perm_z;                    /* [ceil(n_perm / chunk_len)] */
+    const void* const* lookup_input;              /* A, [n_lookup] each */
+    const void* const* lookup_table;              /* T */
+    const void* const* permuted_input;            /* A' */
+    const void* const* permuted_table;            /* S' */
+    const void* const* lookup_z;
+} svdw_quotient_args;
+typedef struct {
+    uint64_t gate_expressions, permutation_expressions, lookup_expressions;   /* folded */
+    uint64_t rows;          /* 2^extended_k */
+    uint32_t extension;     /* E */
+    uint32_t degree;        /* D */
+} svdw_quotient_result;
+/* h_ext: DEVICE, one column of 2^extended_k cells in `form`. All arithmetic is
+ * exact mod p; cells are taken as field elements below p. Any family may be
+ * empty; with all three empty the call returns SVDW_OK and touches nothing. The
+ * checks of the arguments come first, before anything touches the device, in
+ * this order: an unknown form (SVDW_EINVAL), shift, beta, gamma or y >= p or
+ * shift == 0 (SVDW_EINVAL), unusable_rows == 0 or >= 2^k (SVDW_ERANGE),
+ * chunk_len == 0 with n_perm > 0 (SVDW_EINVAL), k outside 1..28 or extended_k
+ * outside k..28 (SVDW_ERANGE), a degree that does not fit, D > E + 1
+ * (SVDW_ERANGE), shift^n an E-th root of unity, which makes a divisor zero
+ * (SVDW_EINVAL), a planning context (SVDW_EINVAL), more than 65535 columns in a
+ * family (SVDW_ERANGE), null pointers (SVDW_EINVAL), h_ext overlapping an input
+ * column (SVDW_EINVAL). The call is queued on the context's streams like
+ * svdw_ntt, with no host wait; scratch is the engine's. The engine builds the
+ * extended columns of l_0, l_last and l_active itself, from their Lagrange
+ * columns through its own inverse and coset transforms, and keeps them on the
+ * context for the next call of the same (k, extended_k, unusable_rows, shift);
+ * they are held in Montgomery form whatever `form` is, as multipliers are. */
+int svdw_quotient(svdw_ctx* ctx, const svdw_quotient_args* args, void* h_ext, svdw_quotient_result* result);
+typedef struct {
+    uint64_t lhs[4];              /* h(x) (x^n - 1), canonical */
+    uint64_t rhs[4];              /* the fold at x, canonical */
+    uint64_t identity_failures;   /* 0 or 1: lhs != rhs */
+    uint64_t tail_checked;        /* coefficients of h above D (n - 1) - n: N - 1 - (D (n - 1) - n) */
+    uint64_t tail_nonzero;        /* those that are not zero */
+} svdw_quotient_check;
+/* The verifier's identity h(x) (x^n - 1) == fold(x) at a caller-chosen point x
+ * (canonical, >= p: SVDW_EINVAL, checked with the challenges). coeffs: the
+ * arguments of svdw_quotient with every column in coefficient form, 2^k cells;
+ * h_coeffs: DEVICE, 2^extended_k cells in `form`. Every polynomial is evaluated
+ * at x omega^r for r in {0, 1, 2, 3, -1, usable} with the kernels of
+ * svdw_eval_polynomial, h at x; l_0(x), l_last(x) and l_active(x) come from the
+ * closed form l_i(x) = omega^i (x^n - 1) / (n (x - omega^i)) on the host, and
+ * the fold is redone on those few values there: it shares nothing with the
+ * extended-domain kernel. The tail is counted on the device. Arguments and
+ * their checks as for svdw_quotient (there is no output to overlap); it writes
+ * to neither side and returns after the device has finished. Without any
+ * family: SVDW_OK, nothing is evaluated and the result is zero. */
+int svdw_check_quotient(svdw_ctx* ctx, const svdw_quotient_args* coeffs, const void* h_coeffs,
+                        const uint64_t x[4], svdw_quotient_check* result);
 /* Up to cap segments of the last witness into out; *n = total count. */
 int svdw_shard_segments(const svdw_ctx* ctx, svdw_segment* out, uint64_t cap, uint64_t* n);
 
