@@ -117,6 +117,17 @@ class NttCheck(ct.Structure):
     _fields_ = [("rows_checked", ct.c_uint64), ("row_failures", ct.c_uint64)]
 
 
+class CommitResult(ct.Structure):
+    _fields_ = [("columns", ct.c_uint32), ("window_bits", ct.c_uint32), ("windows", ct.c_uint32),
+                ("rows", ct.c_uint64), ("zero_scalars", ct.c_uint64), ("identity_bases", ct.c_uint64),
+                ("identity_outputs", ct.c_uint64)]
+
+
+class CommitCheck(ct.Structure):
+    _fields_ = [("columns_checked", ct.c_uint64), ("commit_failures", ct.c_uint64),
+                ("bases_checked", ct.c_uint64), ("bases_off_curve", ct.c_uint64)]
+
+
 class QuotientArgs(ct.Structure):
     _fields_ = [("k", ct.c_uint32), ("extended_k", ct.c_uint32), ("unusable_rows", ct.c_uint32), ("form", ct.c_int),
                 ("shift", ct.c_uint64 * 4), ("beta", ct.c_uint64 * 4), ("gamma", ct.c_uint64 * 4),
@@ -282,6 +293,10 @@ SIGNATURES = {
     "svdw_check_ntt": (_i32, [_P, _u32, _u32, _i32, _i32, _P, _P, _u32, _P, _u32, _u64, ct.POINTER(NttCheck)]),
     "svdw_quotient": (_i32, [_P, ct.POINTER(QuotientArgs), _P, ct.POINTER(QuotientResult)]),
     "svdw_check_quotient": (_i32, [_P, ct.POINTER(QuotientArgs), _P, _P, ct.POINTER(QuotientCheck)]),
+    "svdw_commit_plan": (None, [_u32, ct.POINTER(_u32), ct.POINTER(_u32)]),
+    "svdw_commit": (_i32, [_P, _u32, _i32, _i32, _P, _P, _u32, _P, ct.POINTER(CommitResult)]),
+    "svdw_check_commit": (_i32, [_P, _u32, _i32, _i32, _P, _P, _u32, _P, ct.POINTER(CommitCheck)]),
+    "svdw_commit_add_probe": (_i32, [_P, _P, _u32, _u64, _u32, ct.POINTER(ct.c_double)]),
 }
 
 _lib = None

@@ -33,6 +33,7 @@
 #include "lookup.hpp"
 #include "lookup_product.hpp"
 #include "ntt.hpp"
+#include "commit.hpp"
 #include "quotient.hpp"
 #include "permutation_product.hpp"
 
@@ -430,6 +431,9 @@ struct svdw_ctx {
                                                 // critical path sharded, and unsharded it measured
                                                 // 2.5 % faster at 1024^2 and 2048^2, neutral at 512^2
         uint32_t hold_us = 0;                   // "hold_us": timing aid, st spins this long first
+        uint32_t commit_window_bits = 0;        // "commit_window_bits": svdw_commit's window, 0: svdw_commit_plan's
+                                                // (a tuning aid, tools/commit_bench.py; the result reports it)
+        uint32_t commit_scratch_mib = 1024;     // "commit_scratch_mib": svdw_commit's workspace cap per batch of tasks
         bool rlc_prefix = false;                // "rlc_prefix": svd_witness's phase 1 starts with the
                                                 // ctx_gate cells of load_rlc_cache(.., 1)
         int p1_at = -1;                         // "p1_at": phase 1 on st3 (mode 2) enqueued after
@@ -681,6 +685,7 @@ struct svdw_ctx {
     std::vector<char> pp_up;                // its staged upload: pointer, delta and omega tables
     DBuf ntt_tab, ntt_tmp;                  // transforms (ntt.hpp): the stage and omega tables of ntt_k; the buffer
     uint32_t ntt_k = 0;                     // between passes
+    DBuf commit_ws;                         // commitments (commit.hpp): the window sums and one batch of tasks
     // quotient (quotient.hpp): the extended columns of l_0, l_last, l_active (R form) of the key below, and the
     // scratch they are built in
     DBuf q_l, q_tmp;
@@ -3290,7 +3295,7 @@ static std::vector<DBuf*> dbufs(svdw_ctx* c) {
                             &c->ing_c, &c->ing_p10, &c->ing_val, &c->ing_npos, &c->ing_nd, &c->ing_rpos,
                             &c->ing_kpos, &c->ing_err, &c->ing_q, &c->eq_cp, &c->eq_ks, &c->eq_reg, &c->eq_w,
                             &c->eq_k, &c->eq_err, &c->eq_st, &c->exp_buf[0], &c->exp_buf[1], &c->lkp, &c->ntt_tab,
-                            &c->ntt_tmp, &c->q_l, &c->q_tmp};
+                            &c->ntt_tmp, &c->q_l, &c->q_tmp, &c->commit_ws};
     for (int i = 0; i < kMaxScanJobs; ++i) {
         v.push_back(&c->wbc[i]);
         v.push_back(&c->wbt[i]);
@@ -3404,6 +3409,10 @@ static void set_stage_elems(svdw_ctx* c, int64_t v) {
     REQUIRE(v % 16 == 0, kStageElemsMsg);
     c->opt.stage_elems = (uint32_t)v;
 }
+static void set_commit_window_bits(svdw_ctx* c, int64_t v) {
+    REQUIRE(v != 1, "commit_window_bits: 0 (the plan) or 2..16");
+    c->opt.commit_window_bits = (uint32_t)v;
+}
 using Opt = svdw_ctx::Options;
 static const OptionDef kOptions[] = {
     {"lanes", 1, 2, "lanes: 1 or 2", set_lanes},   // verify_mul_witness on two alternating states
@@ -3425,6 +3434,8 @@ static const OptionDef kOptions[] = {
     {"stage_batch", INT64_MIN, INT64_MAX, "", set_opt<&Opt::stage_batch>},   // small independent stages share k_stage_multi launches
     {"f64_views", INT64_MIN, INT64_MAX, "", set_opt<&Opt::f64_views>},
     {"p1_at", -1, 3, "p1_at: -1 (auto), 0, 1, 2 or 3", set_opt<&Opt::p1_at>},
+    {"commit_window_bits", 0, kCommitMaxBits, "commit_window_bits: 0 (the plan) or 2..16", set_commit_window_bits},
+    {"commit_scratch_mib", 1, 65536, "commit_scratch_mib: 1..65536", set_opt<&Opt::commit_scratch_mib>},
     {"dchk_at", 0, 2, "dchk_at: 0 (cell stream), 1 (st2) or 2 (st3)", set_opt<&Opt::dchk_at>},   // pipelined: the d checks' stream
     {"gamma_at", -1, 1, "gamma_at: -1 (auto), 0 (cell stream) or 1 (st3)", set_opt<&Opt::gamma_at>},   // pipelined: k_gamma_prep's stream
     {"overlap", INT64_MIN, INT64_MAX, "", set_opt<&Opt::overlap>},
@@ -5614,6 +5625,167 @@ int svdw_check_ntt(svdw_ctx* c, uint32_t k_in, uint32_t k, int form, int inverse
         read_counters(c, cnt, hc, 2);
         result->rows_checked = hc[0];
         result->row_failures = hc[1];
+    });
+}
+// ---- KZG commitments of columns: the multi-scalar multiplication and its
+// bit-serial check (commit.hpp)
+// A batch's workspace stays under the option "commit_scratch_mib" (1 GiB by
+// default: the order of ntt_tmp for 8 columns of 2^22 rows) unless one task
+// alone needs more. The kernels between the sort and the window sums are
+// latency-bound per batch, so fewer, larger batches are faster.
+// The argument checks of svdw_commit and svdw_check_commit, in the order
+// include/svdw.h gives; false: no columns, nothing to do.
+static bool commit_args(svdw_ctx* c, const char* fn, uint32_t k, int form, int bases_form, const void* bases,
+                        const void* const* cols, uint32_t ncols, const void* out, bool writes) {
+    const std::string f(fn);
+    REQUIRE(c, "null argument");
+    check_form(form);
+    check_form(bases_form);
+    if (k < 1 || k > 28) fail(SVDW_ERANGE, f + ": k must be in [1, 28]");
+    REQUIRE(!c->dry, f + " needs a device context");
+    if (!ncols) return false;
+    if (ncols > 65535) fail(SVDW_ERANGE, f + ": more than 65535 columns");
+    REQUIRE(bases && cols && out, "null argument");
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)ncols * sizeof(G1Affine);
+    const uintptr_t b0 = (uintptr_t)bases, b1 = b0 + (((uintptr_t)1 << k) * sizeof(G1Affine));
+    REQUIRE(!writes || b1 <= o0 || o1 <= b0, f + ": out overlaps the bases");
+    for (uint32_t j = 0; j < ncols; ++j) {
+        REQUIRE(cols[j], f + ": null column pointer");
+        const uintptr_t i0 = (uintptr_t)cols[j], i1 = i0 + (((uintptr_t)1 << k) * sizeof(Fr));
+        REQUIRE(!writes || i1 <= o0 || o1 <= i0, f + ": out overlaps an input column");
+    }
+    return true;
+}
+void svdw_commit_plan(uint32_t k, uint32_t* window_bits, uint32_t* windows) {
+    uint32_t c = 0, W = 0;
+    commit_plan(k < 1 ? 1 : k > 28 ? 28 : k, &c, &W);
+    if (window_bits) *window_bits = c;
+    if (windows) *windows = W;
+}
+int svdw_commit(svdw_ctx* c, uint32_t k, int form, int bases_form, const void* bases, const void* const* cols,
+                uint32_t ncols, void* out, svdw_commit_result* result) {
+    return guarded([&] {
+        REQUIRE(result, "null argument");
+        const bool any = commit_args(c, "svdw_commit", k, form, bases_form, bases, cols, ncols, out, true);
+        memset(result, 0, sizeof *result);
+        commit_plan(k, &result->window_bits, &result->windows);
+        if (c->opt.commit_window_bits) {                   // the tuning override
+            result->window_bits = c->opt.commit_window_bits;
+            result->windows = (255 + result->window_bits - 1) / result->window_bits;
+        }
+        result->rows = 1ull << k;
+        if (!any) return;
+        sync(c);
+        const uint32_t cb = result->window_bits, W = result->windows;
+        const uint64_t n = 1ull << k, B = 1ull << (cb - 1), tasks = (uint64_t)ncols * W;
+        const uint64_t per = commit_task_bytes(n, B);
+        const uint64_t cap = (uint64_t)c->opt.commit_scratch_mib << 20;
+        const uint32_t T = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(cap / per, 1),
+                                                        std::min<uint64_t>(tasks, 65535));
+        // the call's window sums, then the arrays of one batch, each from a 128-byte boundary
+        size_t off = 0;
+        auto take = [&](size_t bytes) {
+            const size_t at = off;
+            off += (bytes + 127) / 128 * 128;
+            return at;
+        };
+        const size_t o_win = take(tasks * sizeof(G1Xyzz)), o_slots = take(T * commit_slots_all(n) * sizeof(G1Xyzz)),
+                     o_bkt = take(T * B * sizeof(G1Xyzz)), o_chk = take(T * commit_chunks(B) * sizeof(G1Xyzz)),
+                     o_sorted = take(T * n * sizeof(uint32_t)), o_cur = take(T * B * sizeof(uint32_t)),
+                     o_start = take(T * (B + 1) * sizeof(uint32_t));
+        ensure_buf(c, c->commit_ws, off);
+        char* ws = (char*)c->commit_ws.p;
+        const NttDev d = ntt_stage(c, cols, ncols, 0, 0, [](Fr*) {});
+        unsigned long long* cnt = (unsigned long long*)c->lkp.p;
+        CommitBatch a{};
+        a.cols = d.cols;
+        a.bases = (const G1Affine*)bases;
+        a.windows = (G1Xyzz*)(ws + o_win);
+        a.slots = (G1Xyzz*)(ws + o_slots);
+        a.buckets = (G1Xyzz*)(ws + o_bkt);
+        a.chunks = (G1Xyzz*)(ws + o_chk);
+        a.sorted = (uint32_t*)(ws + o_sorted);
+        a.cursor = (uint32_t*)(ws + o_cur);
+        a.start = (uint32_t*)(ws + o_start);
+        a.cnt = cnt;
+        a.k = k;
+        a.c = cb;
+        a.W = W;
+        a.ncols = ncols;
+        a.form = form;
+        a.bases_form = bases_form;
+        for (uint64_t g0 = 0; g0 < tasks; g0 += T) {
+            a.g0 = (uint32_t)g0;
+            a.T = (uint32_t)std::min<uint64_t>(T, tasks - g0);
+            profiled(c, "k_commit_batch", (32.0 + 64.0) * a.T * (double)n,
+                     [&] { return launch_commit_batch(a, c->st); });
+        }
+        profiled(c, "k_commit_horner", 128.0 * tasks, [&] {
+            return launch_commit_horner(a.windows, ncols, cb, W, bases_form, (G1Affine*)out, cnt, c->st);
+        });
+        unsigned long long h[3];
+        read_counters(c, cnt, h, 3);
+        result->columns = ncols;
+        result->zero_scalars = h[0];
+        result->identity_bases = h[1];
+        result->identity_outputs = h[2];
+    });
+}
+int svdw_check_commit(svdw_ctx* c, uint32_t k, int form, int bases_form, const void* bases, const void* const* cols,
+                      uint32_t ncols, const void* commitments, svdw_commit_check* result) {
+    return guarded([&] {
+        REQUIRE(result, "null argument");
+        const bool any =
+            commit_args(c, "svdw_check_commit", k, form, bases_form, bases, cols, ncols, commitments, false);
+        memset(result, 0, sizeof *result);
+        if (!any) return;
+        sync(c);
+        const uint64_t n = 1ull << k;
+        const size_t per = (size_t)kCommitScalarBits * commit_check_blocks(n) * sizeof(G1Xyzz);
+        const uint32_t chunk = (uint32_t)std::min<size_t>(std::max<size_t>(((size_t)64 << 20) / per, 1), ncols);   // 64 MiB of partials
+        const NttDev d = ntt_stage(c, cols, ncols, 0, chunk * per, [](Fr*) {});
+        unsigned long long* cnt = (unsigned long long*)c->lkp.p;
+        profiled(c, "k_commit_check_bases", 64.0 * (double)n,
+                 [&] { return launch_commit_check_bases((const G1Affine*)bases, n, bases_form, cnt, c->st); });
+        for (uint32_t c0 = 0; c0 < ncols; c0 += chunk) {
+            const uint32_t nc = std::min(chunk, ncols - c0);
+            profiled(c, "k_commit_check", 254.0 * nc * (double)n * 32.0, [&] {
+                return launch_commit_check(d.cols, (const G1Affine*)bases, (const G1Affine*)commitments, k, c0, nc,
+                                           form, bases_form, (G1Xyzz*)d.free, cnt, c->st);
+            });
+        }
+        unsigned long long h[4];
+        read_counters(c, cnt, h, 4);
+        result->columns_checked = h[0];
+        result->commit_failures = h[1];
+        result->bases_checked = h[2];
+        result->bases_off_curve = h[3];
+    });
+}
+// A probe of the mixed-add rate: `threads` threads each add one affine point
+// `reps` times into a register-resident accumulator; the seconds of the launch.
+int svdw_commit_add_probe(svdw_ctx* c, const void* points, uint32_t npoints, uint64_t threads, uint32_t reps,
+                          double* seconds) {
+    return guarded([&] {
+        REQUIRE(c && points && seconds && npoints && threads && reps, "null argument");
+        REQUIRE(!c->dry, "svdw_commit_add_probe needs a device context");
+        sync(c);
+        ensure_buf(c, c->commit_ws, threads * sizeof(G1Xyzz));
+        hipEvent_t e0, e1;
+        hipck(hipEventCreate(&e0), "hipEventCreate");
+        hipck(hipEventCreate(&e1), "hipEventCreate");
+        hipck(hipEventRecord(e0, c->st), "hipEventRecord");
+        const hipError_t le = launch_commit_add_probe((const G1Affine*)points, npoints, threads, reps,
+                                                      (G1Xyzz*)c->commit_ws.p, c->st);
+        hipError_t re = hipEventRecord(e1, c->st);
+        if (re == hipSuccess) re = hipEventSynchronize(e1);
+        float ms = 0;
+        if (re == hipSuccess) re = hipEventElapsedTime(&ms, e0, e1);
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        hipck(le, "k_commit_add_probe");
+        hipck(re, "hipEventElapsedTime");
+        *seconds = ms * 1e-3;
     });
 }
 // ---- the quotient polynomial on the extended domain and the verifier's identity

@@ -20,7 +20,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import (CheckResult, EqCheck, LookupCheck, LookupProductCheck, LookupProductResult, LookupResult, NttCheck, NttResult, PermutationProductCheck, PermutationProductResult, PhysParams, QuotientArgs, QuotientCheck, QuotientResult, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SvdwError,
+from ._lib import (CheckResult, CommitCheck, CommitResult, EqCheck, LookupCheck, LookupProductCheck, LookupProductResult, LookupResult, NttCheck, NttResult, PermutationProductCheck, PermutationProductResult, PhysParams, QuotientArgs, QuotientCheck, QuotientResult, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SvdwError,
                    Vec, check, lib)
 
 P_MOD = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -29,7 +29,8 @@ __all__ = ["Context", "ZkMatrix", "ZkVector", "honest_prover_mat_mul", "field_ma
            "mat_times_diag_mat", "check_mat_diff", "check_mat_id", "check_mat_entries_bounded",
            "check_svd_phase0", "check_svd_phase1", "err_calc", "svd_witness", "plan_svd",
            "SvdwError", "SvdPayload", "SvdConfigPy", "P_MOD", "int_to_words", "words_to_int",
-           "fr_convert", "quantization", "dequantization", "format_f64_debug", "permutation_constants"]
+           "fr_convert", "quantization", "dequantization", "format_f64_debug", "permutation_constants",
+           "commit_plan"]
 
 
 def int_to_words(x: int) -> np.ndarray:
@@ -93,6 +94,13 @@ def permutation_constants(k: int):
     d, w = (ct.c_uint64 * 4)(), (ct.c_uint64 * 4)()
     check(lib().svdw_permutation_constants(k, d, w))
     return words_to_int(d), words_to_int(w)
+
+
+def commit_plan(k: int) -> tuple:
+    """(window_bits, windows) of a size-2^k commitment (svdw_commit_plan)."""
+    c, w = ct.c_uint32(), ct.c_uint32()
+    lib().svdw_commit_plan(k, ct.byref(c), ct.byref(w))
+    return c.value, w.value
 
 
 def quantization(x: float, precision_bits: int) -> int:
@@ -796,6 +804,67 @@ class Context:
         check(lib().svdw_check_ntt(self._h, k_in, k, _form(form), 1 if inverse else 0, sh, cp, n,
                                    out.data_ptr() if n else None, log_samples, seed & _M64, ct.byref(r)))
         return {"rows_checked": r.rows_checked, "row_failures": r.row_failures}
+
+    # ---- commitments (include/svdw.h, "commitments"; parity unpinned)
+    def _commit_args(self, columns, bases, k: int):
+        import torch
+        rows = 1 << k if 0 <= k < 32 else 0
+        cp, n, dev = self._column_pointers("columns", columns, rows)
+        if (not isinstance(bases, torch.Tensor) or not bases.is_cuda or bases.dtype != torch.uint8
+                or not bases.is_contiguous() or tuple(bases.shape) != (rows, 64)):
+            raise SvdwError(-1, "bases must be a contiguous uint8 device tensor [2^k, 64]")
+        return cp, n, dev or bases.device
+
+    def commit(self, columns, bases, k: int, form: str = "canonical", bases_form: str = "montgomery", out=None):
+        """(points, result): the KZG commitments sum_i s_i P_i of columns of 2^k
+        cells in `form` over the 2^k G1 bases (svdw_commit), a [ncols, 64] u8
+        device tensor of affine points (x, y; (0, 0) the identity) in bases_form.
+        bases: a [2^k, 64] u8 device tensor in bases_form; "montgomery" is what
+        srs.read_srs returns. columns: a tensor [n, 2^k, 32] u8 or a list of such
+        tensors, so h_coeffs.view(E, 2**k, 32) commits the E pieces of h of
+        2^k coefficients each in one call. result: columns, window_bits,
+        windows, rows, zero_scalars, identity_bases, identity_outputs."""
+        import torch
+        cp, n, dev = self._commit_args(columns, bases, k)
+        if out is None:
+            out = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+        if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.uint8
+                or not out.is_contiguous() or tuple(out.shape) != (n, 64)):
+            raise SvdwError(-1, "out must be a contiguous uint8 device tensor [ncols, 64]")
+        r = CommitResult()
+        _after_torch(self)
+        check(lib().svdw_commit(self._h, k, _form(form), _form(bases_form), bases.data_ptr(), cp, n,
+                                out.data_ptr() if n else None, ct.byref(r)))
+        _before_torch(self)
+        return out, {k_: getattr(r, k_) for k_, _ in CommitResult._fields_}
+
+    def commit_lagrange(self, columns, g_lagrange, k: int, form: str = "canonical", out=None):
+        """ParamsKZG::commit_lagrange of every column (cells in Lagrange form) on
+        the SRS's g_lagrange as read_srs returns it. No blinding term: as far as
+        recalled the reference ignores its Blind argument (unpinned)."""
+        return self.commit(columns, g_lagrange, k, form=form, out=out)
+
+    def commit_coeffs(self, columns, g, k: int, form: str = "canonical", out=None):
+        """ParamsKZG::commit of every column (cells in coefficient form) on the
+        SRS's g as read_srs returns it; the blinding note of commit_lagrange holds."""
+        return self.commit(columns, g, k, form=form, out=out)
+
+    def check_commit(self, columns, bases, commitments, k: int, form: str = "canonical",
+                     bases_form: str = "montgomery") -> dict:
+        """Device check of commitments [ncols, 64] u8 in bases_form against the
+        columns and the bases, bit-serial and division-free, sharing nothing with
+        commit (svdw_check_commit): columns_checked, commit_failures,
+        bases_checked, bases_off_curve."""
+        import torch
+        cp, n, _ = self._commit_args(columns, bases, k)
+        if (not isinstance(commitments, torch.Tensor) or not commitments.is_cuda or commitments.dtype != torch.uint8
+                or not commitments.is_contiguous() or tuple(commitments.shape) != (n, 64)):
+            raise SvdwError(-1, "commitments must be a contiguous uint8 device tensor [ncols, 64]")
+        r = CommitCheck()
+        _after_torch(self)
+        check(lib().svdw_check_commit(self._h, k, _form(form), _form(bases_form), bases.data_ptr(), cp, n,
+                                      commitments.data_ptr() if n else None, ct.byref(r)))
+        return {k_: getattr(r, k_) for k_, _ in CommitCheck._fields_}
 
     # ---- quotient polynomial (include/svdw.h, "quotient"; parity unpinned)
     _QUOTIENT_FAMILIES = ("advice", "selectors", "perm_columns", "sigma", "perm_z", "lookup_input", "lookup_table",

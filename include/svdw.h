@@ -335,6 +335,10 @@ int svdw_set_gemm_impl(svdw_ctx* ctx, int impl);
  *   phase-0 stages, 3 after all of phase 0; -1: 0 on a rank of a >= 4-way shard, 3 of a
  *   2-3-way shard, else 1);
  *   "stage_elems" 256 (elements per stage block, multiple of 16 in [16, 256]);
+ *   "commit_window_bits" 0 | 2..16 (svdw_commit's window instead of
+ *   svdw_commit_plan's, a tuning aid; the result reports what was used);
+ *   "commit_scratch_mib" 1024 | 1..65536 (svdw_commit's workspace cap per batch
+ *   of (column, window) tasks, MiB; one task always runs);
  *   "place_trials" 6 | 0..8 (a cell stream of >= 256 MiB allocated from now on
  *   is chosen among that many placements in HBM by timing the stage kernels'
  *   store pattern on each; 0 or 1: the first one);
@@ -924,6 +928,72 @@ typedef struct {
  * family: SVDW_OK, nothing is evaluated and the result is zero. */
 int svdw_check_quotient(svdw_ctx* ctx, const svdw_quotient_args* coeffs, const void* h_coeffs,
                         const uint64_t x[4], svdw_quotient_check* result);
+/* ------------------------------------------------------------- commitments
+ * KZG commitments of columns on the device: for each column of 2^k BN254 Fr
+ * cells s_i the multi-scalar multiplication sum_i s_i P_i over 2^k shared G1
+ * bases, as halo2_proofs' ParamsKZG::commit_lagrange (bases = g_lagrange, the
+ * column in Lagrange form) and ::commit (bases = g, coefficient form) compute
+ * with best_multiexp. Restated from memory like the steps above (PARITY
+ * UNPINNED for the calls; the SRS layout below is pinned by the reference's
+ * params/kzg_bn254_8.srs, tests/golden). No blinding term is added: as far as
+ * recalled commit_lagrange ignores its Blind argument (unpinned). These calls
+ * need no witness and no physical layout.
+ *
+ * A G1 point is 64 bytes: x then y, each a 32-byte little-endian Fq
+ * (q = 21888242871839275222246405745257275088696311157297823662689037894645226208583),
+ * on y^2 = x^3 + 3; (0, 0) is the identity. bases_form says how the
+ * coordinates of the bases and of the commitments are held:
+ * SVDW_FORM_MONTGOMERY is halo2curves' in-memory G1Affine (x 2^256 mod q), which
+ * is what an SRS file holds (u32 k, 2^k points g, 2^k points g_lagrange, G2);
+ * SVDW_FORM_CANONICAL the plain integers. `form` is the cells' form as
+ * everywhere else. Cells are taken as integers below p; identity bases and
+ * zero cells are skipped. */
+typedef struct {
+    uint32_t columns;
+    uint32_t window_bits, windows;   /* svdw_commit_plan(k) */
+    uint64_t rows;                   /* 2^k */
+    uint64_t zero_scalars;           /* cells equal to 0, over the columns */
+    uint64_t identity_bases;         /* bases equal to (0, 0) */
+    uint64_t identity_outputs;       /* commitments that are the identity, written as (0, 0) */
+} svdw_commit_result;
+/* Host only: the Pippenger window of a size-2^k commitment (k clamped to
+ * 1..28): window_bits = c, non-decreasing in k, and windows = ceil(255 / c)
+ * signed digits per cell. Either pointer may be null. */
+void svdw_commit_plan(uint32_t k, uint32_t* window_bits, uint32_t* windows);
+/* bases: DEVICE, 2^k points in bases_form. cols: HOST array of ncols DEVICE
+ * pointers, each to 2^k cells in `form`. out: DEVICE, ncols points in
+ * bases_form. The checks of the arguments come first, before anything touches
+ * the device, in this order: an unknown form or bases_form (SVDW_EINVAL), k
+ * outside 1..28 (SVDW_ERANGE), a planning context (SVDW_EINVAL), more than 65535
+ * columns (SVDW_ERANGE), null pointers (SVDW_EINVAL), an out that overlaps the
+ * bases or an input column (SVDW_EINVAL). ncols == 0: SVDW_OK, nothing is
+ * touched (window_bits, windows and rows are still reported). Every kernel is
+ * queued on the context's streams like svdw_ntt, with no host wait between
+ * them; like the grand products the call returns once the three counters of
+ * the result have been read back. Scratch is the engine's: the window sums
+ * and one batch of (column, window) tasks at a time, a batch kept under
+ * 1 GiB (option "commit_scratch_mib") unless a single task needs more: about
+ * 21 B per row and 136 B per bucket, 2^(window_bits - 1) buckets, per task. */
+int svdw_commit(svdw_ctx* ctx, uint32_t k, int form, int bases_form, const void* bases, const void* const* cols,
+                uint32_t ncols, void* out, svdw_commit_result* result);
+typedef struct {
+    uint64_t columns_checked, commit_failures;
+    uint64_t bases_checked, bases_off_curve;   /* neither (0, 0) nor on y^2 = x^3 + 3, or a coordinate >= q */
+} svdw_commit_check;
+/* commitments (DEVICE, ncols points in bases_form) against the same inputs,
+ * independently of svdw_commit: no windows, no sort, no buckets. For each of
+ * the 254 bits b the bases whose cell has bit b set are tree-summed, Horner
+ * over the bits (one doubling each) gives the sum, and it is compared with the
+ * given affine point cross-multiplied, without a division. Arguments and
+ * their checks as for svdw_commit (there is no output to overlap); it writes
+ * to none of its inputs and returns after the device has finished. */
+int svdw_check_commit(svdw_ctx* ctx, uint32_t k, int form, int bases_form, const void* bases,
+                      const void* const* cols, uint32_t ncols, const void* commitments, svdw_commit_check* result);
+/* A measurement probe (tools/commit_bench.py): `threads` device threads each
+ * add one of the npoints Montgomery affine points (DEVICE) `reps` times into a
+ * register-resident accumulator; *seconds is the launch's device time. */
+int svdw_commit_add_probe(svdw_ctx* ctx, const void* points, uint32_t npoints, uint64_t threads, uint32_t reps,
+                          double* seconds);
 /* Up to cap segments of the last witness into out; *n = total count. */
 int svdw_shard_segments(const svdw_ctx* ctx, svdw_segment* out, uint64_t cap, uint64_t* n);
 
