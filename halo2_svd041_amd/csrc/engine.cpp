@@ -1,4 +1,8 @@
-// Host engine + C ABI (include/svdw.h) of the SVD-verify witness engine.
+// Host engine + C ABI (include/svdw.h) of the SVD-verify witness engine: the
+// context, the witness calls, the physical layout and its checks, read-out.
+// The prover calls on an assigned witness (lookup argument, grand products,
+// transforms, commitments, quotient) are in prover.cpp; engine_internal.hpp
+// holds what the two files share, the definition of svdw_ctx included.
 //
 // Each reference function (src/matrix/mod.rs, src/svd/mod.rs) becomes:
 //   1. a data-independent cell program built on the host by replaying the
@@ -9,80 +13,25 @@
 // asynchronous on the context's HIP stream. A context created with
 // device = -1 is a "dry" planner: identical control flow, no device work,
 // which is how svdw_plan_svd gets exact closed-form counts.
-#include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
-#include <chrono>
-#include <array>
-#include <functional>
-#include <set>
-#include <stdexcept>
-#include <string>
-#include <tuple>
-#include <vector>
 
-#include "../../include/svdw.h"
+#include "engine_internal.hpp"
 #include "ingest.hpp"
 #include "ingest_dev.hpp"
-#include "kernels.hpp"
 #include "export.hpp"
-#include "lookup.hpp"
-#include "lookup_product.hpp"
-#include "ntt.hpp"
-#include "commit.hpp"
-#include "quotient.hpp"
-#include "permutation_product.hpp"
-
-using namespace svdw;
-
-// ------------------------------------------------------------------ errors
-static thread_local std::string g_err;
-struct SvdwError {
-    int code;
-    std::string msg;
-};
-[[noreturn]] static void fail(int code, const std::string& msg) { throw SvdwError{code, msg}; }
-static void hipck(hipError_t e, const char* what) {
-    if (e != hipSuccess) fail(SVDW_EDEVICE, std::string(what) + ": " + hipGetErrorString(e));
-}
-template <class F>
-static int guarded(F&& f) {
-    try {
-        f();
-        return SVDW_OK;
-    } catch (const SvdwError& e) {
-        g_err = e.msg;
-        return e.code;
-    } catch (const std::bad_alloc&) {
-        g_err = "out of host memory";
-        return SVDW_ENOMEM;
-    } catch (const std::exception& e) {
-        g_err = e.what();
-        return SVDW_EINVAL;
-    }
-}
-#define REQUIRE(cond, msg) \
-    do {                   \
-        if (!(cond)) fail(SVDW_EINVAL, msg); \
-    } while (0)
+#include "commit.hpp"                                       // kCommitMaxBits, for the "commit_window_bits" option
 
 // ------------------------------------------------------- host big integers
 // Unsigned 256-bit integers (BigUint bounds of the range checks).
 struct BigU {
     Fr v;
 };
-static BigU big_from_words(const uint64_t w[4]) {
-    BigU b;
-    for (int i = 0; i < 4; ++i) {
-        b.v.w[2 * i] = (uint32_t)w[i];
-        b.v.w[2 * i + 1] = (uint32_t)(w[i] >> 32);
-    }
-    return b;
-}
+static BigU big_from_words(const uint64_t w[4]) { return BigU{fr_raw_words(w)}; }
 static BigU big_from_u128(unsigned __int128 x) {
     BigU b;
     b.v = fr_zero();
@@ -391,341 +340,12 @@ struct PB {
     }
 };
 
-// -------------------------------------------------------------- context
-struct DBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-};
-struct Stream {
-    Fr* adv = nullptr;
-    uint64_t n = 0, cap = 0;
-    Fr* lk = nullptr;
-    uint64_t nl = 0, lcap = 0;
-};
-struct svdw_ctx {
-    // ---- options: svdw_set_option (kOptions), svdw_set_gemm_impl, svdw_set_shard,
-    // the profiler switches; a lane takes them over as a whole (copy_settings)
-    struct Options {
-        int gemm_impl = SVDW_GEMM_MFMA;         // svdw_set_gemm_impl
-        // STAGE_* (4 KiB-aligned block store windows; "stage_rot" 1: phase B from a
-        // block-dependent window on, tools/r6/place_ab.py over 8 placements of the
-        // 1024^2 cell streams: 1.739-1.891 -> 1.728-1.825 ms, mean 1.815 -> 1.751)
-        uint32_t stage_flags = STAGE_ALIGN | STAGE_ROT;
-        uint32_t stage_elems = kStageElems;     // "stage_elems": elements per stage block (16..256)
-        int gemm_crt = 1;                       // "gemm_crt": multi-modular GEMM (else digits)
-        // "gemm_kern": CRT GEMM kernel (CrtBatch::kern); -1: wide tiles or the
-        // persistent grid for a product queued on its own (svdw_honest_prover_mat_mul,
-        // gemm_solo; CrtBatch::kern 3), one block per unit inside the witness calls,
-        // beside their stage kernels
-        int gemm_kern = -1;
-        int res_wait = -1;                      // "res_wait": stages wait for the residue planes
-        int place_trials = 6;                   // "place_trials": candidate placements of a new cell stream
-        bool res_f64 = true;                    // "res_f64": CRT residue planes of m, u, v from the
-                                                // f64 inputs, one launch (else from the cells)
-        int phase1_overlap = 1;                 // "phase1_overlap": 0 off, 1 on st2 behind the
-                                                // GEMMs, 2 on st3 from quantization on
-        int prod_cell = 1;                      // "prod_cell": svd_witness's products (residues, GEMM,
-                                                // combine) on the cell stream and the u / v bounds and
-                                                // u.d beside them on st2 (1), not (0); -1: on row-sharded
-                                                // ranks only. On by default: the product chain is the
-                                                // critical path sharded, and unsharded it measured
-                                                // 2.5 % faster at 1024^2 and 2048^2, neutral at 512^2
-        uint32_t hold_us = 0;                   // "hold_us": timing aid, st spins this long first
-        uint32_t commit_window_bits = 0;        // "commit_window_bits": svdw_commit's window, 0: svdw_commit_plan's
-                                                // (a tuning aid, tools/commit_bench.py; the result reports it)
-        uint32_t commit_scratch_mib = 1024;     // "commit_scratch_mib": svdw_commit's workspace cap per batch of tasks
-        bool rlc_prefix = false;                // "rlc_prefix": svd_witness's phase 1 starts with the
-                                                // ctx_gate cells of load_rlc_cache(.., 1)
-        int p1_at = -1;                         // "p1_at": phase 1 on st3 (mode 2) enqueued after
-                                                // phase-0 stage 0 / 1 / 2 (the u, v bounds), 3: at the
-                                                // end; -1: auto (tools/shard_sim.py --opt p1_at=):
-                                                // 0 on a rank of >= 4, 3 of 2-3, else 1
-        // pipelined svd_witness: "dchk_at" the d checks on the cell stream behind
-        // the products (0), on st2 with the bounds and u.d (1) or on st3 ahead of
-        // phase 1 (2); "gamma_at" k_gamma_prep at the head of the cell stream (0) or
-        // of st3 (1); -1: st3 on a row-sharded rank, whose cell stream (quantize ->
-        // residues -> GEMM -> combine, then the diff on st2) is the step's chain
-        // (8-way rank 0.331 -> 0.316-0.321 ms; 1024^2 / 512^2 +0.5 %, r5p / r5q)
-        int dchk_at = 0, gamma_at = -1;
-        bool f64_views = true;                  // "f64_views": launches read registered f64 inputs (f64_view)
-        bool overlap = true;                    // "overlap": products queued ahead of the check stages
-        bool stage_batch = true;                // "stage_batch": stage launches share k_stage_multi (BatchScope)
-        int graph_vm = 1;                       // "graph": 0 off, 1 verify_mul_witness captured (vm_graph)
-        // "vm_linear": the captured verify_mul_witness runs on the context stream
-        // alone (st2 = st3 = st while it is queued: a linear graph, no fork / join
-        // events); concurrency comes from the two lanes instead.
-        int vm_linear = 1;
-        int pipeline = 1;                       // "pipeline": 1 on, 0 off (svd_witness_pipe, below)
-        // Row-block sharding of one witness: this context computes the
-        // rows [R rank / world, R (rank + 1) / world) of every row-parallel stage
-        // (R = that stage's row count) into the globally laid-out streams; shared
-        // inputs (quantized operands, single constants, the Freivalds b.g values)
-        // are computed in full. `owned` lists the cell ranges this rank is the
-        // source of, for reassembly.
-        uint32_t shard_rank = 0, shard_world = 1;
-        // built-in event profiler (svdw_profile_*): one start/stop event pair per launch
-        bool prof = false;
-        std::string prof_filter;                // record only kernels whose name starts with this
-        // SVDW_HOST_TRACE=1: host-side timestamps of svd_witness's enqueue points on
-        // stderr (µs since the call started), to find host waits inside a call
-        bool host_trace = false;
-        auto tied() const {
-            return std::tie(gemm_impl, stage_flags, stage_elems, gemm_crt, gemm_kern, res_wait, place_trials,
-                            res_f64, phase1_overlap, prod_cell, hold_us, rlc_prefix, p1_at, dchk_at, gamma_at,
-                            f64_views, overlap, stage_batch, graph_vm, vm_linear, pipeline, shard_rank,
-                            shard_world, prof, prof_filter, host_trace);
-        }
-        bool operator==(const Options& o) const { return tied() == o.tied(); }
-    } opt;
-    // ---- one witness call (svd_witness, verify_mul_witness): meaningful while the
-    // call is being enqueued. Each call sets it from scratch (begin_call, then the
-    // call's own code); CallEnd drops what must not outlive the call.
-    struct PreGemm {
-        uint64_t off;
-        hipEvent_t ev;
-        hipStream_t st;                     // the stream it was launched on
-    };
-    // svd_witness's quantized matrices and their device f64 inputs (u, v): a
-    // row-sharded rank takes b.g of b = u^T, v^T from the f64 rows directly
-    // (k_colsum_f64), not from cells. Cleared at the end of the witness.
-    struct F64Src { svdw_mat m; const double* x; };
-    // loaded regions whose f64 source is on the device for the current call:
-    // launches read them through VIEW_F64 (quantized in registers) instead of
-    // waiting for the quantized cells (f64_view)
-    struct F64Region { uint32_t phase; uint64_t off, n; const double* x; };
-    struct Call {
-        bool in_pipe = false;                   // inside a pipelined svd_witness
-        bool prelaunched = false;               // this witness's products were queued on st2
-        bool prod_on_cell = false;              // this witness's products went on the cell stream
-        bool gemm_batched = false;              // this witness's products went out as one batch
-        std::vector<PreGemm> pre;               // GEMMs launched ahead on st2, in append order
-        hipStream_t pre_wait_st = nullptr;      // the last (stream, event) waited on for them
-        hipEvent_t pre_wait_ev = nullptr;
-        std::vector<hipEvent_t> gemm_done;      // their completion events (this witness)
-        std::vector<hipEvent_t> wait_before_cs; // verify_mul_many: wait before the c_s scans
-        const double* svd_f64[3] = {nullptr, nullptr, nullptr};   // device f64 m, u, v of svd_witness
-        std::vector<F64Region> f64reg;
-        std::vector<F64Src> f64src;
-        std::function<void(const svdw_svd_payload&)> early_p1;   // phase 1's enqueue at p1_at (svd_witness)
-        bool stage_front = false;               // stage_launch: the stage goes ahead of the batch's groups
-        // verify_mul_witness: the one cell and gamma powers written by k_gamma_prep
-        // (phase-1 offsets one_off / pows_off for d), so verify_mul does not launch them
-        struct PowsPre {
-            bool on = false;
-            uint64_t one_off = 0, pows_off = 0;
-            uint32_t d = 0;
-        } pows_pre;
-        // the captured verify_mul_witness (vm_graph): `linear` is set while a
-        // vm_linear call is queued (stream_dep returns lin_ev, never recorded, and
-        // dep_wait skips it)
-        bool linear = false;
-        bool capturing = false;                 // st is capturing: no allocation, no sync
-        bool gp_external = false;               // k_gamma_prep already queued ahead of the graph
-        const Fr* gp_ext_one = nullptr;         // the one cell it wrote (null: none)
-    } call;
-    // ---- the handle: parameters, streams, cells, caches, scratch
-    std::chrono::steady_clock::time_point ht0;   // host_trace: when the call started
-    int device = -1;
-    bool dry = true;
-    hipStream_t st = nullptr;
-    uint32_t P = 32, LB = 19;
-    Stream ph[2];
-    // Pipelined svd_witness ("pipeline", svd_witness_pipe): consecutive
-    // witnesses alternate between two sets of cell streams (ph and alt), so call
-    // j's product chain (st) runs beside call j - 1's HBM-bound stages (st2) and
-    // row scans (st3) instead of after them. Call j's st first waits for call
-    // j - 2's tail (tail_ev[parity]: its last work on st2 / st3), the last user
-    // of this cell set and of this half of the bit-length words. Anything else
-    // that touches the streams after a pipelined call settles first (settle).
-    Stream alt[2];
-    int pipe_par = 0;                       // this call's parity (cell set, bit words)
-    hipEvent_t tail_ev[2][2] = {};          // [parity][st2, st3]
-    bool tail_valid[2] = {false, false};
-    bool tail_pending = false;              // the last pipelined call's tail not yet joined into st
-    int tail_last = 0;
-    size_t mem_total = 0;                   // device memory (hipMemGetInfo at create)
-    // "lanes" 2: svdw_verify_mul_witness on its captured-graph path alternates
-    // between two complete context states, this one and `lane` (own streams,
-    // cells, scratch, graph). The states are exchanged (std::swap) at the start
-    // of a call, so call j + 1 runs on the other state's streams beside call j
-    // and the handle always holds the latest call's cells. sync, stream_wait,
-    // stream_signal, graph_stats and destroy cover both; lane / lanes stay with
-    // the handle.
-    int lanes = 2;                          // (config 2, same box: 0.081 -> 0.058 ms per call)
-    svdw_ctx* lane = nullptr;
-    // svdw_stream_wait's event (the caller's stream), not yet waited on by
-    // st2 / st3: st waits at once; the side streams inherit it through
-    // after_previous or the captured graph's fork from st, and the pipelined
-    // svd_witness (whose side streams do not wait for st) waits explicitly
-    hipEvent_t xwait_side = nullptr;
-    DBuf f64in, digA, digB, digC, w1c, w1t, w2c, w2t, bits, gpc, gtab, crtR, gbits, chk, chkg;
-    DBuf gpc_alt, gtab_alt;                 // pipelined svd_witness: gamma tables of the other parity
-    DBuf wbc[kMaxScanJobs], wbt[kMaxScanJobs];   // b.v per batched verify_mul (canonical, table)
-    // gamma^j (canonical gpc, scaled table gtab, kernels.hpp kTabSlots) of the
-    // current verify_mul calls: recomputed for every witness (a fresh challenge
-    // each time). svd_witness queues it first thing on a side stream (gp_ev).
-    Fr gp_gamma{};
-    uint32_t gp_len = 0;
-    hipEvent_t gp_ev = nullptr;
-    hipStream_t gp_st = nullptr;            // the stream gp_ev was recorded on
-    // Device bit-length words of matrices written in this witness (svd_witness:
-    // quantized m, u, v at dbitw[0..2]): the row scans decide their operand
-    // width on the device from these (NaSpec), so the host never waits for them.
-    struct DevBits { svdw_mat m; int16_t word; };
-    std::vector<DevBits> dwords;
-    const unsigned* dbitw = nullptr;
-    // Known magnitude bounds of matrices written in this witness: cell (i, j) of
-    // `m` satisfies |signed value| < 2^bits. Cleared with the streams.
-    struct MatBits { svdw_mat m; uint32_t bits; };
-    std::vector<MatBits> mbits;
-    // products c_s = a * b (K = 2^lk-bounded inner dimension): |c_s| < 2^(bits_a + bits_b + lk)
-    struct Prod { svdw_mat cs, a, b; uint32_t lk; };
-    std::vector<Prod> prods;
-    // svd_witness: bit lengths of quantized m, u, v travel to pinned host memory
-    // behind ev_bits; the host waits for them only where the GEMM launches need
-    // them (fetch_bits), with check stages already queued on the device.
-    uint32_t* hbits = nullptr;
-    hipEvent_t ev_bits = nullptr;
-    bool bits_pending = false;
-    uint32_t qbits[3] = {0, 0, 0};
-    svdw_mat qmat[3] = {};
-    // the event profiler's records (opt.prof): one start/stop event pair per launch
-    struct Rec {
-        std::string name;
-        double bytes, ops;
-        hipEvent_t e0, e1;
-    };
-    std::vector<Rec> recs;
-    std::vector<hipEvent_t> pool;
-    hipStream_t stream_id[3] = {};          // st, st2, st3 as created (st / st2 / st3 are swapped at times)
-    bool gemm_solo = false;                 // svdw_honest_prover_mat_mul: a product queued on its own (gemm_kern)
-    Fr ext_gamma{};                          // init_rand of the last verify_mul (equality source 2)
-    uint64_t ext_off = 0;                    // its cell in the RLC context
-    // ctx_rlc of the last svd_witness with rlc_prefix: [E(one), E(zero), W(gamma)]
-    // and the phase-1 offsets of the two ctx_gate constants its first cells copy
-    struct RlcTrace {
-        uint32_t n = 0;
-        Fr cells[3];
-        uint64_t src[2];
-    } rlc;
-    // Host-side replays cached for repeated calls of the same shape: the dry
-    // plan of svd_witness's stream sizes (key: N, M, config) and prelaunch's
-    // product offsets (key: stream state at entry, operand views, bounds).
-    std::vector<uint64_t> plan_key, plan_val, log_key, log_val;
-    struct Seg { uint32_t phase, lookup; uint64_t off, n; };
-    std::vector<Seg> owned;                 // row-sharded: the cell ranges this rank is the source of
-    DBuf bvfull[kMaxScanJobs];              // shard mode: full b.g values per verify_mul
-    DBuf colpart;
-    DBuf qfold;                             // k_quantize_multi's fold counters + group maxima
-    // second stream: GEMMs overlap the HBM-bound stages; third: phase 1
-    hipStream_t st2 = nullptr;
-    hipStream_t st3 = nullptr;
-    hipStream_t st_cell = nullptr;          // the cell stream proper (st is swapped at times)
-    hipEvent_t xev[4] = {};                 // svdw_stream_wait / _signal (caller's stream)
-    // svdw_mark ring: slot k holds ticket t[k]'s events (one per stream of
-    // both lanes), recorded on the context's own streams (no waits); it stays
-    // with the handle when lanes exchange states (lane_switch)
-    static constexpr int kMarks = 16;
-    struct Marks {
-        hipEvent_t ev[kMarks][6] = {};
-        uint64_t t[kMarks] = {};
-        uint8_t used[kMarks] = {};
-        uint64_t seq = 0;
-    } mk;
-    std::vector<svdw_region> layout;        // every appended region of the current witness
-    // per region: gate offsets within one element's cells and cells per element
-    // (program regions; empty otherwise; svdw_check_gates)
-    std::vector<RegionChecks> layout_chk;
-    // distinct constant cell values (halo2-base Constant / load_constant):
-    // the fixed-column count of svdw_physical_layout
-    std::set<std::array<uint32_t, 8>> consts;
-    // svdw_physical_layout's plan: per phase, the virtual index of each advice
-    // column's row 0 and each full column's break point
-    struct Phys {
-        bool valid = false;
-        uint32_t k = 0, min_rows = 0;
-        uint64_t R = 0;
-        std::vector<uint64_t> start[2], bp[2];
-    } phys;
-    DBuf gateq[2];
-    std::vector<uint64_t>* gemm_log = nullptr;   // dry run: offsets of honest_prover_mat_mul
-    std::vector<hipEvent_t> deps;           // dependency events (no timing)
-    size_t dep_next = 0;
-    // Stage batches (BatchScope, "stage_batch"): stage launches on a stream with
-    // an open batch are collected and issued as k_stage_multi launches when the
-    // scope closes, when a stage reads cells a pending stage writes, or before
-    // anything else is recorded or launched on that stream.
-    struct Pending {
-        StageArgs a;
-        std::string name;
-        double bytes;
-    };
-    // A batch holds groups issued in order, one k_stage_multi launch each: a
-    // stage joins the group after the last one holding a stage whose cells it
-    // reads, so a dependent stage (entries_in_desc_order's range checks of its
-    // subtractions) defers only itself, not the independent stages after it.
-    struct Batch {
-        hipStream_t st;
-        std::vector<std::vector<Pending>> groups;
-        size_t last = 0;                   // group of the latest stage
-    };
-    std::vector<Batch> batches;
-    // device ingest (svdw_parse_svd_input_device) scratch
-    DBuf ing_x, ing_e, ing_c, ing_p10, ing_val, ing_npos, ing_nd, ing_rpos, ing_kpos, ing_err, ing_q;
-    // device equality records (eq_gen_device)
-    DBuf eq_cp, eq_ks, eq_reg, eq_w, eq_k, eq_err, eq_st;
-    // read-out (svdw_copy_cells, the host variants of svdw_export_* / svdw_dequantize_*):
-    // two staging halves of at most kExportChunk bytes each, and the events that
-    // order them ([0..1] half converted, [2..3] half copied out, [4..5] the join
-    // of st2 / st3 into st ahead of every read-out)
-    DBuf exp_buf[2];
-    DBuf lkp;                               // lookup argument: histograms, scans, counters (lookup.hpp)
-    std::vector<Fr> pp_w;                   // permutation argument: the omega tables of pp_k (permutation_product.hpp)
-    uint32_t pp_k = 0;
-    std::vector<char> pp_up;                // its staged upload: pointer, delta and omega tables
-    DBuf ntt_tab, ntt_tmp;                  // transforms (ntt.hpp): the stage and omega tables of ntt_k; the buffer
-    uint32_t ntt_k = 0;                     // between passes
-    DBuf commit_ws;                         // commitments (commit.hpp): the window sums and one batch of tasks
-    // quotient (quotient.hpp): the extended columns of l_0, l_last, l_active (R form) of the key below, and the
-    // scratch they are built in
-    DBuf q_l, q_tmp;
-    uint32_t q_k = 0, q_ek = 0, q_unusable = 0;
-    Fr q_shift{};
-    hipEvent_t exp_ev[6] = {};
-    // ---- captured verify_mul_witness ("graph", vm_graph): the launch sequence of
-    // a device-input call is captured once into a HIP graph (the second call of
-    // a shape, when every buffer is sized) and replayed by later calls of the
-    // same key; gamma enters only through k_gamma_prep, launched eagerly on st
-    // ahead of the graph (gp_external), so the graph itself is gamma-free.
-    hipEvent_t lin_ev = nullptr;            // "vm_linear": stream_dep's placeholder (call.linear)
-    uint64_t epoch = 0;                     // bumped by every allocation / option change
-    // (layout_chk index, eqk slot) of the constants that hold gamma (the
-    // verify_mul gamma powers' init_rand), patched on replay
-    std::vector<std::pair<size_t, int>> gamma_slots;
-    struct VmGraph {
-        std::vector<uint64_t> key, seen;    // replay key; the last eager call's key
-        hipGraphExec_t exec = nullptr;
-        // host state the captured call left behind (restored on replay)
-        std::vector<svdw_region> layout;
-        std::vector<RegionChecks> layout_chk;
-        std::set<std::array<uint32_t, 8>> consts;
-        std::vector<std::pair<size_t, int>> gamma_slots;
-        std::vector<MatBits> mbits;
-        std::vector<Prod> prods;
-        std::vector<DevBits> dwords;
-        const unsigned* dbitw = nullptr;
-        uint64_t ext_off = 0;
-        svdw_counts counts{};
-        uint64_t replays = 0, captures = 0;
-    } vmg;
-};
-
-static void flush_batch(svdw_ctx* c, hipStream_t s, hipStream_t waiter = nullptr, hipEvent_t then_wait = nullptr);
+// ------------------------------------- context (svdw_ctx: engine_internal.hpp)
 // debug logs (read once: getenv scans the environment)
 static bool env_flag(const char* name) { const char* v = getenv(name); return v && *v && *v != '0'; }
 static const bool g_batch_log = env_flag("SVDW_BATCH_LOG");
 static const bool g_stage_log = env_flag("SVDW_STAGE_LOG");
-static void sync(svdw_ctx* c) {
+void sync(svdw_ctx* c) {
     if (c->dry) return;
     REQUIRE(!c->call.capturing, "internal: synchronisation during graph capture");
     hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
@@ -852,7 +472,6 @@ static void fetch_bits(svdw_ctx* c) {
         reg_bits(c, c->qmat[i], c->qbits[i]);
     }
 }
-static bool sharded(const svdw_ctx* c) { return c->opt.shard_world > 1; }
 static void host_mark(svdw_ctx* c, const char* what) {
     if (!c->opt.host_trace || c->dry) return;
     const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - c->ht0).count();
@@ -881,56 +500,7 @@ static void clear_streams(svdw_ctx* c) {
     c->dbitw = nullptr;
     c->gamma_slots.clear();
 }
-// RAII: brackets one kernel launch with HIP events on the context stream.
-struct ProfScope {
-    svdw_ctx* c;
-    long idx = -1;
-    static hipEvent_t ev(svdw_ctx* c) {
-        if (!c->pool.empty()) {
-            hipEvent_t e = c->pool.back();
-            c->pool.pop_back();
-            return e;
-        }
-        // timing-only events: skip the system-scope fence (cache writeback and
-        // invalidate) a default event performs, which would perturb what it measures
-        hipEvent_t e;
-        hipck(hipEventCreateWithFlags(&e, hipEventDisableSystemFence), "hipEventCreate");
-        return e;
-    }
-    hipStream_t s = nullptr;
-    bool ext = false;                       // stage launches: events recorded by their dispatch
-    // stage: the scope holds stage launches only (launch_stage*), which record
-    // the events themselves (set_launch_events): no event records between the
-    // launches, which cost a few us of stream time each
-    ProfScope(svdw_ctx* cc, hipStream_t ss, const std::string& name, double bytes, double ops,
-              bool batch = false, bool stage = false)
-        : c(cc), s(ss) {
-        if (!batch) flush_batch(c, s);      // earlier batched stages go first
-        if (!c->opt.prof || c->dry) return;
-        if (!c->opt.prof_filter.empty() && name.compare(0, c->opt.prof_filter.size(), c->opt.prof_filter) != 0)
-            return;
-        // every launch is tagged with its stream (@cell, @s2, @s3 as created), so a
-        // bench can report the busiest stream's stage rate beside the all-stream one
-        const char* tag = s == c->stream_id[0] ? "@cell" : s == c->stream_id[1] ? "@s2"
-                          : s == c->stream_id[2] ? "@s3" : "";
-        svdw_ctx::Rec r{name + tag, bytes, ops, ev(c), ev(c)};
-        ext = stage;
-        if (ext)
-            set_launch_events(r.e0, r.e1);
-        else
-            hipck(hipEventRecord(r.e0, s), "hipEventRecord");
-        c->recs.push_back(r);
-        idx = (long)c->recs.size() - 1;
-    }
-    ~ProfScope() {
-        if (idx < 0) return;
-        if (ext && launch_events_used()) return;
-        if (ext) (void)hipEventRecord(c->recs[idx].e0, s);       // nothing launched: an empty interval
-        (void)hipEventRecord(c->recs[idx].e1, s);
-    }
-};
-
-static void ensure_buf(svdw_ctx* c, DBuf& b, size_t bytes) {
+void ensure_buf(svdw_ctx* c, DBuf& b, size_t bytes) {
     if (c->dry || b.cap >= bytes) return;
     REQUIRE(!c->call.capturing, "internal: allocation during graph capture");
     ++c->epoch;
@@ -1264,7 +834,7 @@ static void stage_launch(svdw_ctx* c, uint32_t phase, PB& pb, uint32_t nelem, ui
 // (it needs that stage and what came before on s, not the later groups: those
 // hold stages queued earlier that depend on other pending ones).
 // then_wait: s waits for this event before the groups after that point.
-static void flush_batch(svdw_ctx* c, hipStream_t s, hipStream_t waiter, hipEvent_t then_wait) {
+void flush_batch(svdw_ctx* c, hipStream_t s, hipStream_t waiter, hipEvent_t then_wait) {
     for (auto& b : c->batches) {
         if (b.st != s || b.groups.empty()) continue;
         std::vector<std::vector<svdw_ctx::Pending>> groups;
@@ -3294,8 +2864,8 @@ static std::vector<DBuf*> dbufs(svdw_ctx* c) {
                             &c->gtab_alt, &c->crtR, &c->gbits, &c->colpart, &c->qfold, &c->ing_x, &c->ing_e,
                             &c->ing_c, &c->ing_p10, &c->ing_val, &c->ing_npos, &c->ing_nd, &c->ing_rpos,
                             &c->ing_kpos, &c->ing_err, &c->ing_q, &c->eq_cp, &c->eq_ks, &c->eq_reg, &c->eq_w,
-                            &c->eq_k, &c->eq_err, &c->eq_st, &c->exp_buf[0], &c->exp_buf[1], &c->lkp, &c->ntt_tab,
-                            &c->ntt_tmp, &c->q_l, &c->q_tmp, &c->commit_ws};
+                            &c->eq_k, &c->eq_err, &c->eq_st, &c->exp_buf[0], &c->exp_buf[1]};
+    for (DBuf* d : c->prover.dbufs()) v.push_back(d);
     for (int i = 0; i < kMaxScanJobs; ++i) {
         v.push_back(&c->wbc[i]);
         v.push_back(&c->wbt[i]);
@@ -3947,10 +3517,6 @@ int svdw_copy_lookup(svdw_ctx* c, uint32_t phase, uint64_t off, uint64_t n, uint
 // view, canonical or Montgomery, or dequantized to f64; into device memory
 // (queued, no host wait) or host memory (staged through bounded scratch).
 static constexpr size_t kExportChunk = 64ull << 20;       // bytes of cells per staging half
-static void check_form(int form) {
-    REQUIRE(form == SVDW_FORM_CANONICAL || form == SVDW_FORM_MONTGOMERY,
-            "unknown form (SVDW_FORM_CANONICAL or SVDW_FORM_MONTGOMERY)");
-}
 static hipEvent_t export_event(svdw_ctx* c, int i) {
     if (!c->exp_ev[i])
         hipck(hipEventCreateWithFlags(&c->exp_ev[i], hipEventDisableTiming), "hipEventCreate");
@@ -4081,14 +3647,6 @@ int svdw_dequantize_vec(svdw_ctx* c, const svdw_vec* v, double* out, int on_devi
     });
 }
 // Host helpers (fr.hpp / export.hpp on the host, no context, no GPU).
-static Fr fr_raw_words(const uint64_t w[4]) { return big_from_words(w).v; }
-static void fr_store_words(const Fr& x, uint64_t w[4]) {
-    for (int i = 0; i < 4; ++i) w[i] = (uint64_t)x.w[2 * i] | ((uint64_t)x.w[2 * i + 1] << 32);
-}
-static bool fr_reduced(const Fr& x) {
-    Fr t;
-    return sub_p(t, x) != 0;                               // x - p borrows: x < p
-}
 int svdw_fr_convert(const uint64_t* in, uint64_t n, int from, int to, uint64_t* out) {
     return guarded([&] {
         REQUIRE(n == 0 || (in && out), "null argument");
@@ -4452,7 +4010,7 @@ int svdw_parse_svd_input_device(svdw_ctx* c, const void* text, uint64_t len, int
     namespace ig = svdw_ingest_dev;
     return guarded([&] {
         REQUIRE(c && text && dims, "null argument");
-        REQUIRE(!c->dry, "device ingest needs a device context");
+        need_device(c, "device ingest");
         REQUIRE(mode == SVDW_PARSE_SERDE,
                 "device ingest: serde mode only (correct rounding: svdw_parse_svd_input)");
         REQUIRE(len > 0, "svd input: empty text");
@@ -4629,7 +4187,7 @@ static std::vector<std::pair<uint64_t, uint64_t>> held(const svdw_ctx* c, uint32
 int svdw_check_gates(svdw_ctx* c, svdw_check_result* out) {
     return guarded([&] {
         REQUIRE(c && out, "null argument");
-        REQUIRE(!c->dry, "svdw_check_gates needs a device context");
+        need_device(c, "svdw_check_gates");
         sync(c);
         memset(out, 0, sizeof *out);
         ensure_buf(c, c->chk, 6 * sizeof(unsigned long long));
@@ -4793,7 +4351,7 @@ int svdw_assign_columns_form(svdw_ctx* c, uint32_t phase, int form, void* advice
     return guarded([&] {
         REQUIRE(c && phase < 2, "bad argument");
         check_form(form);
-        REQUIRE(!c->dry, "svdw_assign_columns needs a device context");
+        need_device(c, "svdw_assign_columns");
         REQUIRE(c->phys.valid, "svdw_assign_columns: call svdw_physical_layout after the witness");
         sync(c);
         const auto& P = c->phys;
@@ -4843,7 +4401,7 @@ int svdw_check_physical(svdw_ctx* c, uint32_t phase, const void* advice, const u
                         uint32_t ncols, svdw_check_result* out) {
     return guarded([&] {
         REQUIRE(c && advice && selectors && out && phase < 2, "bad argument");
-        REQUIRE(!c->dry, "svdw_check_physical needs a device context");
+        need_device(c, "svdw_check_physical");
         REQUIRE(c->phys.valid, "svdw_check_physical: call svdw_physical_layout first");
         memset(out, 0, sizeof *out);
         settle(c);
@@ -4896,7 +4454,7 @@ int svdw_check_equalities(svdw_ctx* c, uint32_t phase, const void* columns0, con
                           svdw_eq_check* out) {
     return guarded([&] {
         REQUIRE(c && phase < 2 && out, "bad argument");
-        REQUIRE(!c->dry, "svdw_check_equalities needs a device context");
+        need_device(c, "svdw_check_equalities");
         // a record's source and destination cells may lie in other ranks' rows,
         // which this context never wrote (svdw_check_gates checks a rank's own)
         REQUIRE(!sharded(c), "svdw_check_equalities: not on a row-sharded context (its streams hold "
@@ -4936,1169 +4494,6 @@ int svdw_check_equalities(svdw_ctx* c, uint32_t phase, const void* columns0, con
         out->copy_failures = h[1];
         out->consts_checked = h[2];
         out->const_failures = h[3];
-    });
-}
-// ---- lookup argument: multiplicities, permuted columns, their check (lookup.hpp)
-namespace {
-struct LkArgs {
-    uint32_t lb = 0;
-    uint64_t rows = 0, usable = 0;
-    LkSrc src{};
-};
-}  // namespace
-// The argument checks the three entries share. False: no columns, nothing to do.
-static bool lk_args(svdw_ctx* c, const char* fn, uint32_t phase, uint32_t unusable_rows, const void* columns,
-                    uint32_t ncols, LkArgs* a) {
-    const std::string f(fn);
-    REQUIRE(c && phase < 2, "bad argument");
-    REQUIRE(!c->dry, f + " needs a device context");
-    REQUIRE(!sharded(c), f + ": the lookup stream of a row-sharded context is partial");
-    REQUIRE(c->phys.valid, f + ": call svdw_physical_layout after the witness");
-    const auto& P = c->phys;
-    if (P.k > 31) fail(SVDW_ERANGE, f + ": k > 31");
-    REQUIRE(unusable_rows <= P.min_rows, f + ": unusable_rows exceeds the layout's minimum_rows "
-                                             "(an assigned row would be a blinding row)");
-    const uint64_t TL = c->ph[phase].nl, nl = (TL + P.R - 1) / P.R;
-    REQUIRE(columns || ncols == nl, f + ": ncols differs from num_lookup_advice of the phase");
-    a->lb = c->LB;
-    a->rows = 1ull << P.k;
-    a->usable = a->rows - unusable_rows;
-    if (c->LB > 31 || (1ull << c->LB) > a->usable)
-        fail(SVDW_ERANGE, f + ": the 2^lookup_bits table does not fit the usable rows (not enough rows: raise k)");
-    if (ncols > 65535) fail(SVDW_ERANGE, f + ": more than 65535 columns");
-    a->src = columns ? LkSrc{(const Fr*)columns, a->rows, a->rows, (uint64_t)ncols * a->rows}
-                     : LkSrc{c->ph[phase].lk, P.R, P.R, TL};
-    return ncols != 0;
-}
-// The 128-byte counter block at the head of the lookup scratch (which the caller
-// has sized), zeroed on the stream.
-static unsigned long long* zero_counters(svdw_ctx* c) {
-    unsigned long long* cnt = (unsigned long long*)c->lkp.p;
-    hipck(hipMemsetAsync(cnt, 0, 128, c->st), "hipMemsetAsync");
-    return cnt;
-}
-// h[0..n) = the counters, once the stream has run dry.
-static void read_counters(svdw_ctx* c, const unsigned long long* cnt, unsigned long long* h, size_t n) {
-    hipck(hipMemcpyAsync(h, cnt, n * sizeof *h, hipMemcpyDeviceToHost, c->st), "D2H");
-    hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
-}
-// One launch on the context's stream under its profile label.
-extern "C++" template <class Launch>
-static void profiled(svdw_ctx* c, const char* label, double bytes, Launch&& launch) {
-    ProfScope ps(c, c->st, label, bytes, 0);
-    hipck(launch(), label);
-}
-int svdw_lookup_multiplicities(svdw_ctx* c, uint32_t phase, uint32_t unusable_rows, const void* columns,
-                               uint32_t ncols, uint32_t* mult) {
-    return guarded([&] {
-        LkArgs a;
-        if (!lk_args(c, "svdw_lookup_multiplicities", phase, unusable_rows, columns, ncols, &a)) return;
-        REQUIRE(mult, "null output");
-        sync(c);
-        ensure_buf(c, c->lkp, 128);
-        unsigned long long* oot = zero_counters(c);
-        hipck(hipMemsetAsync(mult, 0, ((size_t)ncols << a.lb) * sizeof(uint32_t), c->st), "hipMemsetAsync");
-        profiled(c, "k_lk_hist", 32.0 * ncols * a.usable,
-                 [&] { return launch_lk_hist(a.src, SVDW_FORM_CANONICAL, ncols, a.usable, a.lb, mult, oot, c->st); });
-        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
-    });
-}
-int svdw_lookup_permute(svdw_ctx* c, uint32_t phase, uint32_t unusable_rows, int form, const void* columns,
-                        uint32_t ncols, void* permuted_input, void* permuted_table, svdw_lookup_result* result) {
-    return guarded([&] {
-        REQUIRE(result, "null argument");
-        check_form(form);
-        LkArgs a;
-        const bool any = lk_args(c, "svdw_lookup_permute", phase, unusable_rows, columns, ncols, &a);
-        memset(result, 0, sizeof *result);
-        result->usable_rows = a.usable;
-        if (!any) return;
-        REQUIRE(permuted_input && permuted_table, "null output");
-        sync(c);
-        const uint64_t B = 1ull << a.lb, nblk = lk_scan_blocks(B), bins = (uint64_t)ncols * B;
-        ensure_buf(c, c->lkp, 128 + (4 * bins + 2 * ncols * nblk + ncols) * sizeof(uint32_t));
-        unsigned long long* oot = (unsigned long long*)c->lkp.p;
-        LkScratch s;
-        s.cnt = (uint32_t*)((char*)c->lkp.p + 128);
-        s.start = s.cnt + bins;
-        s.pincl = s.start + bins;
-        s.absent = s.pincl + bins;
-        s.bsum = s.absent + bins;
-        s.tot = s.bsum + 2 * ncols * nblk;
-        hipck(hipMemsetAsync(c->lkp.p, 0, 128 + bins * sizeof(uint32_t), c->st), "hipMemsetAsync");
-        profiled(c, "k_lk_hist", 32.0 * ncols * a.usable,
-                 [&] { return launch_lk_hist(a.src, SVDW_FORM_CANONICAL, ncols, a.usable, a.lb, s.cnt, oot, c->st); });
-        unsigned long long bad = 0;
-        read_counters(c, oot, &bad, 1);
-        result->columns = ncols;
-        result->out_of_table = bad;
-        if (bad) return;                                    // ConstraintSystemFailure: the outputs stay as they are
-        profiled(c, "k_lk_scan", 20.0 * bins, [&] { return launch_lk_scans(s, ncols, a.lb, c->st); });
-        profiled(c, "k_lk_fill", 64.0 * ncols * a.rows, [&] {
-            return launch_lk_fill(s, ncols, a.rows, a.usable, a.lb, form, (Fr*)permuted_input, (Fr*)permuted_table,
-                                  c->st);
-        });
-        std::vector<uint32_t> tot(ncols);
-        hipck(hipMemcpyAsync(tot.data(), s.tot, ncols * sizeof(uint32_t), hipMemcpyDeviceToHost, c->st), "D2H");
-        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
-        for (uint32_t d : tot) result->distinct += d;
-    });
-}
-int svdw_check_lookup_argument(svdw_ctx* c, uint32_t phase, uint32_t unusable_rows, int form, const void* columns,
-                               uint32_t ncols, const void* permuted_input, const void* permuted_table,
-                               svdw_lookup_check* result) {
-    return guarded([&] {
-        REQUIRE(result, "null argument");
-        check_form(form);
-        LkArgs a;
-        const bool any = lk_args(c, "svdw_check_lookup_argument", phase, unusable_rows, columns, ncols, &a);
-        memset(result, 0, sizeof *result);
-        if (!any) return;
-        REQUIRE(permuted_input && permuted_table, "null argument");
-        sync(c);
-        const uint64_t bins = (uint64_t)ncols << a.lb;
-        ensure_buf(c, c->lkp, 128 + 3 * bins * sizeof(uint32_t));
-        unsigned long long* cnt = (unsigned long long*)c->lkp.p;   // [0..3] rows, [4..5] bins, [8] cells outside the table
-        uint32_t* ha = (uint32_t*)((char*)c->lkp.p + 128);
-        uint32_t *hpin = ha + bins, *htab = hpin + bins;
-        hipck(hipMemsetAsync(c->lkp.p, 0, 128 + 3 * bins * sizeof(uint32_t), c->st), "hipMemsetAsync");
-        const uint64_t cells = (uint64_t)ncols * a.rows;
-        {
-            ProfScope ps(c, c->st, "k_lk_hist:check", 32.0 * ncols * 3 * a.usable, 0);
-            hipck(launch_lk_hist(a.src, SVDW_FORM_CANONICAL, ncols, a.usable, a.lb, ha, cnt + 8, c->st), "k_lk_hist");
-            hipck(launch_lk_hist(LkSrc{(const Fr*)permuted_input, a.rows, a.rows, cells}, form, ncols, a.usable,
-                                 a.lb, hpin, cnt + 8, c->st), "k_lk_hist");
-            hipck(launch_lk_hist(LkSrc{(const Fr*)permuted_table, a.rows, a.rows, cells}, form, ncols, a.usable,
-                                 a.lb, htab, cnt + 8, c->st), "k_lk_hist");
-            hipck(launch_lk_compare(ha, hpin, htab, ncols, a.usable, a.lb, cnt + 4, c->st), "k_lk_compare");
-        }
-        profiled(c, "k_lk_adjacent", 64.0 * ncols * a.rows, [&] {
-            return launch_lk_adjacent((const Fr*)permuted_input, (const Fr*)permuted_table, ncols, a.rows, a.usable,
-                                      cnt, c->st);
-        });
-        unsigned long long h[9];
-        read_counters(c, cnt, h, 9);
-        result->adjacency_checked = h[0];
-        result->adjacency_failures = h[1];
-        result->padding_checked = h[2];
-        result->padding_failures = h[3];
-        result->multiset_checked = h[4];
-        result->multiset_failures = h[5] + h[8];           // a cell outside the table is in no bin
-    });
-}
-// ---- the grand products Z and their checks (grand_product.hpp)
-// What the lookup's and the permutation's entries check first, in this order:
-// the form, beta and gamma (to b, g), a row for Z[usable].
-static void gp_challenges(const char* fn, int form, const uint64_t beta[4], const uint64_t gamma[4],
-                          uint32_t unusable_rows, Fr* b, Fr* g) {
-    const std::string f(fn);
-    REQUIRE(beta && gamma, "null argument");
-    check_form(form);
-    *b = fr_raw_words(beta);
-    *g = fr_raw_words(gamma);
-    REQUIRE(fr_reduced(*b) && fr_reduced(*g), f + ": beta or gamma >= p");
-    if (!unusable_rows) fail(SVDW_ERANGE, f + ": unusable_rows == 0 leaves no row for Z[usable]");
-}
-// The six counters of a check kernel into either argument's check result.
-extern "C++" template <class Check>
-static void gp_check_result(svdw_ctx* c, const unsigned long long* cnt, Check* result) {
-    unsigned long long h[6];
-    read_counters(c, cnt, h, 6);
-    result->recurrence_checked = h[0];
-    result->recurrence_failures = h[1];
-    result->boundary_checked = h[2];
-    result->boundary_failures = h[3];
-    result->padding_checked = h[4];
-    result->padding_failures = h[5];
-}
-// ---- lookup argument: the grand product Z and its check (lookup_product.hpp)
-// The argument checks of both entries and what the kernels read (a->usable also
-// without columns); false: no columns, nothing to do.
-static bool lp_args(svdw_ctx* c, const char* fn, uint32_t phase, uint32_t unusable_rows, int form, const void* columns,
-                    uint32_t ncols, const void* permuted_input, const void* permuted_table, const uint64_t beta[4],
-                    const uint64_t gamma[4], LpArgs* a) {
-    Fr b, g;
-    gp_challenges(fn, form, beta, gamma, unusable_rows, &b, &g);
-    LkArgs lk;
-    const bool any = lk_args(c, fn, phase, unusable_rows, columns, ncols, &lk);
-    const bool mont = form == SVDW_FORM_MONTGOMERY;
-    a->src = lk.src;
-    a->pin = (const Fr*)permuted_input;
-    a->ptab = (const Fr*)permuted_table;
-    a->ncols = ncols;
-    a->lb = lk.lb;
-    a->rows = lk.rows;
-    a->usable = lk.usable;
-    a->ch.b0 = b;
-    a->ch.g0 = g;
-    a->ch.bx = mont ? fr_to_mont(b) : b;
-    a->ch.gx = mont ? fr_to_mont(g) : g;
-    a->ch.g2 = fr_to_mont(fr_to_mont(g));
-    a->ch.t2 = fr_to_mont(fr_to_mont(fr_from_u64(1ull << 32)));
-    a->ch.one = fr_to_mont(fr_from_u64(1));
-    return any;
-}
-int svdw_lookup_product(svdw_ctx* c, uint32_t phase, uint32_t unusable_rows, int form, const void* columns,
-                        uint32_t ncols, const void* permuted_input, const void* permuted_table,
-                        const uint64_t beta[4], const uint64_t gamma[4], void* z, svdw_lookup_product_result* result) {
-    return guarded([&] {
-        REQUIRE(result, "null argument");
-        LpArgs a;
-        const bool any = lp_args(c, "svdw_lookup_product", phase, unusable_rows, form, columns, ncols, permuted_input,
-                                 permuted_table, beta, gamma, &a);
-        memset(result, 0, sizeof *result);
-        result->usable_rows = a.usable;
-        if (!any) return;
-        REQUIRE(permuted_input && permuted_table && z, "null argument");
-        sync(c);
-        const uint64_t nt = gp_tiles(a.rows);
-        ensure_buf(c, c->lkp, 128 + 2 * ncols * nt * sizeof(Fr));
-        unsigned long long* cnt = zero_counters(c);        // [0] zero denominators, [1] columns with Z[usable] != 1
-        Fr* tp = (Fr*)((char*)c->lkp.p + 128);
-        const double cells = (double)ncols * a.usable;
-        profiled(c, "k_lp_tiles", 96.0 * cells, [&] { return launch_lp_tiles(a, form, tp, cnt, c->st); });
-        profiled(c, "k_lp_carry", 128.0 * ncols * nt, [&] { return launch_lp_carry(a, form, tp, cnt, c->st); });
-        profiled(c, "k_lp_write", 96.0 * cells + 32.0 * ncols * a.rows,
-                 [&] { return launch_lp_write(a, form, tp, (Fr*)z, c->st); });
-        unsigned long long h[2];
-        read_counters(c, cnt, h, 2);
-        result->columns = ncols;
-        result->zero_denominators = h[0];
-        result->final_not_one = h[1];
-    });
-}
-int svdw_check_lookup_product(svdw_ctx* c, uint32_t phase, uint32_t unusable_rows, int form, const void* columns,
-                              uint32_t ncols, const void* permuted_input, const void* permuted_table,
-                              const uint64_t beta[4], const uint64_t gamma[4], const void* z,
-                              svdw_lookup_product_check* result) {
-    return guarded([&] {
-        REQUIRE(result, "null argument");
-        LpArgs a;
-        const bool any = lp_args(c, "svdw_check_lookup_product", phase, unusable_rows, form, columns, ncols,
-                                 permuted_input, permuted_table, beta, gamma, &a);
-        memset(result, 0, sizeof *result);
-        if (!any) return;
-        REQUIRE(permuted_input && permuted_table && z, "null argument");
-        sync(c);
-        ensure_buf(c, c->lkp, 128);
-        unsigned long long* cnt = zero_counters(c);
-        profiled(c, "k_lp_check", 96.0 * ncols * a.usable + 32.0 * ncols * a.rows,
-                 [&] { return launch_lp_check(a, form, (const Fr*)z, cnt, c->st); });
-        gp_check_result(c, cnt, result);
-    });
-}
-// ---- permutation argument: sigma values, the grand products Z and their check
-// (permutation_product.hpp)
-namespace {
-struct PpConsts {
-    Fr delta, omega28;                                     // canonical
-};
-struct PpDev {
-    PpArgs a{};
-    unsigned long long* cnt = nullptr;
-    Fr *sv = nullptr, *xs = nullptr, *tp = nullptr;
-};
-}  // namespace
-// delta = 7^(2^28) and omega_28 = 7^((p - 1) / 2^28), as halo2curves derives them.
-static const PpConsts& pp_consts() {
-    static const PpConsts k = [] {
-        Fr e = fr_p();
-        e.w[0] -= 1;
-        for (int i = 0; i < 8; ++i) e.w[i] = (e.w[i] >> 28) | (i < 7 ? e.w[i + 1] << 4 : 0u);
-        const Fr g = fr_to_mont(fr_from_u64(7));
-        Fr w = fr_to_mont(fr_from_u64(1)), d = g;
-        for (int i = 255; i >= 0; --i) {
-            w = mont_mul(w, w);
-            if ((e.w[i >> 5] >> (i & 31)) & 1) w = mont_mul(w, g);
-        }
-        for (int i = 0; i < 28; ++i) d = mont_mul(d, d);
-        return PpConsts{fr_from_mont(d), fr_from_mont(w)};
-    }();
-    return k;
-}
-// omega_k R for 1 <= k <= 28.
-static Fr pp_omega_mont(uint32_t k) {
-    Fr w = fr_to_mont(pp_consts().omega28);
-    for (uint32_t i = k; i < 28; ++i) w = mont_mul(w, w);
-    return w;
-}
-static uint32_t pp_split(uint32_t k) { return (k + 1) / 2; }
-// The context's omega tables for k: omega^i R for i < 2^h, then omega^(i 2^h) R for i < 2^(k - h).
-static const std::vector<Fr>& pp_tables(svdw_ctx* c, uint32_t k) {
-    if (c->pp_k == k && !c->pp_w.empty()) return c->pp_w;
-    const uint32_t h = pp_split(k);
-    const size_t nlo = (size_t)1 << h, nhi = (size_t)1 << (k - h);
-    std::vector<Fr> t(nlo + nhi);
-    const Fr w = pp_omega_mont(k), one = fr_to_mont(fr_from_u64(1));
-    t[0] = one;
-    for (size_t i = 1; i < nlo; ++i) t[i] = mont_mul(t[i - 1], w);
-    const Fr wh = mont_mul(t[nlo - 1], w);
-    t[nlo] = one;
-    for (size_t i = 1; i < nhi; ++i) t[nlo + i] = mont_mul(t[nlo + i - 1], wh);
-    c->pp_w.swap(t);
-    c->pp_k = k;
-    return c->pp_w;
-}
-// x delta^j phi for j < n (phi = 1 canonical, R Montgomery), x canonical.
-static void pp_delta_powers(const Fr& x, int form, uint32_t n, Fr* out) {
-    const Fr dm = fr_to_mont(pp_consts().delta);
-    Fr v = form == SVDW_FORM_MONTGOMERY ? fr_to_mont(x) : x;
-    for (uint32_t j = 0; j < n; ++j) {
-        out[j] = v;
-        v = mont_mul(v, dm);
-    }
-}
-int svdw_permutation_constants(uint32_t k, uint64_t delta[4], uint64_t omega[4]) {
-    return guarded([&] {
-        REQUIRE(delta && omega, "null argument");
-        if (k < 1 || k > 28) fail(SVDW_ERANGE, "svdw_permutation_constants: k must be in [1, 28]");
-        fr_store_words(pp_consts().delta, delta);
-        fr_store_words(fr_from_mont(pp_omega_mont(k)), omega);
-    });
-}
-int svdw_permutation_values(svdw_ctx* c, uint32_t k, int form, const uint64_t* mapping, uint32_t first_col,
-                            uint32_t ncols, uint32_t total_cols, void* out, uint64_t* out_of_range) {
-    return guarded([&] {
-        REQUIRE(c && out_of_range, "null argument");
-        check_form(form);
-        if (k < 1 || k > 28) fail(SVDW_ERANGE, "svdw_permutation_values: k must be in [1, 28]");
-        REQUIRE(!c->dry, "svdw_permutation_values needs a device context");
-        if (ncols > 65535 || total_cols > 65535) fail(SVDW_ERANGE, "svdw_permutation_values: more than 65535 columns");
-        *out_of_range = 0;
-        if (!ncols) return;
-        REQUIRE(out, "null output");
-        sync(c);
-        const std::vector<Fr>& w = pp_tables(c, k);
-        const uint32_t h = pp_split(k);
-        const size_t nd = std::max(total_cols, 1u), bytes = (nd + w.size()) * sizeof(Fr);
-        c->pp_up.resize(bytes);
-        pp_delta_powers(fr_from_u64(1), form, total_cols, (Fr*)c->pp_up.data());
-        memcpy(c->pp_up.data() + nd * sizeof(Fr), w.data(), w.size() * sizeof(Fr));
-        ensure_buf(c, c->lkp, 128 + bytes);
-        unsigned long long* cnt = zero_counters(c);
-        const Fr* dl = (const Fr*)((char*)c->lkp.p + 128);
-        hipck(hipMemcpyAsync((void*)dl, c->pp_up.data(), bytes, hipMemcpyHostToDevice, c->st), "H2D");
-        profiled(c, "k_pp_values", (mapping ? 40.0 : 32.0) * ncols * (double)(1ull << k), [&] {
-            return launch_pp_values(mapping, dl, dl + nd, dl + nd + ((size_t)1 << h), h, first_col, ncols, total_cols,
-                                    1ull << k, (Fr*)out, cnt, c->st);
-        });
-        unsigned long long bad = 0;
-        read_counters(c, cnt, &bad, 1);
-        *out_of_range = bad;
-    });
-}
-// The argument checks of both entries, in the order include/svdw.h gives, and
-// the device tables; false: no columns, nothing to do.
-static bool pp_args(svdw_ctx* c, const char* fn, uint32_t k, uint32_t unusable_rows, int form,
-                    const void* const* columns, const void* const* sigma, uint32_t ncols, uint32_t chunk_len,
-                    const uint64_t beta[4], const uint64_t gamma[4], const void* z, bool scratch, PpDev* d) {
-    const std::string f(fn);
-    REQUIRE(c, "null argument");
-    Fr b, g;
-    gp_challenges(fn, form, beta, gamma, unusable_rows, &b, &g);
-    const uint64_t rows = k < 63 ? 1ull << k : ~0ull;
-    if (unusable_rows >= rows) fail(SVDW_ERANGE, f + ": unusable_rows leaves no usable row");
-    REQUIRE(chunk_len, f + ": chunk_len == 0");
-    if (k < 1 || k > 28) fail(SVDW_ERANGE, f + ": k must be in [1, 28]");
-    REQUIRE(!c->dry, f + " needs a device context");
-    PpArgs& a = d->a;
-    a.rows = rows;
-    a.usable = rows - unusable_rows;
-    a.ncols = ncols;
-    a.chunk = chunk_len;
-    a.nsets = ncols ? pp_sets(ncols, chunk_len) : 0;
-    if (!ncols) return false;
-    if (ncols > 65535) fail(SVDW_ERANGE, f + ": more than 65535 columns");
-    REQUIRE(columns && sigma && z, "null argument");
-    for (uint32_t j = 0; j < ncols; ++j) REQUIRE(columns[j] && sigma[j], f + ": null column pointer");
-    sync(c);
-    const bool mont = form == SVDW_FORM_MONTGOMERY;
-    const std::vector<Fr>& w = pp_tables(c, k);
-    a.h = pp_split(k);
-    a.bR = fr_to_mont(b);
-    a.g = mont ? fr_to_mont(g) : g;
-    a.one = fr_to_mont(fr_from_u64(1));
-    const size_t pbytes = ((size_t)2 * ncols * sizeof(void*) + 31) / 32 * 32;
-    const size_t up = pbytes + ((size_t)ncols + w.size()) * sizeof(Fr);
-    c->pp_up.assign(up, 0);
-    memcpy(c->pp_up.data(), columns, ncols * sizeof(void*));
-    memcpy(c->pp_up.data() + ncols * sizeof(void*), sigma, ncols * sizeof(void*));
-    pp_delta_powers(b, form, ncols, (Fr*)(c->pp_up.data() + pbytes));
-    memcpy(c->pp_up.data() + pbytes + ncols * sizeof(Fr), w.data(), w.size() * sizeof(Fr));
-    const uint64_t cells = scratch ? pp_scratch_cells(a.nsets, rows) : 0;
-    ensure_buf(c, c->lkp, 128 + up + cells * sizeof(Fr));
-    char* base = (char*)c->lkp.p;
-    d->cnt = zero_counters(c);
-    a.cols = (const Fr* const*)(base + 128);
-    a.sig = a.cols + ncols;
-    a.bd = (const Fr*)(base + 128 + pbytes);
-    a.wlo = a.bd + ncols;
-    a.whi = a.wlo + ((size_t)1 << a.h);
-    d->sv = (Fr*)(base + 128 + up);
-    d->xs = d->sv + 2 * (uint64_t)a.nsets;
-    d->tp = d->xs + 2 * (uint64_t)kGpThreads * a.nsets;
-    hipck(hipMemcpyAsync(base + 128, c->pp_up.data(), up, hipMemcpyHostToDevice, c->st), "H2D");
-    return true;
-}
-int svdw_permutation_product(svdw_ctx* c, uint32_t k, uint32_t unusable_rows, int form, const void* const* columns,
-                             const void* const* sigma, uint32_t ncols, uint32_t chunk_len, const uint64_t beta[4],
-                             const uint64_t gamma[4], void* z, svdw_permutation_product_result* result) {
-    return guarded([&] {
-        REQUIRE(result, "null argument");
-        PpDev d;
-        const bool any = pp_args(c, "svdw_permutation_product", k, unusable_rows, form, columns, sigma, ncols,
-                                 chunk_len, beta, gamma, z, true, &d);
-        memset(result, 0, sizeof *result);
-        result->usable_rows = d.a.usable;
-        if (!any) return;
-        const PpArgs& a = d.a;
-        const double cells = (double)ncols * a.usable, nt = (double)gp_tiles(a.rows);
-        profiled(c, "k_pp_tiles", 64.0 * cells, [&] { return launch_pp_tiles(a, form, d.tp, d.cnt, c->st); });
-        profiled(c, "k_pp_totals", 64.0 * a.nsets * nt,
-                 [&] { return launch_pp_totals(a, form, d.tp, d.xs, d.sv, c->st); });
-        profiled(c, "k_pp_chain", 128.0 * a.nsets, [&] { return launch_pp_chain(a, d.sv, d.cnt, c->st); });
-        profiled(c, "k_pp_fold", 128.0 * a.nsets * nt,
-                 [&] { return launch_pp_fold(a, form, d.tp, d.xs, d.sv, c->st); });
-        profiled(c, "k_pp_write", 64.0 * cells + 32.0 * a.nsets * a.rows,
-                 [&] { return launch_pp_write(a, form, d.tp, (Fr*)z, c->st); });
-        unsigned long long h[2];
-        read_counters(c, d.cnt, h, 2);
-        result->columns = ncols;
-        result->sets = a.nsets;
-        result->zero_denominators = h[0];
-        result->final_not_one = (uint32_t)h[1];
-    });
-}
-int svdw_check_permutation_product(svdw_ctx* c, uint32_t k, uint32_t unusable_rows, int form,
-                                   const void* const* columns, const void* const* sigma, uint32_t ncols,
-                                   uint32_t chunk_len, const uint64_t beta[4], const uint64_t gamma[4], const void* z,
-                                   svdw_permutation_product_check* result) {
-    return guarded([&] {
-        REQUIRE(result, "null argument");
-        PpDev d;
-        const bool any = pp_args(c, "svdw_check_permutation_product", k, unusable_rows, form, columns, sigma, ncols,
-                                 chunk_len, beta, gamma, z, false, &d);
-        memset(result, 0, sizeof *result);
-        if (!any) return;
-        const PpArgs& a = d.a;
-        const Fr wstep = fr_to_mont(fr_pow_u64(fr_from_mont(pp_omega_mont(k)), pp_check_stride(a.rows)));
-        profiled(c, "k_pp_check", 64.0 * ncols * a.usable + 32.0 * a.nsets * a.rows,
-                 [&] { return launch_pp_check(a, form, (const Fr*)z, wstep, d.cnt, c->st); });
-        gp_check_result(c, d.cnt, result);
-    });
-}
-// ---- transforms between Lagrange, coefficient and extended form, evaluation at
-// points and the transform's check (ntt.hpp)
-namespace {
-struct NttCall {
-    uint32_t k_in = 0, k = 0, ncols = 0;
-    int form = 0, inverse = 0;
-    bool shifted = false;
-    Fr shift;                                              // canonical
-};
-struct NttDev {                                            // what a call staged behind the counters of c->lkp
-    const Fr* const* cols = nullptr;
-    const Fr* cells = nullptr;                             // the Fr cells staged after the pointers
-    char* free = nullptr;                                  // scratch from here on
-};
-}  // namespace
-// The argument checks of svdw_ntt and svdw_check_ntt (log_samples: the latter's,
-// else 0), in the order include/svdw.h gives; false: no columns, nothing to do.
-static bool ntt_args(svdw_ctx* c, const char* fn, uint32_t k_in, uint32_t k, int form, int inverse,
-                     const uint64_t shift[4], const void* const* in, uint32_t ncols, const void* out,
-                     uint32_t log_samples, NttCall* a) {
-    const std::string f(fn);
-    REQUIRE(c, "null argument");
-    check_form(form);
-    a->shift = fr_from_u64(1);
-    if (shift) {
-        a->shift = fr_raw_words(shift);
-        REQUIRE(fr_reduced(a->shift) && !fr_is_zero(a->shift), f + ": shift >= p or shift == 0");
-    }
-    a->shifted = !fr_eq(a->shift, fr_from_u64(1));
-    REQUIRE(inverse == 0 || inverse == 1, f + ": inverse must be 0 or 1");
-    if (k < 1 || k > 28) fail(SVDW_ERANGE, f + ": k must be in [1, 28]");
-    if (k_in < 1 || k_in > k) fail(SVDW_ERANGE, f + ": k_in must be in [1, k]");
-    if (inverse && k_in != k) fail(SVDW_ERANGE, f + ": an inverse transform needs k_in == k");
-    if (log_samples > k) fail(SVDW_ERANGE, f + ": log_samples must be in [0, k]");
-    REQUIRE(!c->dry, f + " needs a device context");
-    a->k_in = k_in;
-    a->k = k;
-    a->ncols = ncols;
-    a->form = form;
-    a->inverse = inverse;
-    if (!ncols) return false;
-    if (ncols > 65535) fail(SVDW_ERANGE, f + ": more than 65535 columns");
-    REQUIRE(in && out, "null argument");
-    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (((uintptr_t)ncols << k) * sizeof(Fr));
-    for (uint32_t j = 0; j < ncols; ++j) {
-        REQUIRE(in[j], f + ": null column pointer");
-        const uintptr_t i0 = (uintptr_t)in[j], i1 = i0 + (((uintptr_t)1 << k_in) * sizeof(Fr));
-        REQUIRE(i1 <= o0 || o1 <= i0, f + ": out overlaps an input column");
-    }
-    return true;
-}
-// The device tables of k, made once per k: omega_1024^j R and omega_1024^-j R
-// for j < 512, then the two-level omega_k tables of pp_tables.
-static const Fr* ntt_tables(svdw_ctx* c, uint32_t k) {
-    const std::vector<Fr>& w = pp_tables(c, k);
-    const size_t cells = 1024 + w.size();
-    const bool grown = c->ntt_tab.cap < cells * sizeof(Fr);
-    ensure_buf(c, c->ntt_tab, cells * sizeof(Fr));
-    if (grown || c->ntt_k != k) {
-        std::vector<Fr> t(cells);
-        const Fr w10 = pp_omega_mont(10);
-        t[0] = t[512] = fr_to_mont(fr_from_u64(1));
-        for (size_t j = 1; j < 512; ++j) t[j] = mont_mul(t[j - 1], w10);
-        for (size_t j = 1; j < 512; ++j) t[512 + j] = fr_neg(t[512 - j]);   // omega^-j = -omega^(512 - j)
-        memcpy(t.data() + 1024, w.data(), w.size() * sizeof(Fr));
-        hipck(hipMemcpyAsync(c->ntt_tab.p, t.data(), cells * sizeof(Fr), hipMemcpyHostToDevice, c->st), "H2D");
-        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
-        c->ntt_k = k;
-    }
-    return (const Fr*)c->ntt_tab.p;
-}
-// base^i R for i < 2^fh, then top base^(i 2^fh) R for i < 2^(kk - fh): the
-// two-level table of a call's shift, top = the scale times R.
-static void ntt_factor_tables(const Fr& base, const Fr& top, uint32_t kk, Fr* out) {
-    const uint32_t fh = pp_split(kk);
-    const size_t nlo = (size_t)1 << fh, nhi = (size_t)1 << (kk - fh);
-    const Fr b = fr_to_mont(base);
-    out[0] = fr_to_mont(fr_from_u64(1));
-    for (size_t i = 1; i < nlo; ++i) out[i] = mont_mul(out[i - 1], b);
-    const Fr bh = mont_mul(out[nlo - 1], b);
-    out[nlo] = top;
-    for (size_t i = 1; i < nhi; ++i) out[nlo + i] = mont_mul(out[nlo + i - 1], bh);
-}
-// Stage the ncols column pointers and `cells` Fr cells (filled by `fill`) behind
-// the zeroed counters of c->lkp, with `scratch` bytes after them.
-extern "C++" template <class Fill>
-static NttDev ntt_stage(svdw_ctx* c, const void* const* ptrs, uint32_t ncols, size_t cells, size_t scratch,
-                        Fill&& fill) {
-    const size_t pbytes = ((size_t)ncols * sizeof(void*) + 31) / 32 * 32, up = pbytes + cells * sizeof(Fr);
-    c->pp_up.assign(up, 0);
-    if (ncols) memcpy(c->pp_up.data(), ptrs, ncols * sizeof(void*));
-    fill((Fr*)(c->pp_up.data() + pbytes));
-    ensure_buf(c, c->lkp, 128 + up + scratch);
-    char* base = (char*)c->lkp.p;
-    (void)zero_counters(c);
-    hipck(hipMemcpyAsync(base + 128, c->pp_up.data(), up, hipMemcpyHostToDevice, c->st), "H2D");
-    return NttDev{(const Fr* const*)(base + 128), (const Fr*)(base + 128 + pbytes), base + 128 + up};
-}
-uint32_t svdw_ntt_passes(uint32_t k) { return ntt_passes(k); }
-int svdw_ntt(svdw_ctx* c, uint32_t k_in, uint32_t k, int form, int inverse, const uint64_t shift[4],
-             const void* const* in, uint32_t ncols, void* out, svdw_ntt_result* result) {
-    return guarded([&] {
-        REQUIRE(result, "null argument");
-        NttCall a;
-        const bool any = ntt_args(c, "svdw_ntt", k_in, k, form, inverse, shift, in, ncols, out, 0, &a);
-        memset(result, 0, sizeof *result);
-        result->passes = ntt_passes(k);
-        result->rows_in = 1ull << k_in;
-        result->rows_out = 1ull << k;
-        if (!any) return;
-        sync(c);
-        const uint32_t P = ntt_passes(k), h = pp_split(k), kk = inverse ? k : k_in, fh = pp_split(kk);
-        const uint64_t N = 1ull << k;
-        const Fr* tab = ntt_tables(c, k);
-        const Fr scale = inverse ? fr_to_mont(fr_inv(fr_from_u64(N))) : fr_to_mont(fr_from_u64(1));   // 2^-k R
-        const size_t fcells = a.shifted ? ((size_t)1 << fh) + ((size_t)1 << (kk - fh)) : 0;
-        if (P > 1) ensure_buf(c, c->ntt_tmp, (size_t)ncols * N * sizeof(Fr));
-        const NttDev d = ntt_stage(c, in, ncols, fcells, 0, [&](Fr* t) {
-            if (a.shifted) ntt_factor_tables(a.shift, scale, kk, t);
-        });
-        Fr* tmp = (Fr*)c->ntt_tmp.p;
-        uint32_t ls = 0;
-        for (uint32_t i = 0; i < P; ++i) {
-            NttPass p{};
-            p.cols = i ? nullptr : d.cols;
-            // the buffers alternate so that the last pass writes out
-            p.src = i ? ((P - i) % 2 ? tmp : (const Fr*)out) : nullptr;
-            p.dst = (P - 1 - i) % 2 ? tmp : (Fr*)out;
-            p.tw = tab + (inverse ? 512 : 0);
-            p.wlo = tab + 1024;
-            p.whi = p.wlo + ((size_t)1 << h);
-            p.flo = a.shifted ? d.cells : nullptr;
-            p.fhi = a.shifted ? d.cells + ((size_t)1 << fh) : nullptr;
-            p.fc = scale;
-            p.k = k;
-            p.kin = i ? k : k_in;
-            p.b = ntt_pass_bits(k, i);
-            p.ls = ls;
-            p.h = h;
-            p.fh = fh;
-            p.ncols = ncols;
-            p.inverse = (uint32_t)inverse;
-            p.last = i + 1 == P;
-            p.pre = !inverse && a.shifted && i == 0;
-            p.post = inverse && p.last ? (a.shifted ? 2u : 1u) : 0u;
-            ls += p.b;
-            const char* label = i == 0 ? "k_ntt_pass1" : i == 1 ? "k_ntt_pass2" : "k_ntt_pass3";
-            profiled(c, label, 32.0 * ncols * ((double)(1ull << p.kin) + (double)N),
-                     [&] { return launch_ntt_pass(p, c->st); });
-        }
-        result->columns = ncols;
-    });
-}
-// The evaluations of ncols polynomials of n coefficients (cols or src, as the
-// kernels take them) at the npoints points dpts (device, x R), in chunks of at
-// most `chunk` points through part; then(q0, nq) after each chunk's sums.
-extern "C++" template <class Then>
-static void ntt_eval_chunks(svdw_ctx* c, const Fr* const* cols, const Fr* src, uint64_t n, uint32_t ncols,
-                            const Fr* dpts, uint64_t npoints, uint32_t chunk, Fr* part, uint64_t out_stride, Fr* out,
-                            bool advance_out, Then&& then) {
-    const uint32_t nb = ntt_eval_blocks(n);
-    for (uint64_t q0 = 0; q0 < npoints; q0 += chunk) {
-        const uint32_t nq = (uint32_t)std::min<uint64_t>(chunk, npoints - q0);
-        profiled(c, "k_ntt_eval", 32.0 * ncols * (double)n * nq,
-                 [&] { return launch_ntt_eval(cols, src, n, ncols, dpts + q0, nq, part, c->st); });
-        profiled(c, "k_ntt_eval_sum", 32.0 * ncols * (double)nq * (nb + 1), [&] {
-            return launch_ntt_eval_sum(part, nb, ncols, nq, out_stride, out + (advance_out ? q0 : 0), c->st);
-        });
-        then(q0, nq);
-    }
-}
-static constexpr uint32_t kNttPointChunk = 32768;          // points per launch of k_ntt_eval
-int svdw_eval_polynomial(svdw_ctx* c, uint32_t k, int form, const void* const* coeffs, uint32_t ncols,
-                         const uint64_t* points, uint32_t npoints, void* out) {
-    return guarded([&] {
-        const std::string f("svdw_eval_polynomial");
-        REQUIRE(c && (points || !npoints), "null argument");
-        check_form(form);
-        for (uint32_t q = 0; q < npoints; ++q)
-            REQUIRE(fr_reduced(fr_raw_words(points + 4 * (size_t)q)), f + ": point >= p");
-        if (k < 1 || k > 28) fail(SVDW_ERANGE, f + ": k must be in [1, 28]");
-        REQUIRE(!c->dry, f + " needs a device context");
-        if (!ncols || !npoints) return;
-        if (ncols > 65535) fail(SVDW_ERANGE, f + ": more than 65535 columns");
-        REQUIRE(coeffs && out, "null argument");
-        for (uint32_t j = 0; j < ncols; ++j) REQUIRE(coeffs[j], f + ": null column pointer");
-        sync(c);
-        const uint64_t n = 1ull << k;
-        const uint32_t chunk = std::min(npoints, kNttPointChunk);
-        const size_t part = (size_t)ncols * chunk * ntt_eval_blocks(n) * sizeof(Fr);
-        const NttDev d = ntt_stage(c, coeffs, ncols, npoints, part, [&](Fr* t) {
-            for (uint32_t q = 0; q < npoints; ++q) t[q] = fr_to_mont(fr_raw_words(points + 4 * (size_t)q));
-        });
-        ntt_eval_chunks(c, d.cols, nullptr, n, ncols, d.cells, npoints, chunk, (Fr*)d.free, npoints, (Fr*)out, true,
-                        [](uint64_t, uint32_t) {});
-    });
-}
-int svdw_check_ntt(svdw_ctx* c, uint32_t k_in, uint32_t k, int form, int inverse, const uint64_t shift[4],
-                   const void* const* in, uint32_t ncols, const void* out, uint32_t log_samples, uint64_t seed,
-                   svdw_ntt_check* result) {
-    return guarded([&] {
-        REQUIRE(result, "null argument");
-        NttCall a;
-        const bool any = ntt_args(c, "svdw_check_ntt", k_in, k, form, inverse, shift, in, ncols, out, log_samples, &a);
-        memset(result, 0, sizeof *result);
-        if (!any) return;
-        sync(c);
-        // the points: shift omega^j (forward), omega^j / shift (inverse), as x R
-        const std::vector<Fr>& w = pp_tables(c, k);
-        const uint32_t h = pp_split(k);
-        const uint64_t S = 1ull << log_samples, n = 1ull << (inverse ? k : k_in);
-        const Fr sR = fr_to_mont(inverse ? fr_inv(a.shift) : a.shift);
-        const uint32_t chunk = (uint32_t)std::min<uint64_t>(S, kNttPointChunk);
-        const size_t vals = (size_t)ncols * chunk * sizeof(Fr), part = vals * ntt_eval_blocks(n);
-        const NttDev d = ntt_stage(c, in, ncols, S, vals + part, [&](Fr* t) {
-            for (uint64_t s = 0; s < S; ++s) {
-                const uint64_t j = ntt_sample_row(k, log_samples, seed, s);
-                const Fr wj = mont_mul(w[((size_t)1 << h) + (j >> h)], w[j & (((size_t)1 << h) - 1)]);
-                t[s] = mont_mul(wj, sR);
-            }
-        });
-        unsigned long long* cnt = (unsigned long long*)c->lkp.p;
-        Fr* dv = (Fr*)d.free;
-        // forward: the input's polynomial against the cells of out; inverse: the other way round
-        const Fr* const* pcols = inverse ? nullptr : d.cols;
-        const Fr* psrc = inverse ? (const Fr*)out : nullptr;
-        ntt_eval_chunks(c, pcols, psrc, n, ncols, d.cells, S, chunk, dv + (size_t)ncols * chunk, chunk, dv, false,
-                        [&](uint64_t s0, uint32_t ns) {       // ns == chunk: both are powers of two
-                            profiled(c, "k_ntt_compare", 64.0 * ncols * ns, [&] {
-                                return launch_ntt_compare(inverse ? d.cols : nullptr,
-                                                          inverse ? nullptr : (const Fr*)out, k, log_samples, seed,
-                                                          s0, ns, ncols, dv, cnt, c->st);
-                            });
-                        });
-        unsigned long long hc[2];
-        read_counters(c, cnt, hc, 2);
-        result->rows_checked = hc[0];
-        result->row_failures = hc[1];
-    });
-}
-// ---- KZG commitments of columns: the multi-scalar multiplication and its
-// bit-serial check (commit.hpp)
-// A batch's workspace stays under the option "commit_scratch_mib" (1 GiB by
-// default: the order of ntt_tmp for 8 columns of 2^22 rows) unless one task
-// alone needs more. The kernels between the sort and the window sums are
-// latency-bound per batch, so fewer, larger batches are faster.
-// The argument checks of svdw_commit and svdw_check_commit, in the order
-// include/svdw.h gives; false: no columns, nothing to do.
-static bool commit_args(svdw_ctx* c, const char* fn, uint32_t k, int form, int bases_form, const void* bases,
-                        const void* const* cols, uint32_t ncols, const void* out, bool writes) {
-    const std::string f(fn);
-    REQUIRE(c, "null argument");
-    check_form(form);
-    check_form(bases_form);
-    if (k < 1 || k > 28) fail(SVDW_ERANGE, f + ": k must be in [1, 28]");
-    REQUIRE(!c->dry, f + " needs a device context");
-    if (!ncols) return false;
-    if (ncols > 65535) fail(SVDW_ERANGE, f + ": more than 65535 columns");
-    REQUIRE(bases && cols && out, "null argument");
-    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)ncols * sizeof(G1Affine);
-    const uintptr_t b0 = (uintptr_t)bases, b1 = b0 + (((uintptr_t)1 << k) * sizeof(G1Affine));
-    REQUIRE(!writes || b1 <= o0 || o1 <= b0, f + ": out overlaps the bases");
-    for (uint32_t j = 0; j < ncols; ++j) {
-        REQUIRE(cols[j], f + ": null column pointer");
-        const uintptr_t i0 = (uintptr_t)cols[j], i1 = i0 + (((uintptr_t)1 << k) * sizeof(Fr));
-        REQUIRE(!writes || i1 <= o0 || o1 <= i0, f + ": out overlaps an input column");
-    }
-    return true;
-}
-void svdw_commit_plan(uint32_t k, uint32_t* window_bits, uint32_t* windows) {
-    uint32_t c = 0, W = 0;
-    commit_plan(k < 1 ? 1 : k > 28 ? 28 : k, &c, &W);
-    if (window_bits) *window_bits = c;
-    if (windows) *windows = W;
-}
-int svdw_commit(svdw_ctx* c, uint32_t k, int form, int bases_form, const void* bases, const void* const* cols,
-                uint32_t ncols, void* out, svdw_commit_result* result) {
-    return guarded([&] {
-        REQUIRE(result, "null argument");
-        const bool any = commit_args(c, "svdw_commit", k, form, bases_form, bases, cols, ncols, out, true);
-        memset(result, 0, sizeof *result);
-        commit_plan(k, &result->window_bits, &result->windows);
-        if (c->opt.commit_window_bits) {                   // the tuning override
-            result->window_bits = c->opt.commit_window_bits;
-            result->windows = (255 + result->window_bits - 1) / result->window_bits;
-        }
-        result->rows = 1ull << k;
-        if (!any) return;
-        sync(c);
-        const uint32_t cb = result->window_bits, W = result->windows;
-        const uint64_t n = 1ull << k, B = 1ull << (cb - 1), tasks = (uint64_t)ncols * W;
-        const uint64_t per = commit_task_bytes(n, B);
-        const uint64_t cap = (uint64_t)c->opt.commit_scratch_mib << 20;
-        const uint32_t T = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(cap / per, 1),
-                                                        std::min<uint64_t>(tasks, 65535));
-        // the call's window sums, then the arrays of one batch, each from a 128-byte boundary
-        size_t off = 0;
-        auto take = [&](size_t bytes) {
-            const size_t at = off;
-            off += (bytes + 127) / 128 * 128;
-            return at;
-        };
-        const size_t o_win = take(tasks * sizeof(G1Xyzz)), o_slots = take(T * commit_slots_all(n) * sizeof(G1Xyzz)),
-                     o_bkt = take(T * B * sizeof(G1Xyzz)), o_chk = take(T * commit_chunks(B) * sizeof(G1Xyzz)),
-                     o_sorted = take(T * n * sizeof(uint32_t)), o_cur = take(T * B * sizeof(uint32_t)),
-                     o_start = take(T * (B + 1) * sizeof(uint32_t));
-        ensure_buf(c, c->commit_ws, off);
-        char* ws = (char*)c->commit_ws.p;
-        const NttDev d = ntt_stage(c, cols, ncols, 0, 0, [](Fr*) {});
-        unsigned long long* cnt = (unsigned long long*)c->lkp.p;
-        CommitBatch a{};
-        a.cols = d.cols;
-        a.bases = (const G1Affine*)bases;
-        a.windows = (G1Xyzz*)(ws + o_win);
-        a.slots = (G1Xyzz*)(ws + o_slots);
-        a.buckets = (G1Xyzz*)(ws + o_bkt);
-        a.chunks = (G1Xyzz*)(ws + o_chk);
-        a.sorted = (uint32_t*)(ws + o_sorted);
-        a.cursor = (uint32_t*)(ws + o_cur);
-        a.start = (uint32_t*)(ws + o_start);
-        a.cnt = cnt;
-        a.k = k;
-        a.c = cb;
-        a.W = W;
-        a.ncols = ncols;
-        a.form = form;
-        a.bases_form = bases_form;
-        for (uint64_t g0 = 0; g0 < tasks; g0 += T) {
-            a.g0 = (uint32_t)g0;
-            a.T = (uint32_t)std::min<uint64_t>(T, tasks - g0);
-            profiled(c, "k_commit_batch", (32.0 + 64.0) * a.T * (double)n,
-                     [&] { return launch_commit_batch(a, c->st); });
-        }
-        profiled(c, "k_commit_horner", 128.0 * tasks, [&] {
-            return launch_commit_horner(a.windows, ncols, cb, W, bases_form, (G1Affine*)out, cnt, c->st);
-        });
-        unsigned long long h[3];
-        read_counters(c, cnt, h, 3);
-        result->columns = ncols;
-        result->zero_scalars = h[0];
-        result->identity_bases = h[1];
-        result->identity_outputs = h[2];
-    });
-}
-int svdw_check_commit(svdw_ctx* c, uint32_t k, int form, int bases_form, const void* bases, const void* const* cols,
-                      uint32_t ncols, const void* commitments, svdw_commit_check* result) {
-    return guarded([&] {
-        REQUIRE(result, "null argument");
-        const bool any =
-            commit_args(c, "svdw_check_commit", k, form, bases_form, bases, cols, ncols, commitments, false);
-        memset(result, 0, sizeof *result);
-        if (!any) return;
-        sync(c);
-        const uint64_t n = 1ull << k;
-        const size_t per = (size_t)kCommitScalarBits * commit_check_blocks(n) * sizeof(G1Xyzz);
-        const uint32_t chunk = (uint32_t)std::min<size_t>(std::max<size_t>(((size_t)64 << 20) / per, 1), ncols);   // 64 MiB of partials
-        const NttDev d = ntt_stage(c, cols, ncols, 0, chunk * per, [](Fr*) {});
-        unsigned long long* cnt = (unsigned long long*)c->lkp.p;
-        profiled(c, "k_commit_check_bases", 64.0 * (double)n,
-                 [&] { return launch_commit_check_bases((const G1Affine*)bases, n, bases_form, cnt, c->st); });
-        for (uint32_t c0 = 0; c0 < ncols; c0 += chunk) {
-            const uint32_t nc = std::min(chunk, ncols - c0);
-            profiled(c, "k_commit_check", 254.0 * nc * (double)n * 32.0, [&] {
-                return launch_commit_check(d.cols, (const G1Affine*)bases, (const G1Affine*)commitments, k, c0, nc,
-                                           form, bases_form, (G1Xyzz*)d.free, cnt, c->st);
-            });
-        }
-        unsigned long long h[4];
-        read_counters(c, cnt, h, 4);
-        result->columns_checked = h[0];
-        result->commit_failures = h[1];
-        result->bases_checked = h[2];
-        result->bases_off_curve = h[3];
-    });
-}
-// A probe of the mixed-add rate: `threads` threads each add one affine point
-// `reps` times into a register-resident accumulator; the seconds of the launch.
-int svdw_commit_add_probe(svdw_ctx* c, const void* points, uint32_t npoints, uint64_t threads, uint32_t reps,
-                          double* seconds) {
-    return guarded([&] {
-        REQUIRE(c && points && seconds && npoints && threads && reps, "null argument");
-        REQUIRE(!c->dry, "svdw_commit_add_probe needs a device context");
-        sync(c);
-        ensure_buf(c, c->commit_ws, threads * sizeof(G1Xyzz));
-        hipEvent_t e0, e1;
-        hipck(hipEventCreate(&e0), "hipEventCreate");
-        hipck(hipEventCreate(&e1), "hipEventCreate");
-        hipck(hipEventRecord(e0, c->st), "hipEventRecord");
-        const hipError_t le = launch_commit_add_probe((const G1Affine*)points, npoints, threads, reps,
-                                                      (G1Xyzz*)c->commit_ws.p, c->st);
-        hipError_t re = hipEventRecord(e1, c->st);
-        if (re == hipSuccess) re = hipEventSynchronize(e1);
-        float ms = 0;
-        if (re == hipSuccess) re = hipEventElapsedTime(&ms, e0, e1);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        hipck(le, "k_commit_add_probe");
-        hipck(re, "hipEventElapsedTime");
-        *seconds = ms * 1e-3;
-    });
-}
-// ---- the quotient polynomial on the extended domain and the verifier's identity
-// at a point (quotient.hpp)
-namespace {
-struct QCall {
-    Fr shift, beta, gamma, y, x;                           // canonical
-    uint32_t k = 0, ek = 0, le = 0, D = 0, nsets = 0;
-    uint64_t n = 0, N = 0, usable = 0;
-    std::vector<const void*> ptrs;                         // every column, in the order QuotientArgs::ptrs gives
-};
-}  // namespace
-// The argument checks of svdw_quotient and svdw_check_quotient (x: the latter's,
-// else null; out: the former's), in the order include/svdw.h gives; false: no
-// family, nothing to do.
-static bool q_args(svdw_ctx* c, const char* fn, const svdw_quotient_args* a, const void* out, const uint64_t* x,
-                   QCall* q) {
-    const std::string f(fn);
-    REQUIRE(c && a, "null argument");
-    check_form(a->form);
-    q->shift = fr_raw_words(a->shift);
-    q->beta = fr_raw_words(a->beta);
-    q->gamma = fr_raw_words(a->gamma);
-    q->y = fr_raw_words(a->y);
-    q->x = x ? fr_raw_words(x) : fr_zero();
-    REQUIRE(fr_reduced(q->shift) && !fr_is_zero(q->shift), f + ": shift >= p or shift == 0");
-    REQUIRE(fr_reduced(q->beta) && fr_reduced(q->gamma) && fr_reduced(q->y) && fr_reduced(q->x),
-            f + ": beta, gamma, y or x >= p");
-    const uint64_t rows = a->k < 63 ? 1ull << a->k : ~0ull;
-    if (!a->unusable_rows || a->unusable_rows >= rows) fail(SVDW_ERANGE, f + ": unusable_rows must be in [1, 2^k)");
-    REQUIRE(a->chunk_len || !a->n_perm, f + ": chunk_len == 0");
-    if (a->k < 1 || a->k > 28) fail(SVDW_ERANGE, f + ": k must be in [1, 28]");
-    if (a->extended_k < a->k || a->extended_k > 28) fail(SVDW_ERANGE, f + ": extended_k must be in [k, 28]");
-    q->k = a->k;
-    q->ek = a->extended_k;
-    q->le = q->ek - q->k;
-    q->n = rows;
-    q->N = 1ull << q->ek;
-    q->usable = rows - a->unusable_rows;
-    q->nsets = a->n_perm ? pp_sets(a->n_perm, a->chunk_len) : 0;
-    q->D = std::max({a->n_gate ? 3u : 0u, a->n_lookup ? 4u : 0u,
-                     a->n_perm ? 2u + std::min(a->chunk_len, a->n_perm) : 0u});
-    if (q->D > (1ull << q->le) + 1) fail(SVDW_ERANGE, f + ": the degree does not fit the extended domain (D > E + 1)");
-    {
-        Fr t = fr_to_mont(q->shift);                       // shift^N == 1: shift^n is an E-th root of unity
-        for (uint32_t i = 0; i < q->ek; ++i) t = mont_mul(t, t);
-        REQUIRE(!fr_eq(t, fr_to_mont(fr_from_u64(1))), f + ": shift^n is an E-th root of unity (a zero divisor)");
-    }
-    REQUIRE(!c->dry, f + " needs a device context");
-    if (a->n_gate > 65535 || a->n_perm > 65535 || a->n_lookup > 65535)
-        fail(SVDW_ERANGE, f + ": more than 65535 columns in a family");
-    if (!a->n_gate && !a->n_perm && !a->n_lookup) return false;
-    REQUIRE(out || x, "null argument");
-    const struct {
-        const void* const* p;
-        uint32_t n;
-    } fam[] = {{a->advice, a->n_gate},          {a->selectors, a->n_gate},       {a->perm_columns, a->n_perm},
-               {a->sigma, a->n_perm},           {a->perm_z, q->nsets},           {a->lookup_input, a->n_lookup},
-               {a->lookup_table, a->n_lookup},  {a->permuted_input, a->n_lookup}, {a->permuted_table, a->n_lookup},
-               {a->lookup_z, a->n_lookup}};
-    for (const auto& fm : fam) {
-        REQUIRE(fm.p || !fm.n, "null argument");
-        for (uint32_t j = 0; j < fm.n; ++j) {
-            REQUIRE(fm.p[j], f + ": null column pointer");
-            q->ptrs.push_back(fm.p[j]);
-        }
-    }
-    if (out) {
-        const uintptr_t o0 = (uintptr_t)out, o1 = o0 + q->N * sizeof(Fr);
-        for (const void* p : q->ptrs) {
-            const uintptr_t i0 = (uintptr_t)p, i1 = i0 + q->N * sizeof(Fr);
-            REQUIRE(i1 <= o0 || o1 <= i0, f + ": h_ext overlaps an input column");
-        }
-    }
-    return true;
-}
-// The extended columns of l_0, l_last, l_active (R form, 3 x N cells) for the
-// call's key: three Lagrange columns through the engine's own inverse and coset
-// transforms, kept on the context until the key changes.
-static const Fr* q_basis(svdw_ctx* c, const QCall& q, uint32_t unusable_rows) {
-    const size_t need = 3 * q.N * sizeof(Fr);
-    if (c->q_l.cap >= need && c->q_k == q.k && c->q_ek == q.ek && c->q_unusable == unusable_rows &&
-        fr_eq(c->q_shift, q.shift))
-        return (const Fr*)c->q_l.p;
-    c->q_k = 0;                                            // no key while the columns are rebuilt
-    ensure_buf(c, c->q_l, need);
-    ensure_buf(c, c->q_tmp, 6 * q.n * sizeof(Fr));
-    Fr* lag = (Fr*)c->q_tmp.p;
-    Fr* cf = lag + 3 * q.n;
-    profiled(c, "k_quotient_basis", 96.0 * q.n, [&] {
-        return launch_quotient_basis(lag, q.n, q.usable, fr_to_mont(fr_from_u64(1)), c->st);
-    });
-    const void* in[3] = {lag, lag + q.n, lag + 2 * q.n};
-    const void* mid[3] = {cf, cf + q.n, cf + 2 * q.n};
-    uint64_t sh[4];
-    fr_store_words(q.shift, sh);
-    svdw_ntt_result r;
-    int rc = svdw_ntt(c, q.k, q.k, SVDW_FORM_MONTGOMERY, 1, nullptr, in, 3, cf, &r);
-    if (rc == SVDW_OK) rc = svdw_ntt(c, q.k, q.ek, SVDW_FORM_MONTGOMERY, 0, sh, mid, 3, c->q_l.p, &r);
-    if (rc != SVDW_OK) fail(rc, g_err);
-    c->q_k = q.k;
-    c->q_ek = q.ek;
-    c->q_unusable = unusable_rows;
-    c->q_shift = q.shift;
-    return (const Fr*)c->q_l.p;
-}
-int svdw_quotient(svdw_ctx* c, const svdw_quotient_args* args, void* h_ext, svdw_quotient_result* result) {
-    return guarded([&] {
-        REQUIRE(result, "null argument");
-        QCall q;
-        const bool any = q_args(c, "svdw_quotient", args, h_ext, nullptr, &q);
-        memset(result, 0, sizeof *result);
-        result->rows = q.N;
-        result->extension = 1u << q.le;
-        result->degree = q.D;
-        if (!any) return;
-        REQUIRE(h_ext, "null output");
-        sync(c);
-        const bool mont = args->form == SVDW_FORM_MONTGOMERY;
-        const uint32_t ng = args->n_gate, np = args->n_perm, nl = args->n_lookup, E = 1u << q.le;
-        const Fr* l = (np | nl) ? q_basis(c, q, args->unusable_rows) : nullptr;
-        const uint32_t h = pp_split(q.ek);
-        const Fr* tab = ntt_tables(c, q.ek);
-        const Fr one = fr_to_mont(fr_from_u64(1));
-        // the staged cells: beta delta^j phi for j < np, then the E inverses of the divisor as c R
-        const NttDev d = ntt_stage(c, q.ptrs.data(), (uint32_t)q.ptrs.size(), (size_t)np + E, 0, [&](Fr* t) {
-            pp_delta_powers(q.beta, args->form, np, t);
-            Fr* inv = t + np;
-            Fr sn = fr_to_mont(q.shift), wn = pp_omega_mont(q.ek);   // shift^n R, omega_e^n R
-            for (uint32_t i = 0; i < q.k; ++i) {
-                sn = mont_mul(sn, sn);
-                wn = mont_mul(wn, wn);
-            }
-            // batch inversion: prefix products, one inverse, back substitution
-            std::vector<Fr> dv(E), pre(E);
-            Fr acc = one;
-            for (uint32_t i = 0; i < E; ++i) {
-                dv[i] = fr_sub(sn, one);                   // (shift^n omega_e^(n i) - 1) R, not zero (q_args)
-                pre[i] = acc;
-                acc = mont_mul(acc, dv[i]);
-                sn = mont_mul(sn, wn);
-            }
-            Fr ia = fr_to_mont(fr_to_mont(fr_inv(acc)));    // acc = P R: (P R)^-1 R^2 = P^-1 R
-            for (uint32_t i = E; i-- > 0;) {
-                inv[i] = mont_mul(ia, pre[i]);
-                ia = mont_mul(ia, dv[i]);
-            }
-        });
-        QuotientArgs a{};
-        a.ptrs = d.cols;
-        a.bd = d.cells;
-        a.inv = d.cells + np;
-        a.wlo = tab + 1024;
-        a.whi = a.wlo + ((size_t)1 << h);
-        a.l0 = l;
-        a.llast = l ? l + q.N : nullptr;
-        a.lact = l ? l + 2 * q.N : nullptr;
-        a.out = (Fr*)h_ext;
-        a.y = fr_to_mont(q.y);
-        a.beta = fr_to_mont(q.beta);
-        a.shift = fr_to_mont(q.shift);
-        a.gamma = mont ? fr_to_mont(q.gamma) : q.gamma;
-        a.betaf = mont ? a.beta : q.beta;
-        a.one = mont ? one : fr_from_u64(1);
-        a.ek = q.ek;
-        a.le = q.le;
-        a.h = h;
-        a.ng = ng;
-        a.np = np;
-        a.chunk = args->chunk_len;
-        a.nsets = q.nsets;
-        a.nl = nl;
-        a.usable = q.usable;
-        const double cols = 5.0 * ng + 2.0 * np + 3.0 * q.nsets + 7.0 * nl + ((np | nl) ? 3.0 : 0.0) + 1.0;
-        profiled(c, "k_quotient", 32.0 * cols * (double)q.N, [&] { return launch_quotient(a, args->form, c->st); });
-        result->gate_expressions = ng;
-        result->permutation_expressions = np ? 1 + 2 * (uint64_t)q.nsets : 0;
-        result->lookup_expressions = 5 * (uint64_t)nl;
-    });
-}
-// l_i(x) R for x^n != 1: omega^i (x^n - 1) / (n (x - omega^i)); t = (x^n - 1) / n as t R.
-static Fr q_lagrange_at(const Fr& xR, const Fr& wiR, const Fr& tR) {
-    const Fr inv = fr_to_mont(fr_inv(fr_from_mont(fr_sub(xR, wiR))));
-    return mont_mul(mont_mul(wiR, tR), inv);
-}
-int svdw_check_quotient(svdw_ctx* c, const svdw_quotient_args* args, const void* h_coeffs, const uint64_t x[4],
-                        svdw_quotient_check* result) {
-    return guarded([&] {
-        REQUIRE(result && x, "null argument");
-        QCall q;
-        const bool any = q_args(c, "svdw_check_quotient", args, nullptr, x, &q);
-        memset(result, 0, sizeof *result);
-        if (!any) return;
-        REQUIRE(h_coeffs, "null argument");
-        sync(c);
-        const bool mont = args->form == SVDW_FORM_MONTGOMERY;
-        const uint32_t ng = args->n_gate, np = args->n_perm, nl = args->n_lookup, ns = q.nsets;
-        const Fr one = fr_to_mont(fr_from_u64(1));
-        // the points x omega^r R, r in {0, 1, 2, 3, -1, usable}
-        constexpr uint32_t kPts = 6;
-        const Fr xR = fr_to_mont(q.x), w = pp_omega_mont(q.k);
-        const Fr wu = fr_to_mont(fr_pow_u64(fr_from_mont(w), q.usable)), wm = fr_to_mont(fr_pow_u64(fr_from_mont(w), q.n - 1));
-        const Fr w2 = mont_mul(w, w);
-        const Fr pts[kPts] = {xR, mont_mul(xR, w), mont_mul(xR, w2), mont_mul(xR, mont_mul(w2, w)), mont_mul(xR, wm),
-                              mont_mul(xR, wu)};
-        // every column at every point, in chunks of columns; the values as v R
-        const size_t total = q.ptrs.size();
-        std::vector<Fr> vals(total * kPts);
-        constexpr size_t kColChunk = 16384;
-        for (size_t c0 = 0; c0 < total; c0 += kColChunk) {
-            const uint32_t nc = (uint32_t)std::min(kColChunk, total - c0);
-            const size_t part = (size_t)nc * kPts * ntt_eval_blocks(q.n) * sizeof(Fr), outb = (size_t)nc * kPts * sizeof(Fr);
-            const NttDev d = ntt_stage(c, q.ptrs.data() + c0, nc, kPts, part + outb, [&](Fr* t) {
-                for (uint32_t i = 0; i < kPts; ++i) t[i] = pts[i];
-            });
-            Fr* dout = (Fr*)(d.free + part);
-            ntt_eval_chunks(c, d.cols, nullptr, q.n, nc, d.cells, kPts, kPts, (Fr*)d.free, kPts, dout, true,
-                            [](uint64_t, uint32_t) {});
-            hipck(hipMemcpyAsync(vals.data() + c0 * kPts, dout, outb, hipMemcpyDeviceToHost, c->st), "D2H");
-            hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
-        }
-        // h at x, and its tail counted on the device
-        Fr hx;
-        unsigned long long tail[2];
-        {
-            const size_t part = (size_t)ntt_eval_blocks(q.N) * sizeof(Fr);
-            const NttDev d = ntt_stage(c, &h_coeffs, 1, 1, part + sizeof(Fr), [&](Fr* t) { t[0] = xR; });
-            Fr* dout = (Fr*)(d.free + part);
-            ntt_eval_chunks(c, d.cols, nullptr, q.N, 1, d.cells, 1, 1, (Fr*)d.free, 1, dout, true,
-                            [](uint64_t, uint32_t) {});
-            unsigned long long* cnt = (unsigned long long*)c->lkp.p;
-            const uint64_t from = (uint64_t)q.D * (q.n - 1) + 1 - q.n;   // D >= 2: not negative
-            profiled(c, "k_quotient_tail", 32.0 * (double)(q.N - from),
-                     [&] { return launch_quotient_tail((const Fr*)h_coeffs, from, q.N, cnt, c->st); });
-            hipck(hipMemcpyAsync(&hx, dout, sizeof(Fr), hipMemcpyDeviceToHost, c->st), "D2H");
-            read_counters(c, cnt, tail, 2);
-        }
-        if (!mont) {
-            for (Fr& v : vals) v = fr_to_mont(v);
-            hx = fr_to_mont(hx);
-        }
-        // l_0, l_last, l_active at x by the closed form
-        Fr xn = xR;
-        for (uint32_t i = 0; i < q.k; ++i) xn = mont_mul(xn, xn);
-        const Fr xn1 = fr_sub(xn, one);
-        Fr l0, ll, la = one;
-        {
-            const bool on_domain = fr_is_zero(xn1);       // x = omega^i: l_i(x) = 1 there and 0 elsewhere
-            const Fr t = mont_mul(xn1, fr_to_mont(fr_inv(fr_from_u64(q.n))));
-            l0 = on_domain ? (fr_eq(xR, one) ? one : fr_zero()) : q_lagrange_at(xR, one, t);
-            ll = fr_zero();
-            Fr wi = wu;
-            for (uint64_t i = q.usable; i < q.n; ++i) {
-                const Fr li = on_domain ? (fr_eq(xR, wi) ? one : fr_zero()) : q_lagrange_at(xR, wi, t);
-                if (i == q.usable) ll = li;
-                la = fr_sub(la, li);
-                wi = mont_mul(wi, w);
-            }
-        }
-        // the fold, include/svdw.h's list in its order
-        const Fr b = fr_to_mont(q.beta), g = fr_to_mont(q.gamma), y = fr_to_mont(q.y);
-        size_t base[10];
-        {
-            const uint32_t cnt[10] = {ng, ng, np, np, ns, nl, nl, nl, nl, nl};
-            size_t at = 0;
-            for (int i = 0; i < 10; ++i) {
-                base[i] = at;
-                at += cnt[i];
-            }
-        }
-        enum { ADV, SEL, PV, SIG, PZ, LA, LT, LAP, LSP, LZ };
-        enum { X0, X1, X2, X3, XM, XU };
-        auto val = [&](int fam, size_t i, int pt) { return vals[(base[fam] + i) * kPts + pt]; };
-        Fr h = fr_zero();
-        auto push = [&](const Fr& e) { h = fr_add(mont_mul(h, y), e); };
-        for (uint32_t i = 0; i < ng; ++i)
-            push(mont_mul(val(SEL, i, X0),
-                          fr_sub(fr_add(val(ADV, i, X0), mont_mul(val(ADV, i, X1), val(ADV, i, X2))), val(ADV, i, X3))));
-        if (np) {
-            push(mont_mul(l0, fr_sub(one, val(PZ, 0, X0))));
-            const Fr zl = val(PZ, ns - 1, X0);
-            push(mont_mul(ll, fr_sub(mont_mul(zl, zl), zl)));
-            for (uint32_t s = 1; s < ns; ++s) push(mont_mul(l0, fr_sub(val(PZ, s, X0), val(PZ, s - 1, XU))));
-            Fr bd = b;                                     // beta delta^j R
-            const Fr dl = fr_to_mont(pp_consts().delta);
-            for (uint32_t s = 0; s < ns; ++s) {
-                Fr left = val(PZ, s, X1), right = val(PZ, s, X0);
-                for (uint32_t j = s * args->chunk_len; j < std::min<uint64_t>((uint64_t)(s + 1) * args->chunk_len, np); ++j) {
-                    const Fr v = fr_add(val(PV, j, X0), g);
-                    left = mont_mul(left, fr_add(v, mont_mul(b, val(SIG, j, X0))));
-                    right = mont_mul(right, fr_add(v, mont_mul(bd, xR)));
-                    bd = mont_mul(bd, dl);
-                }
-                push(mont_mul(la, fr_sub(left, right)));
-            }
-        }
-        for (uint32_t i = 0; i < nl; ++i) {
-            const Fr z = val(LZ, i, X0), ap = val(LAP, i, X0), sp = val(LSP, i, X0);
-            push(mont_mul(l0, fr_sub(one, z)));
-            push(mont_mul(ll, fr_sub(mont_mul(z, z), z)));
-            const Fr left = mont_mul(val(LZ, i, X1), mont_mul(fr_add(ap, b), fr_add(sp, g)));
-            const Fr right = mont_mul(z, mont_mul(fr_add(val(LA, i, X0), b), fr_add(val(LT, i, X0), g)));
-            push(mont_mul(la, fr_sub(left, right)));
-            const Fr d = fr_sub(ap, sp);
-            push(mont_mul(l0, d));
-            push(mont_mul(la, mont_mul(d, fr_sub(ap, val(LAP, i, XM)))));
-        }
-        const Fr lhs = fr_from_mont(mont_mul(hx, xn1)), rhs = fr_from_mont(h);
-        fr_store_words(lhs, result->lhs);
-        fr_store_words(rhs, result->rhs);
-        result->identity_failures = !fr_eq(lhs, rhs);
-        result->tail_checked = tail[0];
-        result->tail_nonzero = tail[1];
     });
 }
 int svdw_rlc_trace(const svdw_ctx* c, uint64_t* cells, uint64_t* copies, uint32_t* n) {

@@ -1,0 +1,471 @@
+// What engine.cpp (the witness engine) and prover.cpp (the prover calls) share:
+// the error plumbing of the C ABI, device buffers, the host Fr helpers of the
+// entry points, the prover calls' state, the context (svdw_ctx) and the few
+// engine.cpp functions on it that prover.cpp calls.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <array>
+#include <chrono>
+#include <functional>
+#include <new>
+#include <set>
+#include <stdexcept>
+#include <string>
+#include <tuple>
+#include <vector>
+
+#include "../../include/svdw.h"
+#include "kernels.hpp"
+
+using namespace svdw;                                      // (both files are the engine's own)
+
+// ------------------------------------------------------------------ errors
+inline thread_local std::string g_err;
+struct SvdwError {
+    int code;
+    std::string msg;
+};
+[[noreturn]] inline void fail(int code, const std::string& msg) { throw SvdwError{code, msg}; }
+inline void hipck(hipError_t e, const char* what) {
+    if (e != hipSuccess) fail(SVDW_EDEVICE, std::string(what) + ": " + hipGetErrorString(e));
+}
+template <class F>
+int guarded(F&& f) {
+    try {
+        f();
+        return SVDW_OK;
+    } catch (const SvdwError& e) {
+        g_err = e.msg;
+        return e.code;
+    } catch (const std::bad_alloc&) {
+        g_err = "out of host memory";
+        return SVDW_ENOMEM;
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return SVDW_EINVAL;
+    }
+}
+#define REQUIRE(cond, msg) \
+    do {                   \
+        if (!(cond)) fail(SVDW_EINVAL, msg); \
+    } while (0)
+
+// A device allocation that only grows (ensure_buf).
+struct DBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+};
+
+// ------------------------------------------- host Fr helpers of the entries
+inline void check_form(int form) {
+    REQUIRE(form == SVDW_FORM_CANONICAL || form == SVDW_FORM_MONTGOMERY,
+            "unknown form (SVDW_FORM_CANONICAL or SVDW_FORM_MONTGOMERY)");
+}
+// The four 64-bit words as they are (not reduced: fr_reduced).
+inline Fr fr_raw_words(const uint64_t w[4]) {
+    Fr x;
+    for (int i = 0; i < 8; ++i) x.w[i] = (uint32_t)(w[i / 2] >> (32 * (i & 1)));
+    return x;
+}
+inline void fr_store_words(const Fr& x, uint64_t w[4]) {
+    for (int i = 0; i < 4; ++i) w[i] = (uint64_t)x.w[2 * i] | ((uint64_t)x.w[2 * i + 1] << 32);
+}
+inline bool fr_reduced(const Fr& x) {
+    Fr t;
+    return sub_p(t, x) != 0;                               // x - p borrows: x < p
+}
+
+// ------------------------------------------------- prover calls' state
+// What the prover calls (prover.cpp) keep on a context between calls.
+struct ProverState {
+    // every call's device scratch, in the staged-call layout: counters,
+    // pointers, Fr cells, then the call's own arrays
+    DBuf scratch;
+    std::vector<char> upload;               // host staging of a call's pointers and cells
+    std::vector<Fr> omega;                  // host: the two-level omega tables of the domain 2^omega_k
+    uint32_t omega_k = 0;
+    DBuf ntt_tab, ntt_tmp;                  // transforms (ntt.hpp): the stage and omega tables of ntt_k on the
+    uint32_t ntt_k = 0;                     // device; the buffer between passes
+    DBuf commit_ws;                         // commitments (commit.hpp): the window sums and one batch of tasks
+    // quotient (quotient.hpp): the extended columns of l_0, l_last, l_active (R form) of the key below, and the
+    // scratch they are built in
+    DBuf basis, basis_tmp;
+    uint32_t basis_k = 0, basis_ek = 0, basis_unusable = 0;
+    Fr basis_shift{};
+    std::vector<DBuf*> dbufs() { return {&scratch, &ntt_tab, &ntt_tmp, &basis, &basis_tmp, &commit_ws}; }
+};
+
+// -------------------------------------------------------------- context
+struct Stream {
+    Fr* adv = nullptr;
+    uint64_t n = 0, cap = 0;
+    Fr* lk = nullptr;
+    uint64_t nl = 0, lcap = 0;
+};
+struct svdw_ctx {
+    // ---- options: svdw_set_option (kOptions), svdw_set_gemm_impl, svdw_set_shard,
+    // the profiler switches; a lane takes them over as a whole (copy_settings)
+    struct Options {
+        int gemm_impl = SVDW_GEMM_MFMA;         // svdw_set_gemm_impl
+        // STAGE_* (4 KiB-aligned block store windows; "stage_rot" 1: phase B from a
+        // block-dependent window on, tools/r6/place_ab.py over 8 placements of the
+        // 1024^2 cell streams: 1.739-1.891 -> 1.728-1.825 ms, mean 1.815 -> 1.751)
+        uint32_t stage_flags = STAGE_ALIGN | STAGE_ROT;
+        uint32_t stage_elems = kStageElems;     // "stage_elems": elements per stage block (16..256)
+        int gemm_crt = 1;                       // "gemm_crt": multi-modular GEMM (else digits)
+        // "gemm_kern": CRT GEMM kernel (CrtBatch::kern); -1: wide tiles or the
+        // persistent grid for a product queued on its own (svdw_honest_prover_mat_mul,
+        // gemm_solo; CrtBatch::kern 3), one block per unit inside the witness calls,
+        // beside their stage kernels
+        int gemm_kern = -1;
+        int res_wait = -1;                      // "res_wait": stages wait for the residue planes
+        int place_trials = 6;                   // "place_trials": candidate placements of a new cell stream
+        bool res_f64 = true;                    // "res_f64": CRT residue planes of m, u, v from the
+                                                // f64 inputs, one launch (else from the cells)
+        int phase1_overlap = 1;                 // "phase1_overlap": 0 off, 1 on st2 behind the
+                                                // GEMMs, 2 on st3 from quantization on
+        int prod_cell = 1;                      // "prod_cell": svd_witness's products (residues, GEMM,
+                                                // combine) on the cell stream and the u / v bounds and
+                                                // u.d beside them on st2 (1), not (0); -1: on row-sharded
+                                                // ranks only. On by default: the product chain is the
+                                                // critical path sharded, and unsharded it measured
+                                                // 2.5 % faster at 1024^2 and 2048^2, neutral at 512^2
+        uint32_t hold_us = 0;                   // "hold_us": timing aid, st spins this long first
+        uint32_t commit_window_bits = 0;        // "commit_window_bits": svdw_commit's window, 0: svdw_commit_plan's
+                                                // (a tuning aid, tools/commit_bench.py; the result reports it)
+        uint32_t commit_scratch_mib = 1024;     // "commit_scratch_mib": svdw_commit's workspace cap per batch of tasks
+        bool rlc_prefix = false;                // "rlc_prefix": svd_witness's phase 1 starts with the
+                                                // ctx_gate cells of load_rlc_cache(.., 1)
+        int p1_at = -1;                         // "p1_at": phase 1 on st3 (mode 2) enqueued after
+                                                // phase-0 stage 0 / 1 / 2 (the u, v bounds), 3: at the
+                                                // end; -1: auto (tools/shard_sim.py --opt p1_at=):
+                                                // 0 on a rank of >= 4, 3 of 2-3, else 1
+        // pipelined svd_witness: "dchk_at" the d checks on the cell stream behind
+        // the products (0), on st2 with the bounds and u.d (1) or on st3 ahead of
+        // phase 1 (2); "gamma_at" k_gamma_prep at the head of the cell stream (0) or
+        // of st3 (1); -1: st3 on a row-sharded rank, whose cell stream (quantize ->
+        // residues -> GEMM -> combine, then the diff on st2) is the step's chain
+        // (8-way rank 0.331 -> 0.316-0.321 ms; 1024^2 / 512^2 +0.5 %, r5p / r5q)
+        int dchk_at = 0, gamma_at = -1;
+        bool f64_views = true;                  // "f64_views": launches read registered f64 inputs (f64_view)
+        bool overlap = true;                    // "overlap": products queued ahead of the check stages
+        bool stage_batch = true;                // "stage_batch": stage launches share k_stage_multi (BatchScope)
+        int graph_vm = 1;                       // "graph": 0 off, 1 verify_mul_witness captured (vm_graph)
+        // "vm_linear": the captured verify_mul_witness runs on the context stream
+        // alone (st2 = st3 = st while it is queued: a linear graph, no fork / join
+        // events); concurrency comes from the two lanes instead.
+        int vm_linear = 1;
+        int pipeline = 1;                       // "pipeline": 1 on, 0 off (svd_witness_pipe, below)
+        // Row-block sharding of one witness: this context computes the
+        // rows [R rank / world, R (rank + 1) / world) of every row-parallel stage
+        // (R = that stage's row count) into the globally laid-out streams; shared
+        // inputs (quantized operands, single constants, the Freivalds b.g values)
+        // are computed in full. `owned` lists the cell ranges this rank is the
+        // source of, for reassembly.
+        uint32_t shard_rank = 0, shard_world = 1;
+        // built-in event profiler (svdw_profile_*): one start/stop event pair per launch
+        bool prof = false;
+        std::string prof_filter;                // record only kernels whose name starts with this
+        // SVDW_HOST_TRACE=1: host-side timestamps of svd_witness's enqueue points on
+        // stderr (µs since the call started), to find host waits inside a call
+        bool host_trace = false;
+        auto tied() const {
+            return std::tie(gemm_impl, stage_flags, stage_elems, gemm_crt, gemm_kern, res_wait, place_trials,
+                            res_f64, phase1_overlap, prod_cell, hold_us, rlc_prefix, p1_at, dchk_at, gamma_at,
+                            f64_views, overlap, stage_batch, graph_vm, vm_linear, pipeline, shard_rank,
+                            shard_world, prof, prof_filter, host_trace);
+        }
+        bool operator==(const Options& o) const { return tied() == o.tied(); }
+    } opt;
+    // ---- one witness call (svd_witness, verify_mul_witness): meaningful while the
+    // call is being enqueued. Each call sets it from scratch (begin_call, then the
+    // call's own code); CallEnd drops what must not outlive the call.
+    struct PreGemm {
+        uint64_t off;
+        hipEvent_t ev;
+        hipStream_t st;                     // the stream it was launched on
+    };
+    // svd_witness's quantized matrices and their device f64 inputs (u, v): a
+    // row-sharded rank takes b.g of b = u^T, v^T from the f64 rows directly
+    // (k_colsum_f64), not from cells. Cleared at the end of the witness.
+    struct F64Src { svdw_mat m; const double* x; };
+    // loaded regions whose f64 source is on the device for the current call:
+    // launches read them through VIEW_F64 (quantized in registers) instead of
+    // waiting for the quantized cells (f64_view)
+    struct F64Region { uint32_t phase; uint64_t off, n; const double* x; };
+    struct Call {
+        bool in_pipe = false;                   // inside a pipelined svd_witness
+        bool prelaunched = false;               // this witness's products were queued on st2
+        bool prod_on_cell = false;              // this witness's products went on the cell stream
+        bool gemm_batched = false;              // this witness's products went out as one batch
+        std::vector<PreGemm> pre;               // GEMMs launched ahead on st2, in append order
+        hipStream_t pre_wait_st = nullptr;      // the last (stream, event) waited on for them
+        hipEvent_t pre_wait_ev = nullptr;
+        std::vector<hipEvent_t> gemm_done;      // their completion events (this witness)
+        std::vector<hipEvent_t> wait_before_cs; // verify_mul_many: wait before the c_s scans
+        const double* svd_f64[3] = {nullptr, nullptr, nullptr};   // device f64 m, u, v of svd_witness
+        std::vector<F64Region> f64reg;
+        std::vector<F64Src> f64src;
+        std::function<void(const svdw_svd_payload&)> early_p1;   // phase 1's enqueue at p1_at (svd_witness)
+        bool stage_front = false;               // stage_launch: the stage goes ahead of the batch's groups
+        // verify_mul_witness: the one cell and gamma powers written by k_gamma_prep
+        // (phase-1 offsets one_off / pows_off for d), so verify_mul does not launch them
+        struct PowsPre {
+            bool on = false;
+            uint64_t one_off = 0, pows_off = 0;
+            uint32_t d = 0;
+        } pows_pre;
+        // the captured verify_mul_witness (vm_graph): `linear` is set while a
+        // vm_linear call is queued (stream_dep returns lin_ev, never recorded, and
+        // dep_wait skips it)
+        bool linear = false;
+        bool capturing = false;                 // st is capturing: no allocation, no sync
+        bool gp_external = false;               // k_gamma_prep already queued ahead of the graph
+        const Fr* gp_ext_one = nullptr;         // the one cell it wrote (null: none)
+    } call;
+    // ---- the handle: parameters, streams, cells, caches, scratch
+    std::chrono::steady_clock::time_point ht0;   // host_trace: when the call started
+    int device = -1;
+    bool dry = true;
+    hipStream_t st = nullptr;
+    uint32_t P = 32, LB = 19;
+    Stream ph[2];
+    // Pipelined svd_witness ("pipeline", svd_witness_pipe): consecutive
+    // witnesses alternate between two sets of cell streams (ph and alt), so call
+    // j's product chain (st) runs beside call j - 1's HBM-bound stages (st2) and
+    // row scans (st3) instead of after them. Call j's st first waits for call
+    // j - 2's tail (tail_ev[parity]: its last work on st2 / st3), the last user
+    // of this cell set and of this half of the bit-length words. Anything else
+    // that touches the streams after a pipelined call settles first (settle).
+    Stream alt[2];
+    int pipe_par = 0;                       // this call's parity (cell set, bit words)
+    hipEvent_t tail_ev[2][2] = {};          // [parity][st2, st3]
+    bool tail_valid[2] = {false, false};
+    bool tail_pending = false;              // the last pipelined call's tail not yet joined into st
+    int tail_last = 0;
+    size_t mem_total = 0;                   // device memory (hipMemGetInfo at create)
+    // "lanes" 2: svdw_verify_mul_witness on its captured-graph path alternates
+    // between two complete context states, this one and `lane` (own streams,
+    // cells, scratch, graph). The states are exchanged (std::swap) at the start
+    // of a call, so call j + 1 runs on the other state's streams beside call j
+    // and the handle always holds the latest call's cells. sync, stream_wait,
+    // stream_signal, graph_stats and destroy cover both; lane / lanes stay with
+    // the handle.
+    int lanes = 2;                          // (config 2, same box: 0.081 -> 0.058 ms per call)
+    svdw_ctx* lane = nullptr;
+    // svdw_stream_wait's event (the caller's stream), not yet waited on by
+    // st2 / st3: st waits at once; the side streams inherit it through
+    // after_previous or the captured graph's fork from st, and the pipelined
+    // svd_witness (whose side streams do not wait for st) waits explicitly
+    hipEvent_t xwait_side = nullptr;
+    DBuf f64in, digA, digB, digC, w1c, w1t, w2c, w2t, bits, gpc, gtab, crtR, gbits, chk, chkg;
+    DBuf gpc_alt, gtab_alt;                 // pipelined svd_witness: gamma tables of the other parity
+    DBuf wbc[kMaxScanJobs], wbt[kMaxScanJobs];   // b.v per batched verify_mul (canonical, table)
+    // gamma^j (canonical gpc, scaled table gtab, kernels.hpp kTabSlots) of the
+    // current verify_mul calls: recomputed for every witness (a fresh challenge
+    // each time). svd_witness queues it first thing on a side stream (gp_ev).
+    Fr gp_gamma{};
+    uint32_t gp_len = 0;
+    hipEvent_t gp_ev = nullptr;
+    hipStream_t gp_st = nullptr;            // the stream gp_ev was recorded on
+    // Device bit-length words of matrices written in this witness (svd_witness:
+    // quantized m, u, v at dbitw[0..2]): the row scans decide their operand
+    // width on the device from these (NaSpec), so the host never waits for them.
+    struct DevBits { svdw_mat m; int16_t word; };
+    std::vector<DevBits> dwords;
+    const unsigned* dbitw = nullptr;
+    // Known magnitude bounds of matrices written in this witness: cell (i, j) of
+    // `m` satisfies |signed value| < 2^bits. Cleared with the streams.
+    struct MatBits { svdw_mat m; uint32_t bits; };
+    std::vector<MatBits> mbits;
+    // products c_s = a * b (K = 2^lk-bounded inner dimension): |c_s| < 2^(bits_a + bits_b + lk)
+    struct Prod { svdw_mat cs, a, b; uint32_t lk; };
+    std::vector<Prod> prods;
+    // svd_witness: bit lengths of quantized m, u, v travel to pinned host memory
+    // behind ev_bits; the host waits for them only where the GEMM launches need
+    // them (fetch_bits), with check stages already queued on the device.
+    uint32_t* hbits = nullptr;
+    hipEvent_t ev_bits = nullptr;
+    bool bits_pending = false;
+    uint32_t qbits[3] = {0, 0, 0};
+    svdw_mat qmat[3] = {};
+    // the event profiler's records (opt.prof): one start/stop event pair per launch
+    struct Rec {
+        std::string name;
+        double bytes, ops;
+        hipEvent_t e0, e1;
+    };
+    std::vector<Rec> recs;
+    std::vector<hipEvent_t> pool;
+    hipStream_t stream_id[3] = {};          // st, st2, st3 as created (st / st2 / st3 are swapped at times)
+    bool gemm_solo = false;                 // svdw_honest_prover_mat_mul: a product queued on its own (gemm_kern)
+    Fr ext_gamma{};                          // init_rand of the last verify_mul (equality source 2)
+    uint64_t ext_off = 0;                    // its cell in the RLC context
+    // ctx_rlc of the last svd_witness with rlc_prefix: [E(one), E(zero), W(gamma)]
+    // and the phase-1 offsets of the two ctx_gate constants its first cells copy
+    struct RlcTrace {
+        uint32_t n = 0;
+        Fr cells[3];
+        uint64_t src[2];
+    } rlc;
+    // Host-side replays cached for repeated calls of the same shape: the dry
+    // plan of svd_witness's stream sizes (key: N, M, config) and prelaunch's
+    // product offsets (key: stream state at entry, operand views, bounds).
+    std::vector<uint64_t> plan_key, plan_val, log_key, log_val;
+    struct Seg { uint32_t phase, lookup; uint64_t off, n; };
+    std::vector<Seg> owned;                 // row-sharded: the cell ranges this rank is the source of
+    DBuf bvfull[kMaxScanJobs];              // shard mode: full b.g values per verify_mul
+    DBuf colpart;
+    DBuf qfold;                             // k_quantize_multi's fold counters + group maxima
+    // second stream: GEMMs overlap the HBM-bound stages; third: phase 1
+    hipStream_t st2 = nullptr;
+    hipStream_t st3 = nullptr;
+    hipStream_t st_cell = nullptr;          // the cell stream proper (st is swapped at times)
+    hipEvent_t xev[4] = {};                 // svdw_stream_wait / _signal (caller's stream)
+    // svdw_mark ring: slot k holds ticket t[k]'s events (one per stream of
+    // both lanes), recorded on the context's own streams (no waits); it stays
+    // with the handle when lanes exchange states (lane_switch)
+    static constexpr int kMarks = 16;
+    struct Marks {
+        hipEvent_t ev[kMarks][6] = {};
+        uint64_t t[kMarks] = {};
+        uint8_t used[kMarks] = {};
+        uint64_t seq = 0;
+    } mk;
+    std::vector<svdw_region> layout;        // every appended region of the current witness
+    // per region: gate offsets within one element's cells and cells per element
+    // (program regions; empty otherwise; svdw_check_gates)
+    std::vector<RegionChecks> layout_chk;
+    // distinct constant cell values (halo2-base Constant / load_constant):
+    // the fixed-column count of svdw_physical_layout
+    std::set<std::array<uint32_t, 8>> consts;
+    // svdw_physical_layout's plan: per phase, the virtual index of each advice
+    // column's row 0 and each full column's break point
+    struct Phys {
+        bool valid = false;
+        uint32_t k = 0, min_rows = 0;
+        uint64_t R = 0;
+        std::vector<uint64_t> start[2], bp[2];
+    } phys;
+    DBuf gateq[2];
+    std::vector<uint64_t>* gemm_log = nullptr;   // dry run: offsets of honest_prover_mat_mul
+    std::vector<hipEvent_t> deps;           // dependency events (no timing)
+    size_t dep_next = 0;
+    // Stage batches (BatchScope, "stage_batch"): stage launches on a stream with
+    // an open batch are collected and issued as k_stage_multi launches when the
+    // scope closes, when a stage reads cells a pending stage writes, or before
+    // anything else is recorded or launched on that stream.
+    struct Pending {
+        StageArgs a;
+        std::string name;
+        double bytes;
+    };
+    // A batch holds groups issued in order, one k_stage_multi launch each: a
+    // stage joins the group after the last one holding a stage whose cells it
+    // reads, so a dependent stage (entries_in_desc_order's range checks of its
+    // subtractions) defers only itself, not the independent stages after it.
+    struct Batch {
+        hipStream_t st;
+        std::vector<std::vector<Pending>> groups;
+        size_t last = 0;                   // group of the latest stage
+    };
+    std::vector<Batch> batches;
+    // device ingest (svdw_parse_svd_input_device) scratch
+    DBuf ing_x, ing_e, ing_c, ing_p10, ing_val, ing_npos, ing_nd, ing_rpos, ing_kpos, ing_err, ing_q;
+    // device equality records (eq_gen_device)
+    DBuf eq_cp, eq_ks, eq_reg, eq_w, eq_k, eq_err, eq_st;
+    // read-out (svdw_copy_cells, the host variants of svdw_export_* / svdw_dequantize_*):
+    // two staging halves of at most kExportChunk bytes each, and the events that
+    // order them ([0..1] half converted, [2..3] half copied out, [4..5] the join
+    // of st2 / st3 into st ahead of every read-out)
+    DBuf exp_buf[2];
+    ProverState prover;                     // the prover calls (prover.cpp)
+    hipEvent_t exp_ev[6] = {};
+    // ---- captured verify_mul_witness ("graph", vm_graph): the launch sequence of
+    // a device-input call is captured once into a HIP graph (the second call of
+    // a shape, when every buffer is sized) and replayed by later calls of the
+    // same key; gamma enters only through k_gamma_prep, launched eagerly on st
+    // ahead of the graph (gp_external), so the graph itself is gamma-free.
+    hipEvent_t lin_ev = nullptr;            // "vm_linear": stream_dep's placeholder (call.linear)
+    uint64_t epoch = 0;                     // bumped by every allocation / option change
+    // (layout_chk index, eqk slot) of the constants that hold gamma (the
+    // verify_mul gamma powers' init_rand), patched on replay
+    std::vector<std::pair<size_t, int>> gamma_slots;
+    struct VmGraph {
+        std::vector<uint64_t> key, seen;    // replay key; the last eager call's key
+        hipGraphExec_t exec = nullptr;
+        // host state the captured call left behind (restored on replay)
+        std::vector<svdw_region> layout;
+        std::vector<RegionChecks> layout_chk;
+        std::set<std::array<uint32_t, 8>> consts;
+        std::vector<std::pair<size_t, int>> gamma_slots;
+        std::vector<MatBits> mbits;
+        std::vector<Prod> prods;
+        std::vector<DevBits> dwords;
+        const unsigned* dbitw = nullptr;
+        uint64_t ext_off = 0;
+        svdw_counts counts{};
+        uint64_t replays = 0, captures = 0;
+    } vmg;
+};
+
+// engine.cpp's functions that prover.cpp calls too (the library exports only the C ABI).
+#pragma GCC visibility push(hidden)
+void sync(svdw_ctx* c);                                    // every stream of the context has run dry
+void ensure_buf(svdw_ctx* c, DBuf& b, size_t bytes);
+void flush_batch(svdw_ctx* c, hipStream_t s, hipStream_t waiter = nullptr, hipEvent_t then_wait = nullptr);
+#pragma GCC visibility pop
+inline bool sharded(const svdw_ctx* c) { return c->opt.shard_world > 1; }
+// The check every device entry makes, under the entry's name f.
+inline void need_device(const svdw_ctx* c, const std::string& f) { REQUIRE(!c->dry, f + " needs a device context"); }
+
+// RAII: brackets one kernel launch with HIP events on the context stream.
+struct ProfScope {
+    svdw_ctx* c;
+    long idx = -1;
+    static hipEvent_t ev(svdw_ctx* c) {
+        if (!c->pool.empty()) {
+            hipEvent_t e = c->pool.back();
+            c->pool.pop_back();
+            return e;
+        }
+        // timing-only events: skip the system-scope fence (cache writeback and
+        // invalidate) a default event performs, which would perturb what it measures
+        hipEvent_t e;
+        hipck(hipEventCreateWithFlags(&e, hipEventDisableSystemFence), "hipEventCreate");
+        return e;
+    }
+    hipStream_t s = nullptr;
+    bool ext = false;                       // stage launches: events recorded by their dispatch
+    // stage: the scope holds stage launches only (launch_stage*), which record
+    // the events themselves (set_launch_events): no event records between the
+    // launches, which cost a few us of stream time each
+    ProfScope(svdw_ctx* cc, hipStream_t ss, const std::string& name, double bytes, double ops,
+              bool batch = false, bool stage = false)
+        : c(cc), s(ss) {
+        if (!batch) flush_batch(c, s);      // earlier batched stages go first
+        if (!c->opt.prof || c->dry) return;
+        if (!c->opt.prof_filter.empty() && name.compare(0, c->opt.prof_filter.size(), c->opt.prof_filter) != 0)
+            return;
+        // every launch is tagged with its stream (@cell, @s2, @s3 as created), so a
+        // bench can report the busiest stream's stage rate beside the all-stream one
+        const char* tag = s == c->stream_id[0] ? "@cell" : s == c->stream_id[1] ? "@s2"
+                          : s == c->stream_id[2] ? "@s3" : "";
+        svdw_ctx::Rec r{name + tag, bytes, ops, ev(c), ev(c)};
+        ext = stage;
+        if (ext)
+            set_launch_events(r.e0, r.e1);
+        else
+            hipck(hipEventRecord(r.e0, s), "hipEventRecord");
+        c->recs.push_back(r);
+        idx = (long)c->recs.size() - 1;
+    }
+    ~ProfScope() {
+        if (idx < 0) return;
+        if (ext && launch_events_used()) return;
+        if (ext) (void)hipEventRecord(c->recs[idx].e0, s);       // nothing launched: an empty interval
+        (void)hipEventRecord(c->recs[idx].e1, s);
+    }
+};

@@ -377,3 +377,69 @@ def test_no_columns_and_overlap(ctx):
     # next to each other is no overlap
     out1, _ = ctx.ntt(d[:1], k, out=d[1:])
     assert torch.equal(d[:1], before[:1]) and not torch.equal(out1, before[1:])
+
+
+# ------------------------------------- 9. the prover calls alternate on one context
+def test_families_share_one_context(gpu_ctx_factory):
+    """The prover calls stage in one scratch and share the omega tables of the
+    last k: transforms, a permutation product, a commitment and a lookup
+    permutation in turn on one context, each against its Python-integer
+    restatement, and the first transform again, byte for byte as before."""
+    import torch
+    import halo2_svd041_amd as hs
+    from commit_cases import R, msm, parse_srs, point_bytes
+    from lookup_perm_cases import MINIMUM_ROWS, WITNESS_CASES, argument_holds, lookup_columns, table_column
+    from permutation_cases import CHALLENGES, cells_of, grand_products, identity_mapping, sigma_values
+    N, M, P, LB, K, ncells, nlk = WITNESS_CASES[0]
+    ctx = gpu_ctx_factory(P, LB)
+    # 1. forward transform of 2 random columns, k = 4
+    a = [_wide(16, 91), _wide(16, 92)]
+    da = _device(a, "canonical")
+    want_a = np.stack([_cells(ntt_forward(c, 4, 4)) for c in a])
+    first, res = ctx.ntt(da, 4, out=_prefilled(2, 16))
+    assert res == _result(2, 4, 4)
+    assert np.array_equal(first.cpu().numpy(), want_a)
+    # 2. permutation product, k = 5: 3 columns in sets of 2, the identity sigma
+    k, unusable = 5, 6
+    beta, gamma = CHALLENGES[0]
+    cols = [_wide(32 - unusable, 93 + j) + [0] * unusable for j in range(3)]
+    sig = sigma_values(identity_mapping(3, 32), k)
+    Z, zeros = grand_products(cols, sig, beta, gamma, 2, k, unusable)
+    ds, bad = ctx.permutation_values(k, ncols=3)
+    assert bad == 0 and np.array_equal(ds.cpu().numpy(), np.stack([cells_of(c) for c in sig]))
+    z, res = ctx.permutation_product(_device(cols, "canonical"), ds, beta, gamma, 2, k, unusable,
+                                     out=_prefilled(2, 32))
+    assert zeros == 0 and res == {"columns": 3, "sets": 2, "usable_rows": 32 - unusable, "zero_denominators": 0,
+                                  "final_not_one": 0}, res
+    assert np.array_equal(z.cpu().numpy(), np.stack([cells_of(c) for c in Z]))
+    # 3. forward coset transform, k_in = 4 to k = 11: two passes, through the buffer between them
+    assert hs.zk.lib().svdw_ntt_passes(11) == 2
+    ext, res = ctx.coeff_to_extended(da, 4, 11, WIDE_SHIFT, out=_prefilled(2, 1 << 11))
+    assert res == _result(2, 4, 11)
+    assert np.array_equal(ext.cpu().numpy(), np.stack([_cells(ntt_forward(c, 4, 11, WIDE_SHIFT)) for c in a]))
+    # 4. commitment of one k = 4 column to the first 16 bases of the SRS
+    g = parse_srs()[1][:16]
+    assert all(0 < s < R for s in a[0])
+    bases = torch.from_numpy(np.frombuffer(point_bytes(g, "montgomery"), dtype=np.uint8).reshape(-1, 64).copy()).cuda()
+    pts, res = ctx.commit(da[:1].contiguous(), bases, 4)
+    assert pts.cpu().numpy().tobytes() == point_bytes([msm(g, a[0])], "montgomery")
+    assert (res["columns"], res["zero_scalars"], res["identity_bases"], res["identity_outputs"]) == (1, 0, 0, 0), res
+    # 5. lookup permutation of a small witness's phase-0 lookups
+    m, u, d, v = gen_svd_input(N, M, seed=N + M + P)
+    hs.svd_witness(ctx, m, u, v, d, gamma_for(1))
+    assert ctx.physical_layout(K, MINIMUM_ROWS)["num_lookup_advice"] == [nlk, 0]
+    vals = cell_values(ctx.lookups(0).view(np.uint8))
+    assert len(vals) == ncells
+    rows = 1 << K
+    pa, pt, res = ctx.lookup_permute(0, unusable)
+    assert (res["columns"], res["usable_rows"], res["out_of_table"]) == (nlk, rows - unusable, 0), res
+    pa, pt = pa.cpu().numpy(), pt.cpu().numpy()
+    assert not pa[:, rows - unusable:].any() and not pt[:, rows - unusable:].any()
+    for j, col in enumerate(lookup_columns(vals, K)):
+        argument_holds(col, table_column(LB, rows), cell_values(pa[j, :rows - unusable]),
+                       cell_values(pt[j, :rows - unusable]), rows - unusable)
+    # 6. the first transform again
+    again, res = ctx.ntt(da, 4, out=_prefilled(2, 16))
+    assert res == _result(2, 4, 4)
+    assert torch.equal(again, first) and np.array_equal(again.cpu().numpy(), want_a)
+    assert ctx.check_ntt(da, again, 4, log_samples=4) == {"rows_checked": 32, "row_failures": 0}
