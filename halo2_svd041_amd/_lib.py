@@ -149,6 +149,18 @@ class QuotientCheck(ct.Structure):
                 ("tail_checked", ct.c_uint64), ("tail_nonzero", ct.c_uint64)]
 
 
+class OpenResult(ct.Structure):
+    _fields_ = [("columns", ct.c_uint32), ("sets", ct.c_uint32), ("points", ct.c_uint32), ("passes", ct.c_uint32),
+                ("rows", ct.c_uint64), ("remainder", ct.c_uint64 * 4)]
+
+
+class OpenCheck(ct.Structure):
+    _fields_ = [("lhs1", ct.c_uint64 * 4), ("rhs1", ct.c_uint64 * 4), ("lhs2", ct.c_uint64 * 4),
+                ("rhs2", ct.c_uint64 * 4), ("constant", ct.c_uint64 * 4), ("identity1_failures", ct.c_uint64),
+                ("identity2_failures", ct.c_uint64), ("h1_top_checked", ct.c_uint64), ("h1_top_nonzero", ct.c_uint64),
+                ("h2_top_checked", ct.c_uint64), ("h2_top_nonzero", ct.c_uint64)]
+
+
 class PhysParams(ct.Structure):
     _fields_ = [("k", ct.c_uint32), ("minimum_rows", ct.c_uint32), ("max_rows", ct.c_uint64),
                 ("num_advice", ct.c_uint32 * 2), ("columns_used", ct.c_uint32 * 2),
@@ -297,6 +309,12 @@ SIGNATURES = {
     "svdw_commit": (_i32, [_P, _u32, _i32, _i32, _P, _P, _u32, _P, ct.POINTER(CommitResult)]),
     "svdw_check_commit": (_i32, [_P, _u32, _i32, _i32, _P, _P, _u32, _P, ct.POINTER(CommitCheck)]),
     "svdw_commit_add_probe": (_i32, [_P, _P, _u32, _u64, _u32, ct.POINTER(ct.c_double)]),
+    "svdw_open_quotient": (_i32, [_P, _u32, _i32, _P, _u32, _P, _P, _P, _u32, _P, _P, _P, ct.POINTER(OpenResult)]),
+    "svdw_open_linearise": (_i32, [_P, _u32, _i32, _P, _u32, _P, _P, _P, _u32, _P, _P, _P, _P, _P,
+                                   ct.POINTER(OpenResult)]),
+    "svdw_check_open": (_i32, [_P, _u32, _i32, _P, _u32, _P, _P, _P, _u32, _P, _P, _P, _P, _P, _P, _P,
+                               ct.POINTER(OpenCheck)]),
+    "svdw_linear_combination": (_i32, [_P, _u32, _i32, _P, _u32, _P, _P]),
 }
 
 _lib = None

@@ -1,9 +1,9 @@
 // The prover calls of the C ABI (include/svdw.h) on an assigned witness: the
 // lookup argument, the grand products of the lookup and permutation arguments,
-// the transforms, the commitments and the quotient. Each entry checks its
-// arguments in the order include/svdw.h documents, stages what its kernels
-// read in the context's prover scratch (Staged below) and queues the kernels
-// on the context's stream. The context (svdw_ctx, engine_internal.hpp) is
+// the transforms, the commitments, the quotient and the opening. Each entry
+// checks its arguments in the order include/svdw.h documents, stages what its
+// kernels read in the context's prover scratch (Staged below) and queues the
+// kernels on the context's stream. The context (svdw_ctx, engine_internal.hpp) is
 // engine.cpp's: of it this file uses the stream, the profiler, sync, ensure_buf,
 // its own ProverState and the few facts its argument checks read.
 #include <string.h>
@@ -18,6 +18,7 @@
 #include "ntt.hpp"
 #include "commit.hpp"
 #include "quotient.hpp"
+#include "open.hpp"
 
 // ---- what the families share: argument checks, the staged call, profiling
 // The checks several entries repeat, each under the entry's name f.
@@ -1172,5 +1173,357 @@ int svdw_check_quotient(svdw_ctx* c, const svdw_quotient_args* args, const void*
         result->identity_failures = !fr_eq(lhs, rhs);
         result->tail_checked = tail[0];
         result->tail_nonzero = tail[1];
+    });
+}
+// ---- the SHPLONK opening: h1, h2, their check and the linear combination (open.hpp)
+namespace {
+struct OpenCall {
+    uint32_t k = 0, ncols = 0, nsets = 0, passes = 0, minpts = 8;
+    uint64_t n = 0;
+    Fr y, v, u, t;                                         // x R
+    std::vector<std::vector<Fr>> S;                        // the sets' points, x R
+    std::vector<Fr> T;                                     // their union, x R, in the order of first appearance
+    std::vector<uint32_t> first;                           // set i's columns: slots [first[i], first[i + 1])
+    std::vector<uint32_t> col;                             // the column index of a slot: index order within a set
+    std::vector<const void*> ptrs;                         // the columns by slot
+};
+}  // namespace
+// Host field arithmetic on x R.
+static Fr om_inv(const Fr& xR) { return fr_to_mont(fr_inv(fr_from_mont(xR))); }
+static bool om_in(const std::vector<Fr>& set, const Fr& x) {
+    return std::any_of(set.begin(), set.end(), [&](const Fr& s) { return fr_eq(s, x); });
+}
+// prod over the points s of `of` that are not in `without` of (x - s), as R-form.
+static Fr om_vanish(const std::vector<Fr>& of, const std::vector<Fr>* without, const Fr& xR) {
+    Fr z = fr_to_mont(fr_from_u64(1));
+    for (const Fr& s : of)
+        if (!without || !om_in(*without, s)) z = mont_mul(z, fr_sub(xR, s));
+    return z;
+}
+// The argument checks of the three opening entries (u, t: null where the entry
+// has none; out0, out1: the outputs, h1: the input of linearise), in the order
+// include/svdw.h gives; false: no columns, nothing to do.
+static bool open_args(svdw_ctx* c, const char* fn, uint32_t k, int form, const void* const* cols, uint32_t ncols,
+                      const uint32_t* set_of, const uint64_t* points, const uint32_t* npoints, uint32_t nsets,
+                      const uint64_t* y, const uint64_t* v, const uint64_t* u, bool has_u, const uint64_t* t,
+                      bool has_t, const void* h1, const void* h2, bool h1_is_out, bool h2_is_out, OpenCall* q) {
+    const std::string f(fn);
+    REQUIRE(c && y && v && (u || !has_u) && (t || !has_t), "null argument");
+    REQUIRE((set_of || !ncols) && ((points && npoints) || !nsets), "null argument");
+    check_form(form);
+    const Fr zero = fr_zero();
+    const Fr ch[4] = {fr_raw_words(y), fr_raw_words(v), has_u ? fr_raw_words(u) : zero, has_t ? fr_raw_words(t) : zero};
+    REQUIRE(fr_reduced(ch[0]) && fr_reduced(ch[1]) && fr_reduced(ch[2]) && fr_reduced(ch[3]),
+            f + ": y, v, u or t >= p");
+    const uint32_t ns = std::min(nsets, 256u);             // of more sets (refused below) the first 256 are looked at
+    q->S.assign(ns, {});
+    for (uint32_t i = 0; i < ns; ++i)
+        for (uint32_t j = 0; j < std::min(npoints[i], 8u); ++j) {
+            const Fr s = fr_raw_words(points + 4 * (8 * (size_t)i + j));
+            REQUIRE(fr_reduced(s), f + ": a point >= p");
+            q->S[i].push_back(fr_to_mont(s));
+        }
+    for (const auto& s : q->S)
+        for (size_t a = 0; a < s.size(); ++a)
+            for (size_t b = 0; b < a; ++b) REQUIRE(!fr_eq(s[a], s[b]), f + ": two equal points in a set");
+    std::vector<uint32_t> count(ns, 0);
+    for (uint32_t j = 0; j < ncols; ++j) {
+        REQUIRE(set_of[j] < nsets, f + ": set_of out of range");
+        if (set_of[j] < ns) ++count[set_of[j]];
+    }
+    for (uint32_t i = 0; i < ns && ncols; ++i) REQUIRE(count[i], f + ": a set without a polynomial");
+    for (const auto& s : q->S)
+        for (const Fr& x : s)
+            if (!om_in(q->T, x)) q->T.push_back(x);
+    q->y = fr_to_mont(ch[0]);
+    q->v = fr_to_mont(ch[1]);
+    q->u = fr_to_mont(ch[2]);
+    q->t = fr_to_mont(ch[3]);
+    REQUIRE(!has_u || !om_in(q->T, q->u), f + ": u is one of the points");
+    need_k(f, k);
+    need_device(c, f);
+    q->k = k;
+    q->n = 1ull << k;
+    q->ncols = ncols;
+    q->nsets = nsets;
+    if (!ncols) return false;
+    need_columns(f, ncols);
+    if (nsets < 1 || nsets > 255) fail(SVDW_ERANGE, f + ": nsets must be in [1, 255]");
+    for (uint32_t i = 0; i < nsets; ++i) {
+        if (npoints[i] < 1 || npoints[i] > 8) fail(SVDW_ERANGE, f + ": npoints must be in [1, 8]");
+        q->passes += npoints[i];
+        q->minpts = std::min(q->minpts, npoints[i]);
+    }
+    REQUIRE(cols && h1 && (h2 || !has_u), "null argument");
+    for (uint32_t j = 0; j < ncols; ++j) need_pointer(f, cols[j]);
+    const uintptr_t bytes = (uintptr_t)q->n * sizeof(Fr), a1 = (uintptr_t)h1, a2 = (uintptr_t)h2;
+    for (uint32_t j = 0; j < ncols; ++j) {
+        const uintptr_t i0 = (uintptr_t)cols[j];
+        if (h1_is_out) need_apart(f, "h1_out", a1, a1 + bytes, "an input column", i0, i0 + bytes);
+        if (h2_is_out) need_apart(f, "h2_out", a2, a2 + bytes, "an input column", i0, i0 + bytes);
+    }
+    if (h2_is_out) need_apart(f, "h2_out", a2, a2 + bytes, "h1", a1, a1 + bytes);
+    q->first.assign(nsets + 1, 0);
+    for (uint32_t i = 0; i < nsets; ++i) q->first[i + 1] = q->first[i] + count[i];
+    std::vector<uint32_t> at(q->first.begin(), q->first.end() - 1);
+    q->col.resize(ncols);
+    q->ptrs.resize(ncols);
+    for (uint32_t j = 0; j < ncols; ++j) {
+        const uint32_t slot = at[set_of[j]]++;
+        q->col[slot] = j;
+        q->ptrs[slot] = cols[j];
+    }
+    return true;
+}
+// The slots' scalars of the fold per set: y^(m - 1 - pos) R for position pos of a set's m columns.
+static void open_fold_scalars(const OpenCall& q, Fr* sc) {
+    for (uint32_t i = 0; i < q.nsets; ++i) {
+        Fr p = fr_to_mont(fr_from_u64(1));
+        for (uint32_t s = q.first[i + 1]; s-- > q.first[i];) {
+            sc[s] = p;
+            p = mont_mul(p, q.y);
+        }
+    }
+}
+// c_i v^(nsets - 1 - i) R per set, c_i = Z_{T \ S_i}(at) / Z_{T \ S_0}(at) (norm) or Z_{T \ S_i}(at).
+static std::vector<Fr> open_set_weights(const OpenCall& q, const Fr& at, bool norm) {
+    std::vector<Fr> w(q.nsets);
+    const Fr z0i = norm ? om_inv(om_vanish(q.T, &q.S[0], at)) : fr_to_mont(fr_from_u64(1));
+    Fr p = fr_to_mont(fr_from_u64(1));
+    for (uint32_t i = q.nsets; i-- > 0;) {
+        w[i] = mont_mul(mont_mul(om_vanish(q.T, &q.S[i], at), z0i), p);
+        p = mont_mul(p, q.v);
+    }
+    return w;
+}
+// The power table of the point sR for the call's k at `out`, and the kernels' view of its device copy at dev.
+static uint32_t open_table_cells(uint32_t k) {
+    const uint32_t b = open_pow_bits(k), h = domain_split(b);
+    return (1u << h) + (1u << (b - h));
+}
+static OpenPow open_table(uint32_t k, const Fr* dev) {
+    const uint32_t b = open_pow_bits(k), h = domain_split(b);
+    return OpenPow{dev, dev + ((size_t)1 << h), h, b};
+}
+// One division of a[0..n) by (X - s) on the stream: out = the quotient, or out v + it.
+static void open_divide(svdw_ctx* c, const Fr* a, uint64_t n, const OpenPow& pw, Fr* tot, const Fr* v, Fr* out,
+                        Fr* rem) {
+    const uint64_t nt = open_tiles(n);
+    if (nt > 1) {
+        profiled(c, "k_open_tiles", 32.0 * (double)n, [&] { return launch_open_tiles(a, n, pw, tot, c->st); });
+        profiled(c, "k_open_carry", 64.0 * (double)nt, [&] { return launch_open_carry(tot, nt, pw, c->st); });
+    }
+    profiled(c, "k_open_write", (v ? 96.0 : 64.0) * (double)n,
+             [&] { return launch_open_write(a, n, pw, nt > 1 ? tot : nullptr, v, out, rem, c->st); });
+}
+static void open_result(const OpenCall& q, uint32_t passes, svdw_open_result* r) {
+    memset(r, 0, sizeof *r);
+    r->rows = q.n;
+    if (!q.ncols) return;
+    r->columns = q.ncols;
+    r->sets = q.nsets;
+    r->points = (uint32_t)q.T.size();
+    r->passes = passes;
+}
+int svdw_open_quotient(svdw_ctx* c, uint32_t k, int form, const void* const* cols, uint32_t ncols,
+                       const uint32_t* set_of, const uint64_t* points, const uint32_t* npoints, uint32_t nsets,
+                       const uint64_t y[4], const uint64_t v[4], void* h1_out, svdw_open_result* result) {
+    return guarded([&] {
+        REQUIRE(result, "null argument");
+        OpenCall q;
+        const bool any = open_args(c, "svdw_open_quotient", k, form, cols, ncols, set_of, points, npoints, nsets, y, v,
+                                   nullptr, false, nullptr, false, h1_out, nullptr, true, false, &q);
+        open_result(q, q.passes, result);
+        if (!any) return;
+        sync(c);
+        const uint64_t n = q.n, nt = open_tiles(n);
+        const size_t tc = open_table_cells(k);
+        // the staged cells: the slots' scalars, then a power table per point in the order of the divisions
+        const Staged d = stage(c, q.ptrs.data(), ncols, nullptr, 0, ncols + q.passes * tc, (n + nt) * sizeof(Fr),
+                               [&](Fr* t) {
+                                   open_fold_scalars(q, t);
+                                   Fr* tab = t + ncols;
+                                   for (const auto& s : q.S)
+                                       for (const Fr& x : s) {
+                                           domain_power_tables(x, fr_to_mont(fr_from_u64(1)), open_pow_bits(k), tab);
+                                           tab += tc;
+                                       }
+                               });
+        Fr *F = (Fr*)d.free, *tot = F + n;
+        const Fr* tab = d.cells + ncols;
+        for (uint32_t i = 0; i < nsets; ++i) {
+            const uint32_t m = q.first[i + 1] - q.first[i];
+            profiled(c, "k_open_fold", 32.0 * (m + 1) * (double)n, [&] {
+                return launch_open_fold(d.ptrs + q.first[i], d.cells + q.first[i], m, nullptr, fr_zero(), n, F, c->st);
+            });
+            for (size_t p = 0; p < q.S[i].size(); ++p, tab += tc) {
+                const bool last = p + 1 == q.S[i].size();   // h1 <- h1 v + Q_i; set 0 starts h1
+                open_divide(c, F, n, open_table(k, tab), tot, last && i ? &q.v : nullptr, last ? (Fr*)h1_out : F,
+                            nullptr);
+            }
+        }
+    });
+}
+// The slots' scalars of G: c_i v^(nsets - 1 - i) y^(m - 1 - pos) R.
+static void open_g_scalars(const OpenCall& q, Fr* sc) {
+    open_fold_scalars(q, sc);
+    const std::vector<Fr> w = open_set_weights(q, q.u, true);
+    for (uint32_t i = 0; i < q.nsets; ++i)
+        for (uint32_t s = q.first[i]; s < q.first[i + 1]; ++s) sc[s] = mont_mul(sc[s], w[i]);
+}
+int svdw_open_linearise(svdw_ctx* c, uint32_t k, int form, const void* const* cols, uint32_t ncols,
+                        const uint32_t* set_of, const uint64_t* points, const uint32_t* npoints, uint32_t nsets,
+                        const uint64_t y[4], const uint64_t v[4], const uint64_t u[4], const void* h1, void* h2_out,
+                        svdw_open_result* result) {
+    return guarded([&] {
+        REQUIRE(result, "null argument");
+        OpenCall q;
+        const bool any = open_args(c, "svdw_open_linearise", k, form, cols, ncols, set_of, points, npoints, nsets, y,
+                                   v, u, true, nullptr, false, h1, h2_out, false, true, &q);
+        open_result(q, 1, result);
+        if (!any) return;
+        sync(c);
+        const uint64_t n = q.n, nt = open_tiles(n);
+        const size_t tc = open_table_cells(k);
+        // the staged cells: the slots' scalars of G, then the power table of u
+        const Staged d = stage(c, q.ptrs.data(), ncols, nullptr, 0, ncols + tc, nt * sizeof(Fr), [&](Fr* t) {
+            open_g_scalars(q, t);
+            domain_power_tables(q.u, fr_to_mont(fr_from_u64(1)), open_pow_bits(k), t + ncols);
+        });
+        const Fr cacc = fr_neg(om_vanish(q.S[0], nullptr, q.u));   // -Z_{S_0}(u) R
+        Fr *G = (Fr*)h2_out, *rem = (Fr*)d.cnt;            // G is built in h2_out and divided in place
+        profiled(c, "k_open_fold", 32.0 * (ncols + 2) * (double)n, [&] {
+            return launch_open_fold(d.ptrs, d.cells, ncols, (const Fr*)h1, cacc, n, G, c->st);
+        });
+        open_divide(c, G, n, open_table(k, d.cells + ncols), (Fr*)d.free, nullptr, G, rem);
+        Fr r;
+        hipck(hipMemcpyAsync(&r, rem, sizeof r, hipMemcpyDeviceToHost, c->st), "D2H");
+        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+        fr_store_words(form == SVDW_FORM_MONTGOMERY ? fr_from_mont(r) : r, result->remainder);
+    });
+}
+int svdw_check_open(svdw_ctx* c, uint32_t k, int form, const void* const* cols, uint32_t ncols,
+                    const uint32_t* set_of, const uint64_t* points, const uint32_t* npoints, uint32_t nsets,
+                    const uint64_t y[4], const uint64_t v[4], const uint64_t u[4], const void* h1, const void* h2,
+                    const uint64_t t[4], uint64_t* evals_out, svdw_open_check* result) {
+    return guarded([&] {
+        REQUIRE(result, "null argument");
+        OpenCall q;
+        const bool any = open_args(c, "svdw_check_open", k, form, cols, ncols, set_of, points, npoints, nsets, y, v, u,
+                                   true, t, true, h1, h2, false, false, &q);
+        memset(result, 0, sizeof *result);
+        if (!any) return;
+        REQUIRE(evals_out, "null argument");
+        sync(c);
+        const bool mont = form == SVDW_FORM_MONTGOMERY;
+        const uint64_t n = q.n;
+        const Fr one = fr_to_mont(fr_from_u64(1));
+        // points[0..np) R then t R at the nc columns ptrs: nc x (np + 1) values, as x R
+        auto evaluate = [&](const void* const* ptrs, uint32_t nc, const Fr* pts, uint32_t np, Fr* vals) {
+            const uint32_t nq = np + 1;
+            const size_t part = (size_t)nc * nq * ntt_eval_blocks(n) * sizeof(Fr), outb = (size_t)nc * nq * sizeof(Fr);
+            const Staged d = stage(c, ptrs, nc, nullptr, 0, nq, part + outb, [&](Fr* cells) {
+                for (uint32_t i = 0; i < np; ++i) cells[i] = pts[i];
+                cells[np] = q.t;
+            });
+            Fr* dout = (Fr*)(d.free + part);
+            ntt_eval_chunks(c, d.ptrs, nullptr, n, nc, d.cells, nq, nq, (Fr*)d.free, nq, dout, true);
+            hipck(hipMemcpyAsync(vals, dout, outb, hipMemcpyDeviceToHost, c->st), "D2H");
+            hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+            if (!mont)
+                for (size_t i = 0; i < (size_t)nc * nq; ++i) vals[i] = fr_to_mont(vals[i]);
+        };
+        memset(evals_out, 0, (size_t)ncols * 8 * 4 * sizeof(uint64_t));
+        // per set: F_i at its points and at t (folded with y), then r_i at t and at u by Lagrange
+        std::vector<Fr> Ft(nsets), rt(nsets), ru(nsets), vals;
+        for (uint32_t i = 0; i < nsets; ++i) {
+            const std::vector<Fr>& S = q.S[i];
+            const uint32_t m = q.first[i + 1] - q.first[i], np = (uint32_t)S.size(), nq = np + 1;
+            vals.resize((size_t)m * nq);
+            evaluate(q.ptrs.data() + q.first[i], m, S.data(), np, vals.data());
+            std::vector<Fr> F(nq, fr_zero());
+            for (uint32_t s = 0; s < m; ++s)
+                for (uint32_t p = 0; p < nq; ++p) {
+                    const Fr& e = vals[(size_t)s * nq + p];
+                    F[p] = fr_add(mont_mul(F[p], q.y), e);
+                    if (p < np) fr_store_words(fr_from_mont(e), evals_out + 4 * (8 * (size_t)q.col[q.first[i] + s] + p));
+                }
+            Ft[i] = F[np];
+            rt[i] = ru[i] = fr_zero();
+            for (uint32_t a = 0; a < np; ++a) {
+                Fr den = one, nt_ = one, nu = one;
+                for (uint32_t b = 0; b < np; ++b) {
+                    if (b == a) continue;
+                    den = mont_mul(den, fr_sub(S[a], S[b]));
+                    nt_ = mont_mul(nt_, fr_sub(q.t, S[b]));
+                    nu = mont_mul(nu, fr_sub(q.u, S[b]));
+                }
+                const Fr w = mont_mul(F[a], om_inv(den));
+                rt[i] = fr_add(rt[i], mont_mul(w, nt_));
+                ru[i] = fr_add(ru[i], mont_mul(w, nu));
+            }
+        }
+        Fr ht[4];                                           // h1(t), its slot for t twice, h2(t)
+        {
+            const void* hp[2] = {h1, h2};
+            evaluate(hp, 2, nullptr, 0, ht);
+        }
+        const Fr h1t = ht[0], h2t = ht[1];
+        // identity 1
+        const std::vector<Fr> wt = open_set_weights(q, q.t, false), wu = open_set_weights(q, q.u, true);
+        Fr rhs1 = fr_zero(), gt = fr_zero(), cst = fr_zero();
+        for (uint32_t i = 0; i < nsets; ++i) {
+            rhs1 = fr_add(rhs1, mont_mul(wt[i], fr_sub(Ft[i], rt[i])));
+            gt = fr_add(gt, mont_mul(wu[i], Ft[i]));
+            cst = fr_add(cst, mont_mul(wu[i], ru[i]));
+        }
+        const Fr lhs1 = mont_mul(h1t, om_vanish(q.T, nullptr, q.t));
+        // identity 2
+        gt = fr_sub(gt, mont_mul(om_vanish(q.S[0], nullptr, q.u), h1t));
+        const Fr lhs2 = fr_sub(gt, cst), rhs2 = mont_mul(h2t, fr_sub(q.t, q.u));
+        fr_store_words(fr_from_mont(lhs1), result->lhs1);
+        fr_store_words(fr_from_mont(rhs1), result->rhs1);
+        fr_store_words(fr_from_mont(lhs2), result->lhs2);
+        fr_store_words(fr_from_mont(rhs2), result->rhs2);
+        fr_store_words(fr_from_mont(cst), result->constant);
+        result->identity1_failures = !fr_eq(lhs1, rhs1);
+        result->identity2_failures = !fr_eq(lhs2, rhs2);
+        // the top cells
+        const uint64_t top = std::min<uint64_t>(q.minpts, n);
+        Fr cells[9];
+        hipck(hipMemcpyAsync(cells, (const Fr*)h1 + (n - top), top * sizeof(Fr), hipMemcpyDeviceToHost, c->st), "D2H");
+        hipck(hipMemcpyAsync(cells + 8, (const Fr*)h2 + (n - 1), sizeof(Fr), hipMemcpyDeviceToHost, c->st), "D2H");
+        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+        result->h1_top_checked = top;
+        for (uint64_t i = 0; i < top; ++i) result->h1_top_nonzero += !fr_is_zero(cells[i]);
+        result->h2_top_checked = 1;
+        result->h2_top_nonzero = !fr_is_zero(cells[8]);
+    });
+}
+int svdw_linear_combination(svdw_ctx* c, uint32_t k, int form, const void* const* cols, uint32_t ncols,
+                            const uint64_t* scalars, void* out) {
+    return guarded([&] {
+        const std::string f("svdw_linear_combination");
+        REQUIRE(c && (scalars || !ncols), "null argument");
+        check_form(form);
+        for (uint32_t j = 0; j < ncols; ++j)
+            REQUIRE(fr_reduced(fr_raw_words(scalars + 4 * (size_t)j)), f + ": scalar >= p");
+        need_k(f, k);
+        need_device(c, f);
+        if (!ncols) return;
+        need_columns(f, ncols);
+        REQUIRE(cols && out, "null argument");
+        const uint64_t n = 1ull << k;
+        const uintptr_t bytes = (uintptr_t)n * sizeof(Fr), o0 = (uintptr_t)out;
+        for (uint32_t j = 0; j < ncols; ++j) need_pointer(f, cols[j]);
+        for (uint32_t j = 0; j < ncols; ++j)
+            need_apart(f, "out", o0, o0 + bytes, "an input column", (uintptr_t)cols[j], (uintptr_t)cols[j] + bytes);
+        sync(c);
+        const Staged d = stage(c, cols, ncols, nullptr, 0, ncols, 0, [&](Fr* t) {
+            for (uint32_t j = 0; j < ncols; ++j) t[j] = fr_to_mont(fr_raw_words(scalars + 4 * (size_t)j));
+        });
+        profiled(c, "k_open_fold", 32.0 * (ncols + 1) * (double)n, [&] {
+            return launch_open_fold(d.ptrs, d.cells, ncols, nullptr, fr_zero(), n, (Fr*)out, c->st);
+        });
     });
 }

@@ -20,7 +20,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import (CheckResult, CommitCheck, CommitResult, EqCheck, LookupCheck, LookupProductCheck, LookupProductResult, LookupResult, NttCheck, NttResult, PermutationProductCheck, PermutationProductResult, PhysParams, QuotientArgs, QuotientCheck, QuotientResult, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SvdwError,
+from ._lib import (CheckResult, CommitCheck, CommitResult, EqCheck, OpenCheck, OpenResult, LookupCheck, LookupProductCheck, LookupProductResult, LookupResult, NttCheck, NttResult, PermutationProductCheck, PermutationProductResult, PhysParams, QuotientArgs, QuotientCheck, QuotientResult, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SvdwError,
                    Vec, check, lib)
 
 P_MOD = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -30,7 +30,7 @@ __all__ = ["Context", "ZkMatrix", "ZkVector", "honest_prover_mat_mul", "field_ma
            "check_svd_phase0", "check_svd_phase1", "err_calc", "svd_witness", "plan_svd",
            "SvdwError", "SvdPayload", "SvdConfigPy", "P_MOD", "int_to_words", "words_to_int",
            "fr_convert", "quantization", "dequantization", "format_f64_debug", "permutation_constants",
-           "commit_plan"]
+           "commit_plan", "shplonk_queries"]
 
 
 def int_to_words(x: int) -> np.ndarray:
@@ -101,6 +101,41 @@ def commit_plan(k: int) -> tuple:
     c, w = ct.c_uint32(), ct.c_uint32()
     lib().svdw_commit_plan(k, ct.byref(c), ct.byref(w))
     return c.value, w.value
+
+
+def shplonk_queries(k: int, unusable_rows: int, n_gate: int, n_perm: int, chunk_len: int, n_lookup: int, x: int):
+    """(set_of, sets): the rotation sets of the SHPLONK opening at x for the
+    circuit shape svdw_quotient_args describes, as Context.open_quotient takes
+    them. Host only. The columns, in this order: advice [n_gate], selectors
+    [n_gate], sigma [n_perm], lookup_input A [n_lookup], lookup_table [n_lookup],
+    perm_z [ceil(n_perm / chunk_len)], lookup_z [n_lookup], permuted_input A'
+    [n_lookup], permuted_table S' [n_lookup], then the combined h (one column:
+    the pieces of h folded by linear_combination). Their rotations: advice
+    {0, 1, 2, 3}; selectors, sigma, A, the lookup table, S' and h {0}; a
+    permutation Z {0, 1, usable}, the last one {0, 1}; a lookup Z {0, 1}; A'
+    {0, -1}. (perm_columns names no polynomial of its own: the v_j are advice
+    and lookup input columns, opened once.) Families with
+    equal rotations share a set, sets are numbered in the order in which the
+    columns first need them, and a point of rotation r is x omega_k^r
+    (usable = 2^k - unusable_rows, -1 = 2^k - 1). set_of: one set index per
+    column; sets: one list of points (ints) per set."""
+    n = 1 << k
+    if not 0 < unusable_rows < n:
+        raise SvdwError(-2, "shplonk_queries: unusable_rows must be in [1, 2^k)")
+    if n_perm and chunk_len < 1:
+        raise SvdwError(-1, "shplonk_queries: chunk_len == 0")
+    x = int(x)
+    if not 0 <= x < P_MOD:
+        raise SvdwError(-1, "shplonk_queries: x must be in [0, p)")
+    _, w = permutation_constants(k)
+    usable = n - unusable_rows
+    n_z = -(-n_perm // chunk_len) if n_perm else 0
+    families = ([(0, 1, 2, 3)] * n_gate + [(0,)] * (n_gate + n_perm + 2 * n_lookup) + [(0, 1, usable)] * max(n_z - 1, 0)
+                + [(0, 1)] * (min(n_z, 1) + n_lookup) + [(0, n - 1)] * n_lookup + [(0,)] * (n_lookup + 1))
+    index, set_of = {}, []
+    for rot in families:
+        set_of.append(index.setdefault(rot, len(index)))
+    return set_of, [[x * pow(w, r, P_MOD) % P_MOD for r in rot] for rot in index]
 
 
 def quantization(x: float, precision_bits: int) -> int:
@@ -951,6 +986,120 @@ class Context:
                                         xa, ct.byref(r)))
         return {"lhs": words_to_int(r.lhs), "rhs": words_to_int(r.rhs), "identity_failures": r.identity_failures,
                 "tail_checked": r.tail_checked, "tail_nonzero": r.tail_nonzero}
+
+    # ---- openings (include/svdw.h, "openings"; parity unpinned)
+    def _open_args(self, columns, set_of, sets, k: int):
+        """(column pointers, count, set_of, points, npoints, nsets, rows, device)
+        of an opening call; of a set's points the first 8 are handed over, its
+        count as it is (the C ABI rejects more than 8)."""
+        rows = 1 << k if 0 <= k < 32 else 0
+        cp, n, dev = self._column_pointers("columns", columns, rows)
+        set_of = [int(i) for i in set_of]
+        if len(set_of) != n:
+            raise SvdwError(-1, "set_of must hold one set index per column")
+        if any(not 0 <= i < 1 << 32 for i in set_of):
+            raise SvdwError(-1, "set_of out of range")
+        sets = [list(s) for s in sets]
+        ns = len(sets)
+        so = (ct.c_uint32 * max(n, 1))(*set_of)
+        npts = (ct.c_uint32 * max(ns, 1))(*[len(s) for s in sets])
+        pts = (ct.c_uint64 * max(32 * ns, 1))()
+        for i, pset in enumerate(sets):
+            for q, x in enumerate(pset[:8]):
+                pts[32 * i + 4 * q:32 * i + 4 * q + 4] = list(_challenge_arg(x))
+        return cp, n, so, pts, npts, ns, rows, dev
+
+    def _open_cell_tensor(self, what: str, t, rows: int, dev=None):
+        import torch
+        if t is None:
+            return torch.empty((1, rows, 32), dtype=torch.uint8, device=dev or torch.device("cuda", self.device))
+        if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous()
+                or tuple(t.shape) != (1, rows, 32)):
+            raise SvdwError(-1, f"{what} must be a contiguous uint8 device tensor [1, 2^k, 32]")
+        return t
+
+    @staticmethod
+    def _open_result(r) -> dict:
+        return {"columns": r.columns, "sets": r.sets, "points": r.points, "passes": r.passes, "rows": r.rows,
+                "remainder": words_to_int(r.remainder)}
+
+    def open_quotient(self, columns, set_of, sets, y: int, v: int, k: int, form: str = "canonical", out=None):
+        """(h1, result): SHPLONK's first quotient polynomial (svdw_open_quotient),
+        a [1, 2^k, 32] u8 device tensor of coefficients in `form`. columns: the
+        polynomials' 2^k coefficients, a tensor [n, 2^k, 32] u8 in `form` or a list
+        of such tensors; set_of: one rotation-set index per column; sets: one list
+        of points (ints below p, at most 8, distinct) per set, e.g. from
+        shplonk_queries; y, v: the challenges. Per set the columns are folded by
+        Horner in y and divided by the set's vanishing polynomial, the quotients
+        folded by Horner in v. result: columns, sets, points (|T|), passes, rows,
+        remainder (0 here)."""
+        cy, cv = _challenge_arg(y), _challenge_arg(v)
+        cp, n, so, pts, npts, ns, rows, dev = self._open_args(columns, set_of, sets, k)
+        out = self._open_cell_tensor("out", out, rows, dev)
+        r = OpenResult()
+        _after_torch(self)
+        check(lib().svdw_open_quotient(self._h, k, _form(form), cp, n, so, pts, npts, ns, cy, cv, out.data_ptr(),
+                                       ct.byref(r)))
+        _before_torch(self)
+        return out, self._open_result(r)
+
+    def open_linearise(self, columns, set_of, sets, y: int, v: int, u: int, h1, k: int, form: str = "canonical",
+                       out=None):
+        """(h2, result): SHPLONK's second quotient polynomial (svdw_open_linearise)
+        from the arguments of open_quotient, the challenge u and h1 as
+        open_quotient returned it: the quotient of G(X) = (Horner in v of c_i
+        F_i(X)) - Z_{S_0}(u) h1(X) by (X - u). result["remainder"] is G(u), which
+        equals the verifier's constant for an honest h1."""
+        cy, cv, cu = _challenge_arg(y), _challenge_arg(v), _challenge_arg(u)
+        cp, n, so, pts, npts, ns, rows, dev = self._open_args(columns, set_of, sets, k)
+        h1 = self._open_cell_tensor("h1", h1, rows) if h1 is not None else None
+        out = self._open_cell_tensor("out", out, rows, dev)
+        r = OpenResult()
+        _after_torch(self)
+        check(lib().svdw_open_linearise(self._h, k, _form(form), cp, n, so, pts, npts, ns, cy, cv, cu,
+                                        h1.data_ptr() if h1 is not None else None, out.data_ptr(), ct.byref(r)))
+        _before_torch(self)
+        return out, self._open_result(r)
+
+    def check_open(self, columns, set_of, sets, y: int, v: int, u: int, h1, h2, t: int, k: int,
+                   form: str = "canonical") -> dict:
+        """The independent check of h1 and h2 at the point t (svdw_check_open):
+        lhs1, rhs1, lhs2, rhs2 and constant as ints, identity1_failures,
+        identity2_failures, the counts of the top cells, and evals: per column
+        the list of its values at its set's points (what the transcript takes)."""
+        cy, cv, cu, ctt = _challenge_arg(y), _challenge_arg(v), _challenge_arg(u), _challenge_arg(t)
+        cp, n, so, pts, npts, ns, rows, _ = self._open_args(columns, set_of, sets, k)
+        h1 = self._open_cell_tensor("h1", h1, rows) if h1 is not None else None
+        h2 = self._open_cell_tensor("h2", h2, rows) if h2 is not None else None
+        ev = (ct.c_uint64 * max(32 * n, 1))()
+        r = OpenCheck()
+        _after_torch(self)
+        check(lib().svdw_check_open(self._h, k, _form(form), cp, n, so, pts, npts, ns, cy, cv, cu,
+                                    h1.data_ptr() if h1 is not None else None,
+                                    h2.data_ptr() if h2 is not None else None, ctt, ev, ct.byref(r)))
+        out = {f: words_to_int(getattr(r, f)) for f in ("lhs1", "rhs1", "lhs2", "rhs2", "constant")}
+        out.update({f: getattr(r, f) for f, _ in OpenCheck._fields_[5:]})
+        sizes = [len(s) for s in sets]
+        out["evals"] = [[words_to_int(ev[32 * j + 4 * q:32 * j + 4 * q + 4]) for q in range(sizes[so[j]])]
+                        for j in range(n)]
+        return out
+
+    def linear_combination(self, columns, scalars, k: int, form: str = "canonical", out=None):
+        """sum_j scalars[j] columns[j] as a [1, 2^k, 32] u8 device tensor in `form`
+        (svdw_linear_combination): columns a tensor [n, 2^k, 32] u8 or a list of
+        such tensors, scalars ints below p. With h_coeffs.view(E, 2**k, 32) and the
+        scalars x^(n i) it is the one polynomial create_proof opens for h."""
+        rows = 1 << k if 0 <= k < 32 else 0
+        sc = [_challenge_arg(x) for x in scalars]
+        cp, n, dev = self._column_pointers("columns", columns, rows)
+        if len(sc) != n:
+            raise SvdwError(-1, "scalars must hold one value per column")
+        buf = (ct.c_uint64 * max(4 * n, 1))(*[w for x in sc for w in x])
+        out = self._open_cell_tensor("out", out, rows, dev)
+        _after_torch(self)
+        check(lib().svdw_linear_combination(self._h, k, _form(form), cp, n, buf, out.data_ptr()))
+        _before_torch(self)
+        return out
 
     def profile(self, on: bool = True, prefix: str = "") -> None:
         """Record HIP events around kernel launches (names starting with `prefix`)."""

@@ -994,6 +994,112 @@ int svdw_check_commit(svdw_ctx* ctx, uint32_t k, int form, int bases_form, const
  * register-resident accumulator; *seconds is the launch's device time. */
 int svdw_commit_add_probe(svdw_ctx* ctx, const void* points, uint32_t npoints, uint64_t threads, uint32_t reps,
                           double* seconds);
+/* ---------------------------------------------------------------- openings
+ * The quotient polynomials of halo2_proofs' poly::kzg::multiopen::shplonk
+ * prover (ProverSHPLONK::create_proof) for polynomials held as coefficient
+ * columns on the device. Restated from memory like the steps above: PARITY
+ * UNPINNED; the rule below is the specification. These calls need no witness
+ * and no physical layout. All arithmetic is exact mod p; cells are taken as
+ * field elements below p.
+ *
+ * ncols polynomials p_j of n = 2^k coefficients each (cols: HOST array of DEVICE
+ * pointers, cells in `form`, as svdw_ntt takes them). set_of[j] < nsets assigns
+ * p_j to a rotation set; set i holds npoints[i] points S_i, 1 <= npoints[i] <= 8,
+ * canonical and pairwise distinct, nsets <= 255. points: HOST, nsets x 8 x 4
+ * words, the points of set i in slots 8 i .. 8 i + npoints[i] - 1 (the other
+ * slots are not read). Every set holds a polynomial. T is the union of the S_i
+ * as field elements, Z_A(X) = prod_{s in A} (X - s). The challenges y, v, u are
+ * the caller's (canonical), as beta, gamma, y and x are everywhere else.
+ *
+ *  1. Fold per set:  F_i(X) = Horner in y over the polynomials of set i in
+ *     index order: acc starts at 0 and acc <- acc y + p_j.
+ *  2. Quotient per set:  Q_i = the Euclidean quotient of F_i by Z_{S_i}, which
+ *     equals (F_i - r_i) / Z_{S_i} with r_i the interpolant of F_i on S_i:
+ *     successive synthetic divisions by (X - s), s in S_i in the order given,
+ *     each remainder dropped. No evaluation is needed.
+ *  3. First quotient:  h1(X) = Horner in v over the sets in index order: acc
+ *     starts at 0 and acc <- acc v + Q_i. The caller commits h1 (svdw_commit on
+ *     g) and derives u.
+ *  4. Second quotient:  z_i = Z_{T \ S_i}(u), c_i = z_i / z_0,
+ *       G(X) = (Horner in v of c_i F_i(X)) - Z_{S_0}(u) h1(X),
+ *     h2 = the Euclidean quotient of G by (X - u). The dropped remainder G(u)
+ *     equals the same Horner in v of c_i r_i(u), the verifier's constant, when
+ *     h1 is step 3's; the call reports the remainder and does not subtract the
+ *     constant.
+ *
+ * What stays with the caller: the transcript, deriving y, v, u (and x),
+ * blinding, the commitments of h1 and h2 (svdw_commit), G2 and the pairing. */
+typedef struct {
+    uint32_t columns, sets;
+    uint32_t points;          /* |T| */
+    uint32_t passes;          /* divisions by one (X - s): sum of npoints (quotient), 1 (linearise) */
+    uint64_t rows;            /* 2^k */
+    uint64_t remainder[4];    /* svdw_open_linearise: G(u), canonical; else zero */
+} svdw_open_result;
+/* h1_out: DEVICE, 2^k cells in `form`; the top min_i |S_i| cells are written as
+ * zero (the degree of Q_i is n - 1 - |S_i|, that of h1 the largest of them). The checks of the arguments come
+ * first, before anything touches the device, in this order: an unknown form
+ * (SVDW_EINVAL); y or v >= p, then a point >= p, then two equal points in a set,
+ * then a set_of[j] >= nsets, then a set without a polynomial (all SVDW_EINVAL;
+ * of the sets at most 256 and of each at most 8 points are looked at here); k
+ * outside 1..28
+ * (SVDW_ERANGE); a planning context (SVDW_EINVAL); more than 65535 columns, then
+ * nsets outside 1..255 or an npoints[i] outside 1..8 (SVDW_ERANGE); null
+ * pointers (SVDW_EINVAL); h1_out overlapping an input column (SVDW_EINVAL).
+ * ncols == 0: SVDW_OK, nothing is touched. The call is queued on the context's
+ * streams like svdw_ntt, with no host wait; scratch (one column of 2^k cells,
+ * the tile carries and a power table per point) is the engine's. */
+int svdw_open_quotient(svdw_ctx* ctx, uint32_t k, int form, const void* const* cols, uint32_t ncols,
+                       const uint32_t* set_of, const uint64_t* points, const uint32_t* npoints, uint32_t nsets,
+                       const uint64_t y[4], const uint64_t v[4], void* h1_out, svdw_open_result* result);
+/* h2 from the same arguments, u and h1 (DEVICE, 2^k cells in `form`): h2_out
+ * (DEVICE, 2^k cells in `form`; its top cell is written as zero) and
+ * result->remainder = G(u), read back as the grand products read their
+ * counters. Checks as for svdw_open_quotient with u >= p beside y and v, and
+ * u in T (SVDW_EINVAL: z_0 or a divisor would be zero) after the empty set;
+ * h2_out overlapping an input column or h1 (SVDW_EINVAL). */
+int svdw_open_linearise(svdw_ctx* ctx, uint32_t k, int form, const void* const* cols, uint32_t ncols,
+                        const uint32_t* set_of, const uint64_t* points, const uint32_t* npoints, uint32_t nsets,
+                        const uint64_t y[4], const uint64_t v[4], const uint64_t u[4], const void* h1, void* h2_out,
+                        svdw_open_result* result);
+typedef struct {
+    uint64_t lhs1[4], rhs1[4];    /* h1(t) Z_T(t); Horner in v of Z_{T \ S_i}(t) (F_i(t) - r_i(t)) */
+    uint64_t lhs2[4], rhs2[4];    /* G(t) - constant; h2(t) (t - u) */
+    uint64_t constant[4];         /* Horner in v of c_i r_i(u) */
+    uint64_t identity1_failures;  /* 0 or 1: lhs1 != rhs1 */
+    uint64_t identity2_failures;  /* 0 or 1: lhs2 != rhs2 */
+    uint64_t h1_top_checked, h1_top_nonzero;   /* the top min_i |S_i| cells of h1 */
+    uint64_t h2_top_checked, h2_top_nonzero;   /* the top cell of h2 */
+} svdw_open_check;
+/* The independent check of h1 and h2 (DEVICE, 2^k cells in `form`) at a
+ * caller-chosen point t (canonical; >= p: SVDW_EINVAL, with the challenges). It
+ * shares no fold and no scan with the two calls above: every column is
+ * evaluated at its set's points and at t, h1 and h2 at t, with the kernels of
+ * svdw_eval_polynomial; the host folds the evaluations with y, interpolates each
+ * r_i (Lagrange on at most 8 points) and tests
+ *   h1(t) Z_T(t) == Horner in v of Z_{T \ S_i}(t) (F_i(t) - r_i(t)),
+ *   G(t) - constant == h2(t) (t - u),   constant = Horner in v of c_i r_i(u).
+ * evals_out: HOST, ncols x 8 x 4 words, canonical: slot q of column j is
+ * p_j(S_{set_of[j]}[q]), the evals the transcript takes; unused slots zero.
+ * Arguments and their checks as for svdw_open_linearise (there is no output
+ * to overlap); it writes to none of its device inputs and returns after the
+ * device has finished. */
+int svdw_check_open(svdw_ctx* ctx, uint32_t k, int form, const void* const* cols, uint32_t ncols,
+                    const uint32_t* set_of, const uint64_t* points, const uint32_t* npoints, uint32_t nsets,
+                    const uint64_t y[4], const uint64_t v[4], const uint64_t u[4], const void* h1, const void* h2,
+                    const uint64_t t[4], uint64_t* evals_out, svdw_open_check* result);
+/* out[r] = sum_j scalars[j] cols[j][r] over ncols columns of 2^k cells in
+ * `form` (cols as above; scalars: HOST, ncols x 4 words, canonical; out:
+ * DEVICE, 2^k cells in `form`): the fold kernel of the opening by itself.
+ * create_proof opens the pieces of h as the one polynomial sum_i x^(n i) h_i,
+ * which is this call on the pieces with the scalars x^(n i). Checks in this
+ * order: form (SVDW_EINVAL), a scalar >= p (SVDW_EINVAL), k outside 1..28
+ * (SVDW_ERANGE), a planning context (SVDW_EINVAL), more than 65535 columns
+ * (SVDW_ERANGE), null pointers (SVDW_EINVAL), out overlapping an input column
+ * (SVDW_EINVAL). ncols == 0: SVDW_OK, nothing is touched. Queued with no host
+ * wait. */
+int svdw_linear_combination(svdw_ctx* ctx, uint32_t k, int form, const void* const* cols, uint32_t ncols,
+                            const uint64_t* scalars, void* out);
 /* Up to cap segments of the last witness into out; *n = total count. */
 int svdw_shard_segments(const svdw_ctx* ctx, svdw_segment* out, uint64_t cap, uint64_t* n);
 
