@@ -108,6 +108,25 @@ class PermutationProductCheck(ct.Structure):
                 ("padding_checked", ct.c_uint64), ("padding_failures", ct.c_uint64)]
 
 
+class PermutationCyclesResult(ct.Structure):
+    _fields_ = [("cells", ct.c_uint64), ("edges", ct.c_uint64), ("out_of_range", ct.c_uint64),
+                ("self_edges", ct.c_uint64), ("classes", ct.c_uint64), ("linked_cells", ct.c_uint64),
+                ("largest_class", ct.c_uint64), ("sort_passes", ct.c_uint32), ("_pad", ct.c_uint32)]
+
+
+class PermutationMappingCheck(ct.Structure):
+    _fields_ = [("cells_checked", ct.c_uint64), ("not_permutation", ct.c_uint64), ("order_failures", ct.c_uint64),
+                ("padding_failures", ct.c_uint64), ("edges_checked", ct.c_uint64), ("edge_failures", ct.c_uint64),
+                ("cycles", ct.c_uint64)]
+
+
+class PermutationLayout(ct.Structure):
+    _fields_ = [("k", ct.c_uint32), ("advice", ct.c_uint32 * 2), ("fixed", ct.c_uint32), ("external", ct.c_uint32),
+                ("total_cols", ct.c_uint32), ("edges", ct.c_uint64), ("break_edges", ct.c_uint64),
+                ("copy_edges", ct.c_uint64), ("const_edges", ct.c_uint64), ("external_edges", ct.c_uint64),
+                ("constants", ct.c_uint64)]
+
+
 class NttResult(ct.Structure):
     _fields_ = [("columns", ct.c_uint32), ("passes", ct.c_uint32), ("rows_in", ct.c_uint64),
                 ("rows_out", ct.c_uint64)]
@@ -299,6 +318,11 @@ SIGNATURES = {
                                         ct.POINTER(PermutationProductResult)]),
     "svdw_check_permutation_product": (_i32, [_P, _u32, _u32, _i32, _P, _P, _u32, _u32, _P, _P, _P,
                                               ct.POINTER(PermutationProductCheck)]),
+    "svdw_permutation_cycles": (_i32, [_P, _u32, _u32, _u32, _P, _u64, _P, ct.POINTER(PermutationCyclesResult)]),
+    "svdw_check_permutation_mapping": (_i32, [_P, _u32, _u32, _u32, _P, _u64, _P,
+                                              ct.POINTER(PermutationMappingCheck)]),
+    "svdw_permutation_edges": (_i32, [_P, _P, _u64, ct.POINTER(PermutationLayout)]),
+    "svdw_assign_fixed": (_i32, [_P, _i32, _P]),
     "svdw_ntt_passes": (_u32, [_u32]),
     "svdw_ntt": (_i32, [_P, _u32, _u32, _i32, _i32, _P, _P, _u32, _P, ct.POINTER(NttResult)]),
     "svdw_eval_polynomial": (_i32, [_P, _u32, _i32, _P, _u32, _P, _u32, _P]),

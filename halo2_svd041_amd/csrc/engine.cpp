@@ -19,11 +19,13 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 
 #include "engine_internal.hpp"
 #include "ingest.hpp"
 #include "ingest_dev.hpp"
 #include "export.hpp"
+#include "permutation_cycles.hpp"                            // the witness's edge list (svdw_permutation_edges)
 #include "commit.hpp"                                       // kCommitMaxBits, for the "commit_window_bits" option
 
 // ------------------------------------------------------- host big integers
@@ -2864,7 +2866,7 @@ static std::vector<DBuf*> dbufs(svdw_ctx* c) {
                             &c->gtab_alt, &c->crtR, &c->gbits, &c->colpart, &c->qfold, &c->ing_x, &c->ing_e,
                             &c->ing_c, &c->ing_p10, &c->ing_val, &c->ing_npos, &c->ing_nd, &c->ing_rpos,
                             &c->ing_kpos, &c->ing_err, &c->ing_q, &c->eq_cp, &c->eq_ks, &c->eq_reg, &c->eq_w,
-                            &c->eq_k, &c->eq_err, &c->eq_st, &c->exp_buf[0], &c->exp_buf[1]};
+                            &c->eq_k, &c->eq_err, &c->eq_st, &c->eq_fx, &c->exp_buf[0], &c->exp_buf[1]};
     for (DBuf* d : c->prover.dbufs()) v.push_back(d);
     for (int i = 0; i < kMaxScanJobs; ++i) {
         v.push_back(&c->wbc[i]);
@@ -4293,6 +4295,8 @@ int svdw_physical_layout(svdw_ctx* c, uint32_t k, uint32_t minimum_rows, svdw_ph
         const uint64_t R = (1ull << k) - minimum_rows;
         auto& P = c->phys;
         P.valid = false;
+        P.fixed_ready = false;
+        P.fixed.clear();
         P.k = k;
         P.min_rows = minimum_rows;
         P.R = R;
@@ -4494,6 +4498,192 @@ int svdw_check_equalities(svdw_ctx* c, uint32_t phase, const void* columns0, con
         out->copy_failures = h[1];
         out->consts_checked = h[2];
         out->const_failures = h[3];
+    });
+}
+// ---- the permutation argument's edge list and fixed columns of the witness
+// (include/svdw.h, svdw_permutation_edges; kernels: permutation_cycles.hpp)
+namespace {
+struct EqCounts {
+    uint64_t copies = 0, consts = 0, external = 0;        // external: the copies whose source is init_rand
+};
+}  // namespace
+// The record counts of a phase, as eq_gen_device and eq_lists produce them.
+static EqCounts eq_counts(const svdw_ctx* c, uint32_t phase) {
+    EqCounts n;
+    for (size_t k = 0; k < c->layout.size(); ++k) {
+        const svdw_region& r = c->layout[k];
+        const RegionChecks& rc = c->layout_chk[k];
+        if (r.phase != phase || !r.n) continue;
+        if (rc.scan) {
+            const uint64_t R = r.rows, unit = r.n / R, L = (unit - 1) / 3;
+            n.copies += R * 2 * L;
+            n.consts += R;
+            continue;
+        }
+        if (rc.eq.empty() || !rc.unit) continue;
+        const uint64_t nel = r.n / rc.unit;
+        for (uint32_t w : rc.eq) {
+            (eq_kind(w) == EQ_CONST ? n.consts : n.copies) += nel;
+            if (eq_kind(w) == EQ_EXT) n.external += nel;
+        }
+    }
+    return n;
+}
+static uint64_t perm_cell(uint32_t col, uint64_t row) { return (uint64_t)col << 32 | row; }
+int svdw_permutation_edges(svdw_ctx* c, uint64_t* edges, uint64_t cap, svdw_permutation_layout* out) {
+    return guarded([&] {
+        REQUIRE(c && out, "null argument");
+        REQUIRE(c->phys.valid, "svdw_permutation_edges: call svdw_physical_layout after the witness");
+        REQUIRE(!sharded(c), "svdw_permutation_edges: the witness of a sharded context is partial");
+        REQUIRE(!edges || !c->dry, "svdw_permutation_edges: the edge list needs a device context");
+        auto& P = c->phys;
+        const uint32_t k = P.k;
+        if (k > 28) fail(SVDW_ERANGE, "svdw_permutation_edges: k > 28");
+        const EqCounts n[2] = {eq_counts(c, 0), eq_counts(c, 1)};
+        const uint64_t D = c->consts.size(), rows = 1ull << k;
+        memset(out, 0, sizeof *out);
+        out->k = k;
+        out->advice[0] = (uint32_t)P.start[0].size();
+        out->advice[1] = (uint32_t)P.start[1].size();
+        out->fixed = (uint32_t)((D + rows - 1) >> k);
+        out->break_edges = P.bp[0].size() + P.bp[1].size();
+        out->copy_edges = n[0].copies - n[0].external + n[1].copies - n[1].external;
+        out->const_edges = n[0].consts + n[1].consts;
+        out->external_edges = n[0].external + n[1].external + (c->rlc.n ? 2 : 0);
+        out->external = out->external_edges ? 1 : 0;
+        out->total_cols = out->advice[0] + out->advice[1] + out->fixed + out->external;
+        out->edges = out->break_edges + out->copy_edges + out->const_edges + out->external_edges;
+        out->constants = D;
+        // constant i sits in row i / fixed: the last one has to lie above the blinding rows
+        if (D && (D - 1) / out->fixed >= P.R)
+            fail(SVDW_ERANGE, "svdw_permutation_edges: a constant's fixed row is not usable (raise k)");
+        if (out->total_cols > 65535) fail(SVDW_ERANGE, "svdw_permutation_edges: more than 65535 columns");
+        if (!edges) return;
+        REQUIRE(cap >= out->edges, "svdw_permutation_edges: cap is below the number of edges");
+        sync(c);
+        const uint32_t base[2] = {0, out->advice[0]}, fixed_col = out->advice[0] + out->advice[1],
+                       ext_col = fixed_col + out->fixed;
+        const PcColumns w{k, {base[0], base[1]}, ext_col};
+        // 1. the break cells, and the last edges of 4.: ctx_rlc's two copies (host)
+        std::vector<uint64_t> head, tail;
+        for (uint32_t ph = 0; ph < 2; ++ph)
+            for (size_t j = 0; j < P.bp[ph].size(); ++j) {
+                head.push_back(perm_cell(base[ph] + (uint32_t)j, P.bp[ph][j]));
+                head.push_back(perm_cell(base[ph] + (uint32_t)j + 1, 0));
+            }
+        for (uint32_t i = 0; c->rlc.n && i < 2; ++i) {
+            const uint32_t ph = (uint32_t)(c->rlc.src[i] >> 62);
+            REQUIRE(ph < 2, "internal: ctx_rlc copies a cell outside the streams");
+            const uint64_t p = phys_index(c, ph, c->rlc.src[i] & ((1ull << 62) - 1));
+            tail.push_back(perm_cell(base[ph] + (uint32_t)(p >> k), p & (rows - 1)));
+            tail.push_back(perm_cell(ext_col, i));
+        }
+        uint64_t* o_copy = edges + 2 * out->break_edges;
+        uint64_t* o_const = o_copy + 2 * out->copy_edges;
+        uint64_t* o_ext = o_const + 2 * out->const_edges;
+        if (!head.empty()) hipck(hipMemcpyAsync(edges, head.data(), head.size() * 8, hipMemcpyHostToDevice, c->st), "H2D");
+        if (!tail.empty())
+            hipck(hipMemcpyAsync(o_ext + 2 * (n[0].external + n[1].external), tail.data(), tail.size() * 8,
+                                 hipMemcpyHostToDevice, c->st), "H2D");
+        // the distinct constants, ascending as numbers, and per value the first record that holds it
+        std::vector<std::array<uint64_t, 4>> table;
+        for (const auto& v : c->consts)
+            table.push_back({v[0] | (uint64_t)v[1] << 32, v[2] | (uint64_t)v[3] << 32, v[4] | (uint64_t)v[5] << 32,
+                             v[6] | (uint64_t)v[7] << 32});
+        std::sort(table.begin(), table.end(), [](const std::array<uint64_t, 4>& a, const std::array<uint64_t, 4>& b) {
+            for (int q = 3; q >= 0; --q)
+                if (a[q] != b[q]) return a[q] < b[q];
+            return false;
+        });
+        const uint64_t maxc = std::max(n[0].copies, n[1].copies);
+        const size_t o_first = (D * 32 + 127) / 128 * 128, o_rank = o_first + (D * 8 + 127) / 128 * 128,
+                     o_err = o_rank + (D * 4 + 127) / 128 * 128, o_bsum = o_err + 128;
+        ensure_buf(c, c->eq_fx, o_bsum + std::max<uint64_t>(pc_tiles(maxc), 1) * 8);
+        char* fx = (char*)c->eq_fx.p;
+        unsigned long long* first = (unsigned long long*)(fx + o_first);
+        if (D) hipck(hipMemcpyAsync(fx, table.data(), D * 32, hipMemcpyHostToDevice, c->st), "H2D");
+        hipck(hipMemsetAsync(first, 0xff, o_err - o_first, c->st), "hipMemsetAsync");
+        hipck(hipMemsetAsync(fx + o_err, 0, 4, c->st), "hipMemsetAsync");
+        const auto& s0 = P.start[0];
+        const auto& s1 = P.start[1];
+        ensure_buf(c, c->eq_st, (s0.size() + s1.size() + 1) * sizeof(uint64_t));
+        uint64_t* st = (uint64_t*)c->eq_st.p;
+        if (!s0.empty()) hipck(hipMemcpyAsync(st, s0.data(), s0.size() * 8, hipMemcpyHostToDevice, c->st), "H2D");
+        if (!s1.empty())
+            hipck(hipMemcpyAsync(st + s0.size(), s1.data(), s1.size() * 8, hipMemcpyHostToDevice, c->st), "H2D");
+        // 2. - 4. per phase: the records (k_eq_records), onto the columns (k_eq_phys), into their groups
+        uint64_t g0 = 0;
+        for (uint32_t ph = 0; ph < 2; ++ph) {
+            uint64_t nc = 0, nk = 0;
+            eq_gen_device(c, ph, &nc, &nk);
+            REQUIRE(nc == n[ph].copies && nk == n[ph].consts, "internal: the record counts differ");
+            hipck(launch_eq_phys((uint64_t*)c->eq_cp.p, nc, (uint64_t*)c->eq_ks.p, nk, st, (uint32_t)s0.size(),
+                                 st + s0.size(), (uint32_t)s1.size(), ph, k, c->st), "k_eq_phys");
+            {
+                ProfScope ps(c, c->st, "k_pcw_split", 32.0 * (double)nc, 0);
+                hipck(launch_pcw_split((const uint64_t*)c->eq_cp.p, nc, w, ph, (uint64_t*)(fx + o_bsum), o_copy,
+                                       nc - n[ph].external, o_ext, n[ph].external, (unsigned*)(fx + o_err), c->st),
+                      "k_pcw_split");
+            }
+            {
+                ProfScope ps(c, c->st, "k_pcw_consts", 56.0 * (double)nk, 0);
+                hipck(launch_pcw_consts((const uint64_t*)c->eq_ks.p, nk, (const uint64_t*)fx, (uint32_t)D, g0, w, ph,
+                                        first, o_const, (unsigned*)(fx + o_err), c->st), "k_pcw_consts");
+            }
+            o_copy += 2 * (nc - n[ph].external);
+            o_ext += 2 * n[ph].external;
+            o_const += 2 * nk;
+            g0 += nk;
+            hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");   // the records are the next phase's too
+        }
+        // the constants in the order of their first record (one without a record: after the others)
+        std::vector<unsigned long long> hfirst(D);
+        unsigned err = 0;
+        if (D) hipck(hipMemcpyAsync(hfirst.data(), first, D * 8, hipMemcpyDeviceToHost, c->st), "D2H");
+        hipck(hipMemcpyAsync(&err, fx + o_err, 4, hipMemcpyDeviceToHost, c->st), "D2H");
+        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+        REQUIRE(!(err & 2), "internal: the external copy records differ from their count");
+        REQUIRE(!err, "svdw_permutation_edges: a constant record's value is not among the context's constants");
+        std::vector<uint32_t> order(D), rank(D);
+        for (uint32_t i = 0; i < D; ++i) order[i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return hfirst[a] < hfirst[b]; });
+        P.fixed.assign(D, fr_zero());
+        for (uint32_t i = 0; i < D; ++i) {
+            rank[order[i]] = i;
+            for (int q = 0; q < 8; ++q) P.fixed[i].w[q] = (uint32_t)(table[order[i]][q / 2] >> (32 * (q & 1)));
+        }
+        P.fixed_ready = true;
+        if (D) hipck(hipMemcpyAsync(fx + o_rank, rank.data(), D * 4, hipMemcpyHostToDevice, c->st), "H2D");
+        hipck(launch_pcw_place(edges + 2 * (out->break_edges + out->copy_edges), out->const_edges,
+                               (const uint32_t*)(fx + o_rank), (uint32_t)D, fixed_col, out->fixed, c->st),
+              "k_pcw_place");
+        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+    });
+}
+int svdw_assign_fixed(svdw_ctx* c, int form, void* fixed) {
+    return guarded([&] {
+        REQUIRE(c, "null argument");
+        check_form(form);
+        need_device(c, "svdw_assign_fixed");
+        auto& P = c->phys;
+        REQUIRE(P.valid && P.fixed_ready,
+                "svdw_assign_fixed: call svdw_permutation_edges with an edge list after svdw_physical_layout");
+        const uint64_t D = P.fixed.size(), rows = 1ull << P.k, F = (D + rows - 1) >> P.k;
+        if (!F) return;
+        REQUIRE(fixed, "null output");
+        sync(c);
+        // column j holds the constants j, j + F, ... from row 0 on
+        std::vector<Fr> cells(D);
+        std::vector<size_t> at(F + 1, 0);
+        for (uint64_t j = 0; j < F; ++j) at[j + 1] = at[j] + (D - j + F - 1) / F;
+        for (uint64_t i = 0; i < D; ++i)
+            cells[at[i % F] + i / F] = form == SVDW_FORM_MONTGOMERY ? fr_to_mont(P.fixed[i]) : P.fixed[i];
+        hipck(hipMemsetAsync(fixed, 0, F * rows * sizeof(Fr), c->st), "hipMemsetAsync");
+        for (uint64_t j = 0; j < F; ++j)
+            if (at[j + 1] > at[j])
+                hipck(hipMemcpyAsync((Fr*)fixed + j * rows, cells.data() + at[j], (at[j + 1] - at[j]) * sizeof(Fr),
+                                     hipMemcpyHostToDevice, c->st), "H2D");
+        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
     });
 }
 int svdw_rlc_trace(const svdw_ctx* c, uint64_t* cells, uint64_t* copies, uint32_t* n) {

@@ -89,12 +89,13 @@ struct ProverState {
     DBuf ntt_tab, ntt_tmp;                  // transforms (ntt.hpp): the stage and omega tables of ntt_k on the
     uint32_t ntt_k = 0;                     // device; the buffer between passes
     DBuf commit_ws;                         // commitments (commit.hpp): the window sums and one batch of tasks
+    DBuf cycles_ws;                         // sigma's cycles (permutation_cycles.hpp): the sort's arrays and tables
     // quotient (quotient.hpp): the extended columns of l_0, l_last, l_active (R form) of the key below, and the
     // scratch they are built in
     DBuf basis, basis_tmp;
     uint32_t basis_k = 0, basis_ek = 0, basis_unusable = 0;
     Fr basis_shift{};
-    std::vector<DBuf*> dbufs() { return {&scratch, &ntt_tab, &ntt_tmp, &basis, &basis_tmp, &commit_ws}; }
+    std::vector<DBuf*> dbufs() { return {&scratch, &ntt_tab, &ntt_tmp, &basis, &basis_tmp, &commit_ws, &cycles_ws}; }
 };
 
 // -------------------------------------------------------------- context
@@ -348,6 +349,9 @@ struct svdw_ctx {
         uint32_t k = 0, min_rows = 0;
         uint64_t R = 0;
         std::vector<uint64_t> start[2], bp[2];
+        // svdw_permutation_edges: the distinct constants in the order of their placement in the fixed columns
+        bool fixed_ready = false;
+        std::vector<Fr> fixed;
     } phys;
     DBuf gateq[2];
     std::vector<uint64_t>* gemm_log = nullptr;   // dry run: offsets of honest_prover_mat_mul
@@ -375,7 +379,7 @@ struct svdw_ctx {
     // device ingest (svdw_parse_svd_input_device) scratch
     DBuf ing_x, ing_e, ing_c, ing_p10, ing_val, ing_npos, ing_nd, ing_rpos, ing_kpos, ing_err, ing_q;
     // device equality records (eq_gen_device)
-    DBuf eq_cp, eq_ks, eq_reg, eq_w, eq_k, eq_err, eq_st;
+    DBuf eq_cp, eq_ks, eq_reg, eq_w, eq_k, eq_err, eq_st, eq_fx;
     // read-out (svdw_copy_cells, the host variants of svdw_export_* / svdw_dequantize_*):
     // two staging halves of at most kExportChunk bytes each, and the events that
     // order them ([0..1] half converted, [2..3] half copied out, [4..5] the join

@@ -15,6 +15,7 @@
 #include "lookup.hpp"
 #include "lookup_product.hpp"
 #include "permutation_product.hpp"
+#include "permutation_cycles.hpp"
 #include "ntt.hpp"
 #include "commit.hpp"
 #include "quotient.hpp"
@@ -507,6 +508,137 @@ int svdw_check_permutation_product(svdw_ctx* c, uint32_t k, uint32_t unusable_ro
         profiled(c, "k_pp_check", 64.0 * ncols * a.usable + 32.0 * a.nsets * a.rows,
                  [&] { return launch_pp_check(a, form, (const Fr*)z, wstep, d.cnt, c->st); });
         gp_check_result(c, d.cnt, result);
+    });
+}
+// ---- permutation argument: sigma's mapping from the copy constraints and its
+// check (permutation_cycles.hpp)
+// The argument checks of both entries, in the order include/svdw.h gives; false:
+// no columns, nothing to do.
+static bool pc_args(svdw_ctx* c, const char* fn, uint32_t k, uint32_t unusable_rows, uint32_t total_cols,
+                    const uint64_t* edges, uint64_t n_edges, const uint64_t* mapping, bool writes, PcShape* s) {
+    const std::string f(fn);
+    REQUIRE(c, "null argument");
+    need_k(f, k);
+    const uint64_t rows = 1ull << k;
+    if (unusable_rows >= rows) fail(SVDW_ERANGE, f + ": unusable_rows leaves no usable row");
+    need_device(c, f);
+    need_columns(f, total_cols);
+    const uint64_t cells = (uint64_t)total_cols << k;
+    if (cells > (1ull << 32)) fail(SVDW_ERANGE, f + ": total_cols << k above 2^32 (cell ids are 32-bit)");
+    if (n_edges > (1ull << 59)) fail(SVDW_ERANGE, f + ": n_edges above 2^59");
+    *s = PcShape{k, total_cols, rows, rows - unusable_rows, cells};
+    if (!total_cols) return false;
+    REQUIRE(mapping && (edges || !n_edges), "null argument");
+    const uintptr_t o0 = (uintptr_t)mapping, e0 = (uintptr_t)edges;
+    if (writes && n_edges) need_apart(f, "mapping", o0, o0 + cells * 8, "the edges", e0, e0 + n_edges * 16);
+    return true;
+}
+static size_t pc_pad(size_t bytes) { return (bytes + 127) / 128 * 128; }
+int svdw_permutation_cycles(svdw_ctx* c, uint32_t k, uint32_t unusable_rows, uint32_t total_cols,
+                            const uint64_t* edges, uint64_t n_edges, uint64_t* mapping,
+                            svdw_permutation_cycles_result* result) {
+    return guarded([&] {
+        REQUIRE(result, "null argument");
+        PcShape s{};
+        const bool any =
+            pc_args(c, "svdw_permutation_cycles", k, unusable_rows, total_cols, edges, n_edges, mapping, true, &s);
+        memset(result, 0, sizeof *result);
+        result->cells = s.cells;
+        result->edges = n_edges;
+        result->sort_passes = pc_sort_passes(s.cells);
+        if (!any) return;
+        sync(c);
+        const uint64_t n = s.cells, nt = pc_tiles(n);
+        // the flags (zeroed with the counters), the tile sums, the parents
+        const size_t o_bsum = pc_pad(n), o_parent = o_bsum + pc_pad(nt * 8);
+        const Staged d = stage_counters(c, o_parent + n * 4, pc_pad(n));
+        unsigned long long* cnt = d.cnt;   // [0] out of range, [1] self edges, [2] members, [3] classes, [4] largest
+        uint8_t* flag = (uint8_t*)d.free;
+        uint64_t* bsum = (uint64_t*)(d.free + o_bsum);
+        uint32_t* parent = (uint32_t*)(d.free + o_parent);
+        const double dn = (double)n, de = (double)n_edges;
+        profiled(c, "k_pc_init", 4.0 * dn, [&] { return launch_pc_init(s, parent, c->st); });
+        profiled(c, "k_pc_union", 16.0 * de, [&] { return launch_pc_union(s, edges, n_edges, parent, cnt, c->st); });
+        profiled(c, "k_pc_flatten", 8.0 * dn, [&] { return launch_pc_flatten(s, parent, c->st); });
+        profiled(c, "k_pc_flag", 5.0 * dn, [&] { return launch_pc_flag(s, parent, flag, c->st); });
+        profiled(c, "k_pc_scan", 5.0 * dn, [&] { return launch_pc_member_scan(s, parent, flag, bsum, cnt + 2, c->st); });
+        unsigned long long h[5];
+        read_counters(c, cnt, h, 3);
+        const uint64_t m = h[2];
+        REQUIRE(m <= n, "internal: more linked cells than cells");
+        if (m) {
+            // two (key, val) pairs of arrays, the digit table of one pass and its tile sums
+            const uint64_t nblk = pc_sort_blocks(m);
+            const size_t o_arr = pc_pad(m * 4), o_hist = 4 * o_arr, o_bs2 = o_hist + pc_pad(256 * nblk * 4);
+            DBuf& ws = c->prover.cycles_ws;
+            ensure_buf(c, ws, o_bs2 + pc_tiles(256 * nblk) * 8);
+            char* w = (char*)ws.p;
+            uint32_t *key = (uint32_t*)w, *val = (uint32_t*)(w + o_arr), *key2 = (uint32_t*)(w + 2 * o_arr),
+                     *val2 = (uint32_t*)(w + 3 * o_arr);
+            const double dm = (double)m;
+            profiled(c, "k_pc_compact", 5.0 * dn + 12.0 * dm,
+                     [&] { return launch_pc_compact(s, parent, flag, bsum, m, key, val, c->st); });
+            for (uint32_t p = 0; p < result->sort_passes; ++p) {
+                profiled(c, "k_pc_sort", 24.0 * dm, [&] {
+                    return launch_pc_sort_pass(key, val, m, 8 * p, (uint32_t*)(w + o_hist), (uint64_t*)(w + o_bs2),
+                                               key2, val2, c->st);
+                });
+                std::swap(key, key2);
+                std::swap(val, val2);
+            }
+            profiled(c, "k_pc_link", 16.0 * dm, [&] { return launch_pc_link(s, key, val, m, mapping, cnt + 3, c->st); });
+        }
+        profiled(c, "k_pc_identity", 5.0 * dn + 8.0 * (dn - (double)m),
+                 [&] { return launch_pc_identity(s, parent, flag, mapping, c->st); });
+        read_counters(c, cnt, h, 5);
+        result->out_of_range = h[0];
+        result->self_edges = h[1];
+        result->linked_cells = m;
+        result->classes = h[3];
+        result->largest_class = h[4];
+    });
+}
+int svdw_check_permutation_mapping(svdw_ctx* c, uint32_t k, uint32_t unusable_rows, uint32_t total_cols,
+                                   const uint64_t* edges, uint64_t n_edges, const uint64_t* mapping,
+                                   svdw_permutation_mapping_check* result) {
+    return guarded([&] {
+        REQUIRE(result, "null argument");
+        PcShape s{};
+        const bool any = pc_args(c, "svdw_check_permutation_mapping", k, unusable_rows, total_cols, edges, n_edges,
+                                 mapping, false, &s);
+        memset(result, 0, sizeof *result);
+        if (!any) return;
+        sync(c);
+        const uint64_t n = s.cells;
+        // hit counts and descents (zeroed with the counters), then the two buffers of (next, min) pairs
+        const size_t o_desc = pc_pad(n * 4), o_nm = 2 * o_desc, o_nm2 = o_nm + pc_pad(n * 8);
+        const Staged d = stage_counters(c, o_nm2 + n * 8, o_nm);
+        unsigned long long* cnt = d.cnt;   // [0] bad entries, [1] padding, [2] hits != 1, [3] cycles, [4] order,
+                                           // [5] edges, [6] edge failures
+        uint32_t *hit = (uint32_t*)d.free, *desc = (uint32_t*)(d.free + o_desc);
+        uint2 *nm = (uint2*)(d.free + o_nm), *nm2 = (uint2*)(d.free + o_nm2);
+        const double dn = (double)n;
+        profiled(c, "k_pm_hits", 20.0 * dn, [&] { return launch_pm_hits(s, mapping, hit, nm, cnt, c->st); });
+        uint32_t rounds = 0;
+        while ((1ull << rounds) < n) ++rounds;
+        for (uint32_t r = 0; r < rounds; ++r) {
+            profiled(c, "k_pm_double", 24.0 * dn, [&] { return launch_pm_double(s, nm, nm2, c->st); });
+            std::swap(nm, nm2);
+        }
+        profiled(c, "k_pm_descents", 24.0 * dn,
+                 [&] { return launch_pm_descents(s, mapping, hit, nm, desc, cnt + 2, c->st); });
+        profiled(c, "k_pm_cycles", 20.0 * dn, [&] { return launch_pm_cycles(s, mapping, nm, desc, cnt + 3, c->st); });
+        profiled(c, "k_pm_edges", 24.0 * (double)n_edges,
+                 [&] { return launch_pm_edges(s, edges, n_edges, nm, cnt + 5, c->st); });
+        unsigned long long h[7];
+        read_counters(c, cnt, h, 7);
+        result->cells_checked = n;
+        result->not_permutation = h[0] + h[2];
+        result->padding_failures = h[1];
+        result->cycles = h[3];
+        result->order_failures = h[4];
+        result->edges_checked = h[5];
+        result->edge_failures = h[6];
     });
 }
 // ---- transforms between Lagrange, coefficient and extended form, evaluation at

@@ -20,7 +20,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import (CheckResult, CommitCheck, CommitResult, EqCheck, OpenCheck, OpenResult, LookupCheck, LookupProductCheck, LookupProductResult, LookupResult, NttCheck, NttResult, PermutationProductCheck, PermutationProductResult, PhysParams, QuotientArgs, QuotientCheck, QuotientResult, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SvdwError,
+from ._lib import (CheckResult, CommitCheck, CommitResult, EqCheck, OpenCheck, OpenResult, LookupCheck, LookupProductCheck, LookupProductResult, LookupResult, NttCheck, NttResult, PermutationCyclesResult, PermutationLayout, PermutationMappingCheck, PermutationProductCheck, PermutationProductResult, PhysParams, QuotientArgs, QuotientCheck, QuotientResult, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SvdwError,
                    Vec, check, lib)
 
 P_MOD = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -747,6 +747,106 @@ class Context:
         check(lib().svdw_check_permutation_product(self._h, k, unusable_rows, _form(form), cp, sp, n, chunk_len,
                                                    b, g, z.data_ptr() if nsets else None, ct.byref(r)))
         return {k_: getattr(r, k_) for k_, _ in PermutationProductCheck._fields_}
+
+    def _cycles_args(self, edges, k: int, total_cols: int):
+        """(edge pointer, edge count, 2^k) of a [n, 2] int64 device edge list."""
+        import torch
+        if (not isinstance(edges, torch.Tensor) or not edges.is_cuda or edges.dtype != torch.int64
+                or not edges.is_contiguous() or edges.dim() != 2 or edges.shape[1] != 2):
+            raise SvdwError(-1, "edges must be a contiguous int64 device tensor [n, 2]")
+        rows = 1 << k if 0 <= k < 32 else 0
+        return (edges.data_ptr() if edges.shape[0] else None), edges.shape[0], rows
+
+    def permutation_cycles(self, edges, k: int, total_cols: int, unusable_rows: int = 6, out=None):
+        """(mapping, result): sigma's mapping from the copy constraints, an int64
+        device tensor [total_cols, 2^k] of col << 32 | row entries, as
+        permutation_values takes it (svdw_permutation_cycles): the cells of every
+        connected component of the edges over the rows below 2^k -
+        unusable_rows, linked in ascending (col, row) into one cycle; every other
+        cell maps to itself. edges: an int64 device tensor [n, 2] of col << 32 |
+        row cells. result: cells, edges, out_of_range, self_edges, classes,
+        linked_cells, largest_class, sort_passes."""
+        import torch
+        ep, ne, rows = self._cycles_args(edges, k, total_cols)
+        if out is None:
+            out = torch.empty((total_cols, rows), dtype=torch.int64, device=edges.device)
+        if (not out.is_cuda or out.dtype != torch.int64 or not out.is_contiguous()
+                or tuple(out.shape) != (total_cols, rows)):
+            raise SvdwError(-1, "out must be a contiguous int64 device tensor [total_cols, 2^k]")
+        r = PermutationCyclesResult()
+        _after_torch(self)
+        check(lib().svdw_permutation_cycles(self._h, k, unusable_rows, total_cols, ep, ne,
+                                            out.data_ptr() if out.numel() else None, ct.byref(r)))
+        _before_torch(self)
+        return out, {k_: getattr(r, k_) for k_, _ in PermutationCyclesResult._fields_ if k_ != "_pad"}
+
+    def check_permutation_mapping(self, edges, mapping, k: int, total_cols: int, unusable_rows: int = 6) -> dict:
+        """Device check of a mapping against the rule of permutation_cycles and
+        the edges (svdw_check_permutation_mapping): cells_checked,
+        not_permutation, order_failures, padding_failures, edges_checked,
+        edge_failures, cycles."""
+        import torch
+        ep, ne, rows = self._cycles_args(edges, k, total_cols)
+        if (not isinstance(mapping, torch.Tensor) or not mapping.is_cuda or mapping.dtype != torch.int64
+                or not mapping.is_contiguous() or tuple(mapping.shape) != (total_cols, rows)):
+            raise SvdwError(-1, "mapping must be a contiguous int64 device tensor [total_cols, 2^k]")
+        r = PermutationMappingCheck()
+        _after_torch(self)
+        check(lib().svdw_check_permutation_mapping(self._h, k, unusable_rows, total_cols, ep, ne,
+                                                   mapping.data_ptr() if mapping.numel() else None, ct.byref(r)))
+        return {k_: getattr(r, k_) for k_, _ in PermutationMappingCheck._fields_}
+
+    def permutation_layout(self) -> dict:
+        """The columns and edge counts of the permutation argument of the last
+        witness (svdw_permutation_edges without a list; also on a planning
+        context): k, advice [2], fixed, external, total_cols, edges, break_edges,
+        copy_edges, const_edges, external_edges, constants."""
+        lay = PermutationLayout()
+        check(lib().svdw_permutation_edges(self._h, None, 0, ct.byref(lay)))
+        d = {k_: getattr(lay, k_) for k_, _ in PermutationLayout._fields_}
+        d["advice"] = list(lay.advice)
+        return d
+
+    def permutation_edges(self):
+        """(edges, layout): the copy constraints of the last witness as an int64
+        device tensor [n, 2] of col << 32 | row cells over the columns [advice 0,
+        advice 1, fixed, external], in the order include/svdw.h gives
+        (svdw_permutation_edges), and the layout dict of permutation_layout."""
+        import torch
+        lay = self.permutation_layout()
+        edges = torch.empty((lay["edges"], 2), dtype=torch.int64, device=torch.device("cuda", self.device))
+        out = PermutationLayout()
+        _after_torch(self)
+        check(lib().svdw_permutation_edges(self._h, edges.data_ptr() if lay["edges"] else None, lay["edges"],
+                                           ct.byref(out)))
+        _before_torch(self)
+        return edges, lay
+
+    def assign_fixed(self, form: str = "canonical"):
+        """[num_fixed, 2^k, 32] u8 device cells in `form`: the fixed columns that
+        hold the witness's constants, placed as permutation_edges places them
+        (svdw_assign_fixed; call permutation_edges first)."""
+        import torch
+        lay = self.permutation_layout()
+        out = torch.empty((lay["fixed"], 1 << lay["k"], 32), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        _after_torch(self)
+        check(lib().svdw_assign_fixed(self._h, _form(form), out.data_ptr() if lay["fixed"] else None))
+        _before_torch(self)
+        return out
+
+    def witness_sigma(self, unusable_rows: int = 6, form: str = "canonical"):
+        """(sigma, mapping, layout): the permutation columns of the last witness
+        over [advice 0, advice 1, fixed, external], [total_cols, 2^k, 32] u8 in
+        `form`, from permutation_edges, permutation_cycles and
+        permutation_values; an edge out of range raises."""
+        edges, lay = self.permutation_edges()
+        mapping, res = self.permutation_cycles(edges, lay["k"], lay["total_cols"], unusable_rows)
+        if res["out_of_range"]:
+            raise SvdwError(-2, f"{res['out_of_range']} copy constraints touch a row >= 2^k - unusable_rows")
+        sigma, bad = self.permutation_values(lay["k"], mapping, form=form)
+        if bad:
+            raise SvdwError(-2, "internal: a mapping entry out of range")
+        return sigma, mapping, lay
 
     # ---- domain transforms (include/svdw.h, "domain transforms"; parity unpinned)
     @staticmethod

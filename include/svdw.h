@@ -697,8 +697,26 @@ int svdw_check_lookup_product(svdw_ctx* ctx, uint32_t phase, uint32_t unusable_r
  * Rows above `usable` are the prover's random blinding rows: the engine writes
  * zero. For an honest sigma only the last set ends at 1. A zero denominator
  * makes Z zero from the next row on, and in every later set. Deriving beta and
- * gamma, the blinding randomness, the commitments and building sigma from
- * equality records (keygen's cycle merge) stay with the caller. */
+ * gamma, the blinding randomness and the commitments stay with the caller.
+ *
+ * Sigma itself comes from the copy constraints by keygen's cycle merge, on the
+ * device (svdw_permutation_cycles below), in its order-independent form:
+ *   cells    total_cols columns of 2^k rows, a cell written col << 32 | row as
+ *            svdw_permutation_values takes it;
+ *   classes  the connected components of the graph whose edges are the copy
+ *            constraints, over the cells of rows < usable;
+ *   sigma    links the cells of each class in ascending (col, row) into one
+ *            cycle: every cell maps to the next one of its class, the last to
+ *            the first; a cell alone in its class and every cell of a row >=
+ *            usable maps to itself.
+ * halo2's serial Assembly::copy gives a sigma that depends on the order of its
+ * calls, which no parallel merge reproduces. The classes here are the partition
+ * that merge produces, so Z closes for exactly the same witnesses; only the
+ * order inside a cycle differs, and a verifying key made from this sigma
+ * differs from one made by halo2's serial keygen on the same circuit. It is
+ * believed to be what halo2's thread-safe-region keygen builds: restated from
+ * memory, PARITY UNPINNED like the rest. The mapping is the same bits from run
+ * to run and for any order or repetition of the edges. */
 /* delta and omega_k, canonical, 4 little-endian words each. Host only.
  * k outside 1..28: SVDW_ERANGE. */
 int svdw_permutation_constants(uint32_t k, uint64_t delta[4], uint64_t omega[4]);
@@ -746,6 +764,94 @@ int svdw_check_permutation_product(svdw_ctx* ctx, uint32_t k, uint32_t unusable_
                                    const void* const* columns, const void* const* sigma, uint32_t ncols,
                                    uint32_t chunk_len, const uint64_t beta[4], const uint64_t gamma[4],
                                    const void* z, svdw_permutation_product_check* result);
+typedef struct {
+    uint64_t cells, edges;
+    uint64_t out_of_range;    /* edges with an end outside the columns, the 2^k rows or the usable rows: skipped */
+    uint64_t self_edges;      /* in-range edges whose two ends are one cell: skipped */
+    uint64_t classes, linked_cells, largest_class;   /* of the classes of two or more cells */
+    uint32_t sort_passes, _pad;                      /* 8-bit digits that hold every cell id */
+} svdw_permutation_cycles_result;
+/* The mapping of sigma, by the rule above, from an edge list. edges: DEVICE
+ * array of n_edges x 2 cells col << 32 | row; mapping: DEVICE array of
+ * total_cols x 2^k uint64_t, every entry written, in the form
+ * svdw_permutation_values takes. An edge with an end outside the columns,
+ * outside the 2^k rows or in a row >= usable is halo2's bounds failure: it is
+ * counted in out_of_range and skipped, for the caller to treat as an error.
+ * Cell ids are 32-bit: total_cols << k above 2^32 is SVDW_ERANGE, which leaves
+ * out the witness of a 4096 x 4096 matrix. Needs no witness and no physical
+ * layout; any edge list does, so a caller who has further copies (those between
+ * lookup advice columns and the advice cells they repeat, which the engine does
+ * not list) appends them. Checks in this order: null ctx or result
+ * (SVDW_EINVAL), k outside 1..28 (SVDW_ERANGE), unusable_rows >= 2^k
+ * (SVDW_ERANGE), a planning context (SVDW_EINVAL), total_cols > 65535 or
+ * total_cols << k above 2^32 (SVDW_ERANGE); total_cols == 0: SVDW_OK, nothing
+ * is touched; then a null mapping, null edges with n_edges > 0, a mapping that
+ * overlaps the edges (SVDW_EINVAL). n_edges == 0 gives the identity. Returns
+ * after the device has finished. */
+int svdw_permutation_cycles(svdw_ctx* ctx, uint32_t k, uint32_t unusable_rows, uint32_t total_cols,
+                            const uint64_t* edges, uint64_t n_edges, uint64_t* mapping,
+                            svdw_permutation_cycles_result* result);
+typedef struct {
+    uint64_t cells_checked;
+    uint64_t not_permutation;   /* cells not hit exactly once, and entries out of range */
+    uint64_t order_failures;    /* cycles of two or more cells whose descents mapping[i] < i are not exactly 1 */
+    uint64_t padding_failures;  /* non-identity entries in rows >= usable */
+    uint64_t edges_checked;     /* edges with both ends in range */
+    uint64_t edge_failures;     /* of those, the edges whose ends lie in different cycles */
+    uint64_t cycles;            /* cycles of two or more cells */
+} svdw_permutation_mapping_check;
+/* A mapping against the rule and the edges, on the device, a debug aid: hit
+ * counts by one scatter pass, the minimum of every cycle by pointer doubling
+ * over the mapping, descents per cycle, the ends of every edge against the
+ * minima. It shares no union-find and no sort with svdw_permutation_cycles. It
+ * cannot see that the cycles are no coarser than the classes: two classes
+ * linked into one ascending cycle pass (compare `cycles` with `classes`, or the
+ * mapping with a host restatement as the tests do). Arguments and their checks
+ * as for svdw_permutation_cycles; the mapping is only read. */
+int svdw_check_permutation_mapping(svdw_ctx* ctx, uint32_t k, uint32_t unusable_rows, uint32_t total_cols,
+                                   const uint64_t* edges, uint64_t n_edges, const uint64_t* mapping,
+                                   svdw_permutation_mapping_check* result);
+typedef struct {
+    uint32_t k, advice[2], fixed, external, total_cols;   /* columns: advice per phase, fixed, external (0 or 1) */
+    uint64_t edges, break_edges, copy_edges, const_edges, external_edges;
+    uint64_t constants;       /* distinct constant values = svdw_physical_params.constants */
+} svdw_permutation_layout;
+/* The copy constraints of the last witness as the edge list
+ * svdw_permutation_cycles takes, after svdw_physical_layout. The argument's
+ * columns, in this order: the advice columns of phase 0 (columns_used[0]), those
+ * of phase 1 (columns_used[1]), num_fixed fixed columns, and one external column
+ * if and only if a record has source phase 2 (or the witness has the rlc_prefix):
+ * it holds the RLC context's cells, gamma at row 0, or at row 2 behind the
+ * prefix's two cells. The edges, in this order:
+ *   1. per phase, each break cell against row 0 of the next column;
+ *   2. the copy records of phase 0, then of phase 1, whose source is an advice
+ *      cell, (source, destination) at their first placement, in the order of
+ *      svdw_equalities;
+ *   3. the constant records of phase 0, then of phase 1, (cell, the fixed cell
+ *      of its value);
+ *   4. the records of source phase 2 of phase 0, then of phase 1, (external
+ *      cell, destination); with the rlc_prefix then the two copies of
+ *      svdw_rlc_trace, (advice cell, external row 0), (advice cell, external
+ *      row 1).
+ * The constants: the distinct values in the order of their first occurrence
+ * over the constant records of phase 0 and then of phase 1; constant i goes to
+ * fixed column i % num_fixed, row i / num_fixed (halo2-base's round-robin as
+ * recalled, PARITY UNPINNED); every other fixed cell is zero. A constant whose
+ * row would be one of the layout's minimum_rows last rows: SVDW_ERANGE.
+ * edges == NULL: the counts alone, also on a planning context. Else edges is a
+ * DEVICE array of cap x 2 cells, cap >= the layout's edges (else SVDW_EINVAL),
+ * on a device context. SVDW_EINVAL without a layout and on a row-sharded
+ * context; SVDW_ERANGE for k > 28 or more than 65535 columns. Copies between
+ * lookup advice columns and the advice cells they repeat are not listed: the
+ * lookup stream keeps no origin cell (svdw_equalities does not list them
+ * either); a caller who has them appends them. */
+int svdw_permutation_edges(svdw_ctx* ctx, uint64_t* edges, uint64_t cap, svdw_permutation_layout* layout);
+/* The fixed columns of that placement: fixed is a DEVICE array of num_fixed x
+ * 2^k cells in `form`, column-major. Needs a svdw_permutation_edges call with an
+ * edge list since the last svdw_physical_layout (it finds the order of the
+ * constants); SVDW_EINVAL otherwise, for an unknown form and on a planning
+ * context. No constants: SVDW_OK, nothing is touched. */
+int svdw_assign_fixed(svdw_ctx* ctx, int form, void* fixed);
 /* ------------------------------------------------------ domain transforms
  * halo2_proofs' poly::EvaluationDomain conversions of columns of BN254 Fr cells
  * on the device, eval_polynomial for a batch, and a check of a transform by
