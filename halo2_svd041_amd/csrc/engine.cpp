@@ -1,8 +1,10 @@
 // Host engine + C ABI (include/svdw.h) of the SVD-verify witness engine: the
-// context, the witness calls, the physical layout and its checks, read-out.
-// The prover calls on an assigned witness (lookup argument, grand products,
-// transforms, commitments, quotient) are in prover.cpp; engine_internal.hpp
-// holds what the two files share, the definition of svdw_ctx included.
+// context, the program builder, the witness calls, the captured graph, read-out,
+// ingest, options and profiling. The calls on a finished witness (checker,
+// physical layout, equality records, edge list) are in circuit.cpp, the prover
+// calls (lookup argument, grand products, transforms, commitments, quotient,
+// opening) in prover.cpp; engine_internal.hpp holds what the three files share,
+// the definition of svdw_ctx included.
 //
 // Each reference function (src/matrix/mod.rs, src/svd/mod.rs) becomes:
 //   1. a data-independent cell program built on the host by replaying the
@@ -25,7 +27,6 @@
 #include "ingest.hpp"
 #include "ingest_dev.hpp"
 #include "export.hpp"
-#include "permutation_cycles.hpp"                            // the witness's edge list (svdw_permutation_edges)
 #include "commit.hpp"                                       // kCommitMaxBits, for the "commit_window_bits" option
 
 // ------------------------------------------------------- host big integers
@@ -358,7 +359,7 @@ void sync(svdw_ctx* c) {
 }
 // After a pipelined svd_witness its tail (st2, st3) is not joined into st:
 // anything else queued on the context waits for it first.
-static void settle(svdw_ctx* c) {
+void settle(svdw_ctx* c) {
     if (c->dry || !c->tail_pending || c->call.in_pipe) return;
     for (int k = 0; k < 2; ++k)
         hipck(hipStreamWaitEvent(c->st, c->tail_ev[c->tail_last][k], 0), "hipStreamWaitEvent");
@@ -2861,12 +2862,12 @@ static svdw_counts vmg_restore(svdw_ctx* c, const Fr& gamma) {
 }
 // Every scratch buffer of a state (release, footprint).
 static std::vector<DBuf*> dbufs(svdw_ctx* c) {
-    std::vector<DBuf*> v = {&c->f64in, &c->digA, &c->digB, &c->digC, &c->chk, &c->chkg, &c->gateq[0], &c->gateq[1],
-                            &c->w1c, &c->w1t, &c->w2c, &c->w2t, &c->bits, &c->gpc, &c->gtab, &c->gpc_alt,
-                            &c->gtab_alt, &c->crtR, &c->gbits, &c->colpart, &c->qfold, &c->ing_x, &c->ing_e,
-                            &c->ing_c, &c->ing_p10, &c->ing_val, &c->ing_npos, &c->ing_nd, &c->ing_rpos,
-                            &c->ing_kpos, &c->ing_err, &c->ing_q, &c->eq_cp, &c->eq_ks, &c->eq_reg, &c->eq_w,
-                            &c->eq_k, &c->eq_err, &c->eq_st, &c->eq_fx, &c->exp_buf[0], &c->exp_buf[1]};
+    std::vector<DBuf*> v = {&c->f64in, &c->digA, &c->digB, &c->digC, &c->w1c, &c->w1t, &c->w2c, &c->w2t, &c->bits,
+                            &c->gpc, &c->gtab, &c->gpc_alt, &c->gtab_alt, &c->crtR, &c->gbits, &c->colpart, &c->qfold,
+                            &c->ing_x, &c->ing_e, &c->ing_c, &c->ing_p10, &c->ing_val, &c->ing_npos, &c->ing_nd,
+                            &c->ing_rpos, &c->ing_kpos, &c->ing_err, &c->ing_q, &c->exp_buf[0], &c->exp_buf[1],
+                            &c->staging.buf};
+    for (DBuf* d : c->circuit.dbufs()) v.push_back(d);
     for (DBuf* d : c->prover.dbufs()) v.push_back(d);
     for (int i = 0; i < kMaxScanJobs; ++i) {
         v.push_back(&c->wbc[i]);
@@ -3151,159 +3152,6 @@ static svdw_counts verify_mul_witness_api(svdw_ctx* c, const double* a, const do
     const svdw_counts k = verify_mul_witness(c, a, b, N, K, M, on_device, gamma);
     c->vmg.seen = key_now();
     return k;
-}
-
-// ------------------------------------------------------ equality lists
-// halo2-base's equality records of phase `phase` (svdw_equalities), in assign
-// order, from the layout table: per region its element program's eq words
-// (PB::eq) or the inner-product row pattern, with the source cells of the
-// loaded values (RegionChecks::esrc). copies: (source | store << 62,
-// destination) pairs, store 2 = the external init_rand cell; consts: (cell,
-// 4 canonical words).
-static uint64_t eq_src_cell(const RegionChecks::EqSrc& e, uint64_t i, uint64_t j, uint64_t t) {
-    if (e.kind == EQS_CHAIN) {
-        if (t == 0) return e.first | (uint64_t)e.first_phase << 62;
-        return (e.off + (t - 1) * (uint64_t)e.rs) | (uint64_t)e.phase << 62;
-    }
-    if (e.kind == EQS_MAT) {
-        if (e.diag_phase >= 0 && i == j) return e.diag_off | (uint64_t)e.diag_phase << 62;
-        if (i < e.rows && j < e.cols)
-            return (uint64_t)((int64_t)e.off + (int64_t)i * e.rs + (int64_t)j * e.cs) | (uint64_t)e.phase << 62;
-        if (e.pad_phase >= 0) return e.pad_off | (uint64_t)e.pad_phase << 62;
-    }
-    fail(SVDW_EINVAL, "svdw_equalities: a region's copy source is not in the cell streams");
-    return 0;
-}
-static void eq_lists(const svdw_ctx* c, uint32_t phase, std::vector<uint64_t>* copies,
-                     std::vector<uint64_t>* consts) {
-    auto konst = [&](uint64_t dst, const Fr& v) {
-        consts->push_back(dst);
-        for (int w = 0; w < 4; ++w) consts->push_back((uint64_t)v.w[2 * w] | (uint64_t)v.w[2 * w + 1] << 32);
-    };
-    const uint64_t me = (uint64_t)phase << 62;
-    for (size_t k = 0; k < c->layout.size(); ++k) {
-        const svdw_region& r = c->layout[k];
-        const RegionChecks& rc = c->layout_chk[k];
-        if (r.phase != phase || !r.n) continue;
-        if (rc.scan) {                                    // [C(0), E(a_j), E(v_j), W(s_j), ...]
-            const uint64_t R = r.rows, unit = r.n / R, L = (unit - 1) / 3;
-            for (uint64_t i = 0; i < R; ++i) {
-                const uint64_t base = r.off + i * unit;
-                konst(base, fr_zero());
-                for (uint64_t j = 0; j < L; ++j) {
-                    copies->push_back(eq_src_cell(rc.esrc[0], i, j, 0));
-                    copies->push_back(base + 1 + 3 * j);
-                    copies->push_back(eq_src_cell(rc.esrc[1], 0, 0, j));
-                    copies->push_back(base + 2 + 3 * j);
-                }
-            }
-            continue;
-        }
-        if (rc.eq.empty() || !rc.unit) continue;
-        const uint64_t unit = rc.unit, nel = r.n / unit, cols = rc.cols ? rc.cols : 1;
-        for (uint64_t e = 0; e < nel; ++e) {
-            const uint64_t base = r.off + e * unit, i = e / cols, j = e % cols;
-            for (uint32_t w : rc.eq) {
-                const uint32_t a = eq_a(w), at = eq_slot(w);
-                switch (eq_kind(w)) {
-                case EQ_CONST: konst(base + at, rc.eqk.at(a)); break;
-                case EQ_LOCAL: copies->push_back((base + a) | me); copies->push_back(base + at); break;
-                case EQ_VIEW:
-                    copies->push_back(eq_src_cell(rc.esrc[a], i, j, i));
-                    copies->push_back(base + at);
-                    break;
-                default:                                  // EQ_EXT: init_rand's RLC cell
-                    copies->push_back(c->ext_off | 2ull << 62); copies->push_back(base + at); break;
-                }
-            }
-        }
-    }
-}
-// The same records generated on the device (k_eq_records) into c->eq_cp /
-// c->eq_ks: per region its record counts are closed-form (elements x copy /
-// constant words, or rows x 2L copies + rows constants for a scan), so every
-// work item writes at a fixed offset and the order is eq_lists' order.
-static EqSrcDev eqsrc_dev(const RegionChecks::EqSrc& e) {
-    EqSrcDev d;
-    memset(&d, 0, sizeof d);
-    d.kind = e.kind; d.phase = (int32_t)e.phase; d.pad_phase = e.pad_phase; d.diag_phase = e.diag_phase;
-    d.first_phase = (int32_t)e.first_phase; d.off = e.off; d.pad_off = e.pad_off; d.diag_off = e.diag_off;
-    d.first = e.first; d.rs = e.rs; d.cs = e.cs; d.rows = e.rows; d.cols = e.cols;
-    return d;
-}
-static void eq_gen_device(svdw_ctx* c, uint32_t phase, uint64_t* n_copies, uint64_t* n_consts) {
-    std::vector<EqRegionDev> regs;
-    std::vector<uint32_t> words;
-    std::vector<Fr> konst;
-    uint64_t items = 0, nc = 0, nk = 0;
-    for (size_t k = 0; k < c->layout.size(); ++k) {
-        const svdw_region& r = c->layout[k];
-        const RegionChecks& rc = c->layout_chk[k];
-        if (r.phase != phase || !r.n) continue;
-        EqRegionDev d;
-        memset(&d, 0, sizeof d);
-        d.off = r.off;
-        d.item0 = items;
-        d.copy0 = nc;
-        d.const0 = nk;
-        d.src[0] = eqsrc_dev(rc.esrc[0]);
-        d.src[1] = eqsrc_dev(rc.esrc[1]);
-        if (rc.scan) {
-            const uint64_t R = r.rows, unit = r.n / R, L = (unit - 1) / 3;
-            REQUIRE(L >= 1, "internal: empty scan rows");
-            d.scan = 1; d.unit = (uint32_t)unit; d.L = (uint32_t)L;
-            d.nitems = R * L;
-            nc += R * 2 * L;
-            nk += R;
-        } else {
-            if (rc.eq.empty() || !rc.unit) continue;
-            const uint64_t nel = r.n / rc.unit;
-            d.unit = rc.unit;
-            d.cols = rc.cols ? rc.cols : 1;
-            d.w0 = (uint32_t)words.size();
-            d.nw = (uint32_t)rc.eq.size();
-            d.k0 = (uint32_t)konst.size();
-            for (uint32_t w : rc.eq) (eq_kind(w) == EQ_CONST ? d.nkw : d.ncw) += 1;
-            words.insert(words.end(), rc.eq.begin(), rc.eq.end());
-            konst.insert(konst.end(), rc.eqk.begin(), rc.eqk.end());
-            d.nitems = nel;
-            nc += nel * d.ncw;
-            nk += nel * d.nkw;
-        }
-        items += d.nitems;
-        regs.push_back(d);
-    }
-    *n_copies = nc;
-    *n_consts = nk;
-    ensure_buf(c, c->eq_cp, std::max<uint64_t>(nc, 1) * 16);
-    ensure_buf(c, c->eq_ks, std::max<uint64_t>(nk, 1) * 40);
-    ensure_buf(c, c->eq_reg, std::max<size_t>(regs.size(), 1) * sizeof(EqRegionDev));
-    ensure_buf(c, c->eq_w, std::max<size_t>(words.size(), 1) * 4);
-    ensure_buf(c, c->eq_k, std::max<size_t>(konst.size(), 1) * sizeof(Fr));
-    ensure_buf(c, c->eq_err, 4);
-    hipStream_t s = c->st;
-    if (!regs.empty())
-        hipck(hipMemcpyAsync(c->eq_reg.p, regs.data(), regs.size() * sizeof(EqRegionDev), hipMemcpyHostToDevice, s), "H2D");
-    if (!words.empty()) hipck(hipMemcpyAsync(c->eq_w.p, words.data(), words.size() * 4, hipMemcpyHostToDevice, s), "H2D");
-    if (!konst.empty())
-        hipck(hipMemcpyAsync(c->eq_k.p, konst.data(), konst.size() * sizeof(Fr), hipMemcpyHostToDevice, s), "H2D");
-    hipck(hipMemsetAsync(c->eq_err.p, 0, 4, s), "memset");
-    hipck(launch_eq_records((const EqRegionDev*)c->eq_reg.p, (uint32_t)regs.size(), items, (const uint32_t*)c->eq_w.p,
-                            (const Fr*)c->eq_k.p, phase, c->ext_off, (uint64_t*)c->eq_cp.p, (uint64_t*)c->eq_ks.p,
-                            (unsigned*)c->eq_err.p, s), "k_eq_records");
-    unsigned err = 0;
-    hipck(hipMemcpyAsync(&err, c->eq_err.p, 4, hipMemcpyDeviceToHost, s), "D2H");
-    hipck(hipStreamSynchronize(s), "hipStreamSynchronize");
-    REQUIRE(!err, "svdw_equalities: a region's copy source is not in the cell streams");
-}
-// virtual cell -> column-major physical index (the first placement of a break cell)
-static uint64_t phys_index(const svdw_ctx* c, uint32_t phase, uint64_t v) {
-    const auto& st = c->phys.start[phase];
-    size_t col = std::upper_bound(st.begin(), st.end(), v) - st.begin();
-    REQUIRE(col > 0, "internal: cell before column 0");
-    --col;
-    if (col > 0 && v == st[col]) --col;                   // break cell: its row in the column before
-    return ((uint64_t)col << c->phys.k) + (v - st[col]);
 }
 
 // ================================================================== C ABI
@@ -4166,553 +4014,6 @@ int svdw_set_shard(svdw_ctx* c, uint32_t rank, uint32_t world) {
         c->opt.shard_rank = rank;
         c->opt.shard_world = world;
         c->owned.clear();
-    });
-}
-// The parts of [off, off + n) of a phase's advice (lookup) stream this context
-// holds: all of it, or for a row-sharded rank the intersection with its owned
-// segments (whole row blocks).
-static std::vector<std::pair<uint64_t, uint64_t>> held(const svdw_ctx* c, uint32_t phase, bool lookup,
-                                                       uint64_t off, uint64_t n) {
-    std::vector<std::pair<uint64_t, uint64_t>> out;
-    if (!n) return out;
-    if (!sharded(c)) {
-        out.emplace_back(off, n);
-        return out;
-    }
-    for (const auto& o : c->owned) {
-        if (o.phase != phase || (o.lookup != 0) != lookup) continue;
-        const uint64_t b = std::max(off, o.off), e = std::min(off + n, o.off + o.n);
-        if (b < e) out.emplace_back(b, e - b);
-    }
-    return out;
-}
-int svdw_check_gates(svdw_ctx* c, svdw_check_result* out) {
-    return guarded([&] {
-        REQUIRE(c && out, "null argument");
-        need_device(c, "svdw_check_gates");
-        sync(c);
-        memset(out, 0, sizeof *out);
-        ensure_buf(c, c->chk, 6 * sizeof(unsigned long long));
-        unsigned long long* cnt = (unsigned long long*)c->chk.p;
-        hipck(hipMemsetAsync(cnt, 0, 6 * sizeof(unsigned long long), c->st), "hipMemsetAsync");
-        std::vector<uint32_t> scan_w;
-        for (size_t k = 0; k < c->layout.size(); ++k) {
-            const svdw_region& r = c->layout[k];
-            const RegionChecks& rc = c->layout_chk[k];
-            for (const auto& sg : held(c, r.phase, true, r.loff, r.nl))
-                hipck(launch_check_lookups(c->ph[r.phase].lk + sg.first, sg.second, c->LB, cnt + 2, c->st),
-                      "k_check_lookups");
-            const std::vector<uint32_t>* w = &rc.words;
-            uint64_t unit = rc.unit;
-            uint32_t cols = rc.cols;
-            if (!strcmp(r.tag, "scan") && r.rows) {         // rows [0, a0, v0, s0, a1, v1, s1, ...]
-                unit = r.n / r.rows;
-                cols = 1;
-                scan_w.clear();
-                for (uint64_t q = 0; q + 3 < unit; q += 3) scan_w.push_back(chk_gate((uint32_t)q));
-                w = &scan_w;
-            }
-            if (w->empty() || !unit || !r.n) continue;
-            ChkView v[kMaxViews];
-            for (int q = 0; q < kMaxViews; ++q) {
-                const RegionChecks::Src& s = rc.src[q];
-                v[q] = s.phase < 0 ? ChkView{nullptr, 0, 0, 0, 0}
-                                   : ChkView{c->ph[s.phase].adv + s.off, s.rs, s.cs, s.rows, s.cols};
-            }
-            const auto segs = held(c, r.phase, false, r.off, r.n);
-            if (segs.empty()) continue;
-            ensure_buf(c, c->chkg, w->size() * sizeof(uint32_t));
-            hipck(hipMemcpyAsync(c->chkg.p, w->data(), w->size() * sizeof(uint32_t),
-                                 hipMemcpyHostToDevice, c->st), "H2D");
-            for (const auto& sg : segs) {
-                if ((sg.first - r.off) % unit || sg.second % unit)
-                    fail(SVDW_EINVAL, "svdw_check_gates: owned segment is not whole elements");
-                hipck(launch_check_cells(c->ph[r.phase].adv + sg.first, (sg.first - r.off) / unit,
-                                         sg.second / unit, (uint32_t)unit, cols, (const uint32_t*)c->chkg.p,
-                                         (uint32_t)w->size(), v[0], v[1], cnt, c->st), "k_check_cells");
-            }
-            hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");   // chkg is reused
-        }
-        unsigned long long h[6];
-        hipck(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, c->st), "D2H");
-        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
-        out->gates_checked = h[0];
-        out->gate_failures = h[1];
-        out->lookups_checked = h[2];
-        out->lookup_failures = h[3];
-        out->copies_checked = h[4];
-        out->copy_failures = h[5];
-    });
-}
-// ------------------------------------------------- physical layout
-// Virtual -> physical assignment of a phase's cells (halo2-base 0.4.1, recalled;
-// oracle/pyoracle.py physical_layout): basic-gate advice columns of max_rows =
-// 2^k - minimum_rows usable rows. A column ends at a cell whose gate would
-// cross max_rows (q && row + 4 > max_rows) or at row max_rows - 1; that cell is
-// repeated at row 0 of the next column (copy-constrained) and its selector is
-// enabled there only.
-namespace {
-struct GateIndex {               // q(i): does a basic gate start at virtual cell i
-    struct Reg {
-        uint64_t off, n, unit;
-        bool scan;
-        std::vector<uint8_t> bit;    // per unit offset (program regions)
-    };
-    std::vector<Reg> regs;       // ascending offsets
-    GateIndex(const svdw_ctx* c, uint32_t phase) {
-        for (size_t k = 0; k < c->layout.size(); ++k) {
-            const svdw_region& r = c->layout[k];
-            if (r.phase != phase || !r.n) continue;
-            if (!strcmp(r.tag, "scan") && r.rows) {
-                regs.push_back(Reg{r.off, r.n, r.n / r.rows, true, {}});
-                continue;
-            }
-            const RegionChecks& rc = c->layout_chk[k];
-            Reg g{r.off, r.n, rc.unit, false, std::vector<uint8_t>(rc.unit, 0)};
-            bool any = false;
-            for (uint32_t w : rc.words)
-                if (chk_kind(w) == CHK_GATE) g.bit[w] = 1, any = true;
-            if (any && rc.unit) regs.push_back(std::move(g));
-        }
-    }
-    bool q(uint64_t i) const {
-        auto it = std::upper_bound(regs.begin(), regs.end(), i,
-                                   [](uint64_t x, const Reg& r) { return x < r.off; });
-        if (it == regs.begin()) return false;
-        const Reg& r = *--it;
-        if (i >= r.off + r.n) return false;
-        const uint64_t o = (i - r.off) % r.unit;
-        return r.scan ? (o % 3 == 0 && o + 3 < r.unit) : r.bit[o] != 0;
-    }
-};
-}  // namespace
-int svdw_physical_layout(svdw_ctx* c, uint32_t k, uint32_t minimum_rows, svdw_physical_params* out) {
-    return guarded([&] {
-        REQUIRE(c && out, "null argument");
-        REQUIRE(k >= 3 && k <= 40, "svdw_physical_layout: k out of range");
-        REQUIRE(!sharded(c), "svdw_physical_layout: the witness of a sharded context is partial");
-        REQUIRE((1ull << k) > (uint64_t)minimum_rows + 4, "svdw_physical_layout: minimum_rows >= 2^k - 4");
-        const uint64_t R = (1ull << k) - minimum_rows;
-        auto& P = c->phys;
-        P.valid = false;
-        P.fixed_ready = false;
-        P.fixed.clear();
-        P.k = k;
-        P.min_rows = minimum_rows;
-        P.R = R;
-        memset(out, 0, sizeof *out);
-        out->k = k;
-        out->minimum_rows = minimum_rows;
-        out->max_rows = R;
-        for (uint32_t ph = 0; ph < 2; ++ph) {
-            const uint64_t T = c->ph[ph].n, TL = c->ph[ph].nl;
-            P.start[ph].clear();
-            P.bp[ph].clear();
-            const GateIndex gi(c, ph);
-            for (uint64_t s = 0; T && true;) {
-                P.start[ph].push_back(s);
-                // the first of rows R-3, R-2 (gate crossing max_rows) or R-1 (last row)
-                uint64_t r = R - 3;
-                for (; r < R - 1; ++r)
-                    if (s + r < T && gi.q(s + r)) break;
-                if (s + r >= T) break;                     // the phase ends in this column
-                P.bp[ph].push_back(r);
-                s += r;
-            }
-            out->num_advice[ph] = (uint32_t)((T + R - 1) / R);
-            out->columns_used[ph] = (uint32_t)P.start[ph].size();
-            out->num_lookup_advice[ph] = (uint32_t)((TL + R - 1) / R);
-        }
-        out->constants = c->consts.size();
-        out->num_fixed = (uint32_t)((c->consts.size() + (1ull << k) - 1) >> k);
-        P.valid = true;
-    });
-}
-int svdw_break_points(const svdw_ctx* c, uint32_t phase, uint64_t* out, uint64_t cap, uint64_t* n) {
-    return guarded([&] {
-        REQUIRE(c && n && phase < 2, "bad argument");
-        REQUIRE(c->phys.valid, "svdw_break_points: call svdw_physical_layout after the witness");
-        const auto& b = c->phys.bp[phase];
-        *n = b.size();
-        for (uint64_t i = 0; i < cap && i < b.size() && out; ++i) out[i] = b[i];
-    });
-}
-// One column's cells: the stream range [s, s + len) then zero rows up to `rows`.
-// Canonical: a device copy and a memset; Montgomery: converted while it is
-// written (k_export pads the column itself), no second pass over the column.
-static void assign_column(svdw_ctx* c, int form, const Fr* stream, uint64_t s, uint64_t len, uint64_t rows, Fr* dst) {
-    if (form == SVDW_FORM_MONTGOMERY) {
-        hipck(launch_export(ExportSrc{stream, s, len, 0, 0, 0, 0}, form, dst, rows - len, c->st), "k_export");
-        return;
-    }
-    hipck(hipMemcpyAsync(dst, stream + s, len * sizeof(Fr), hipMemcpyDeviceToDevice, c->st), "D2D");
-    if (len < rows) hipck(hipMemsetAsync(dst + len, 0, (rows - len) * sizeof(Fr), c->st), "hipMemsetAsync");
-}
-int svdw_assign_columns(svdw_ctx* c, uint32_t phase, void* advice, uint8_t* selectors, void* lookup) {
-    return svdw_assign_columns_form(c, phase, SVDW_FORM_CANONICAL, advice, selectors, lookup);
-}
-int svdw_assign_columns_form(svdw_ctx* c, uint32_t phase, int form, void* advice, uint8_t* selectors, void* lookup) {
-    return guarded([&] {
-        REQUIRE(c && phase < 2, "bad argument");
-        check_form(form);
-        need_device(c, "svdw_assign_columns");
-        REQUIRE(c->phys.valid, "svdw_assign_columns: call svdw_physical_layout after the witness");
-        sync(c);
-        const auto& P = c->phys;
-        const uint64_t rows = 1ull << P.k, T = c->ph[phase].n, TL = c->ph[phase].nl;
-        const size_t ncols = P.start[phase].size();
-        REQUIRE(ncols <= (T + P.R - 1) / P.R,
-                "NOT ENOUGH ADVICE COLUMNS IN PHASE (columns_used > num_advice: raise k)");
-        if (selectors && T) {                              // q bits of the virtual stream
-            const GateIndex gi(c, phase);
-            const uint64_t nw = (T + 31) / 32;
-            ensure_buf(c, c->gateq[phase], nw * 4);
-            uint32_t* qb = (uint32_t*)c->gateq[phase].p;
-            hipck(hipMemsetAsync(qb, 0, nw * 4, c->st), "hipMemsetAsync");
-            for (const auto& r : gi.regs) {
-                std::vector<uint8_t> bits(r.unit);
-                for (uint64_t o = 0; o < r.unit; ++o)
-                    bits[o] = r.scan ? (o % 3 == 0 && o + 3 < r.unit) : r.bit[o];
-                ensure_buf(c, c->chkg, r.unit);
-                hipck(hipMemcpyAsync(c->chkg.p, bits.data(), r.unit, hipMemcpyHostToDevice, c->st), "H2D");
-                hipck(launch_gate_bits(qb, r.off, r.n, r.unit, (const uint8_t*)c->chkg.p, c->st),
-                      "k_gate_bits");
-                hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");   // chkg is reused
-            }
-        }
-        for (size_t col = 0; col < ncols; ++col) {
-            const uint64_t s = P.start[phase][col];
-            const bool last = col + 1 == ncols;
-            const uint64_t len = last ? T - s : P.bp[phase][col] + 1;
-            if (advice) {
-                assign_column(c, form, c->ph[phase].adv, s, len, rows, (Fr*)advice + col * rows);
-            }
-            if (selectors)
-                hipck(launch_selectors(selectors + col * rows, (const uint32_t*)c->gateq[phase].p, s, len,
-                                       rows, !last, c->st), "k_selectors");
-        }
-        if (lookup) {
-            const uint64_t nl = (TL + P.R - 1) / P.R;
-            for (uint64_t col = 0; col < nl; ++col) {
-                const uint64_t s = col * P.R, len = std::min(P.R, TL - s);
-                assign_column(c, form, c->ph[phase].lk, s, len, rows, (Fr*)lookup + col * rows);
-            }
-        }
-        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
-    });
-}
-int svdw_check_physical(svdw_ctx* c, uint32_t phase, const void* advice, const uint8_t* selectors,
-                        uint32_t ncols, svdw_check_result* out) {
-    return guarded([&] {
-        REQUIRE(c && advice && selectors && out && phase < 2, "bad argument");
-        need_device(c, "svdw_check_physical");
-        REQUIRE(c->phys.valid, "svdw_check_physical: call svdw_physical_layout first");
-        memset(out, 0, sizeof *out);
-        settle(c);
-        ensure_buf(c, c->chk, 6 * sizeof(unsigned long long));
-        unsigned long long* cnt = (unsigned long long*)c->chk.p;
-        hipck(hipMemsetAsync(cnt, 0, 6 * sizeof(unsigned long long), c->st), "hipMemsetAsync");
-        hipck(launch_check_physical((const Fr*)advice, selectors, 1ull << c->phys.k, ncols, cnt, c->st),
-              "k_check_physical");
-        const auto& bp = c->phys.bp[phase];
-        const uint32_t nb = (uint32_t)std::min<uint64_t>(bp.size(), ncols ? ncols - 1 : 0);
-        if (nb) {
-            ensure_buf(c, c->chkg, nb * sizeof(uint64_t));
-            hipck(hipMemcpyAsync(c->chkg.p, bp.data(), nb * sizeof(uint64_t), hipMemcpyHostToDevice, c->st),
-                  "H2D");
-            hipck(launch_check_breaks((const Fr*)advice, 1ull << c->phys.k, (const uint64_t*)c->chkg.p, nb,
-                                      cnt + 4, c->st), "k_check_breaks");
-        }
-        unsigned long long h[6];
-        hipck(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, c->st), "D2H");
-        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
-        out->gates_checked = h[0];
-        out->gate_failures = h[1];
-        out->copies_checked = h[4];
-        out->copy_failures = h[5];
-    });
-}
-int svdw_equalities(const svdw_ctx* c, uint32_t phase, uint64_t* copies, uint64_t copies_cap,
-                    uint64_t* n_copies, uint64_t* consts, uint64_t consts_cap, uint64_t* n_consts) {
-    return guarded([&] {
-        REQUIRE(c && phase < 2 && n_copies && n_consts, "bad argument");
-        if (!c->dry) {                       // generated on the device, copied out up to the caps
-            svdw_ctx* m = const_cast<svdw_ctx*>(c);
-            sync(m);
-            eq_gen_device(m, phase, n_copies, n_consts);
-            if (copies && copies_cap)
-                hipck(hipMemcpy(copies, m->eq_cp.p, std::min(copies_cap, *n_copies) * 16, hipMemcpyDeviceToHost), "D2H");
-            if (consts && consts_cap)
-                hipck(hipMemcpy(consts, m->eq_ks.p, std::min(consts_cap, *n_consts) * 40, hipMemcpyDeviceToHost), "D2H");
-            return;
-        }
-        std::vector<uint64_t> cp, cs;
-        eq_lists(c, phase, &cp, &cs);
-        *n_copies = cp.size() / 2;
-        *n_consts = cs.size() / 5;
-        if (copies) memcpy(copies, cp.data(), std::min<uint64_t>(copies_cap, cp.size() / 2) * 16);
-        if (consts) memcpy(consts, cs.data(), std::min<uint64_t>(consts_cap, cs.size() / 5) * 40);
-    });
-}
-int svdw_check_equalities(svdw_ctx* c, uint32_t phase, const void* columns0, const void* columns1,
-                          svdw_eq_check* out) {
-    return guarded([&] {
-        REQUIRE(c && phase < 2 && out, "bad argument");
-        need_device(c, "svdw_check_equalities");
-        // a record's source and destination cells may lie in other ranks' rows,
-        // which this context never wrote (svdw_check_gates checks a rank's own)
-        REQUIRE(!sharded(c), "svdw_check_equalities: not on a row-sharded context (its streams hold "
-                             "this rank's rows only; check the reassembled witness, or use svdw_check_gates)");
-        const bool phys = columns0 || columns1;
-        REQUIRE(!phys || (c->phys.valid && (phase == 0 ? columns0 != nullptr : columns0 && columns1)),
-                "svdw_check_equalities: physical columns need svdw_physical_layout and phase 0's "
-                "columns (and phase 1's for phase 1)");
-        memset(out, 0, sizeof *out);
-        sync(c);
-        uint64_t nc = 0, nk = 0;
-        eq_gen_device(c, phase, &nc, &nk);
-        if (phys) {                          // records onto the assigned columns
-            const auto& s0 = c->phys.start[0];
-            const auto& s1 = c->phys.start[1];
-            ensure_buf(c, c->eq_st, (s0.size() + s1.size() + 1) * sizeof(uint64_t));
-            uint64_t* st = (uint64_t*)c->eq_st.p;
-            if (!s0.empty()) hipck(hipMemcpyAsync(st, s0.data(), s0.size() * 8, hipMemcpyHostToDevice, c->st), "H2D");
-            if (!s1.empty())
-                hipck(hipMemcpyAsync(st + s0.size(), s1.data(), s1.size() * 8, hipMemcpyHostToDevice, c->st), "H2D");
-            hipck(launch_eq_phys((uint64_t*)c->eq_cp.p, nc, (uint64_t*)c->eq_ks.p, nk, st, (uint32_t)s0.size(),
-                                 st + s0.size(), (uint32_t)s1.size(), phase, c->phys.k, c->st), "k_eq_phys");
-        }
-        const Fr* s0 = phys ? (const Fr*)columns0 : c->ph[0].adv;
-        const Fr* s1 = phys ? (const Fr*)columns1 : c->ph[1].adv;
-        const Fr* dst = phase ? s1 : s0;
-        ensure_buf(c, c->chk, 6 * sizeof(unsigned long long));
-        unsigned long long* cnt = (unsigned long long*)c->chk.p;
-        hipck(hipMemsetAsync(cnt, 0, 6 * sizeof(unsigned long long), c->st), "hipMemsetAsync");
-        hipck(launch_check_copies(s0, s1, dst, (const uint64_t*)c->eq_cp.p, nc, c->ext_gamma, cnt, c->st),
-              "k_check_copies");
-        hipck(launch_check_consts(dst, (const uint64_t*)c->eq_ks.p, nk, cnt + 2, c->st), "k_check_consts");
-        unsigned long long h[4];
-        hipck(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, c->st), "D2H");
-        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
-        out->copies_checked = h[0];
-        out->copy_failures = h[1];
-        out->consts_checked = h[2];
-        out->const_failures = h[3];
-    });
-}
-// ---- the permutation argument's edge list and fixed columns of the witness
-// (include/svdw.h, svdw_permutation_edges; kernels: permutation_cycles.hpp)
-namespace {
-struct EqCounts {
-    uint64_t copies = 0, consts = 0, external = 0;        // external: the copies whose source is init_rand
-};
-}  // namespace
-// The record counts of a phase, as eq_gen_device and eq_lists produce them.
-static EqCounts eq_counts(const svdw_ctx* c, uint32_t phase) {
-    EqCounts n;
-    for (size_t k = 0; k < c->layout.size(); ++k) {
-        const svdw_region& r = c->layout[k];
-        const RegionChecks& rc = c->layout_chk[k];
-        if (r.phase != phase || !r.n) continue;
-        if (rc.scan) {
-            const uint64_t R = r.rows, unit = r.n / R, L = (unit - 1) / 3;
-            n.copies += R * 2 * L;
-            n.consts += R;
-            continue;
-        }
-        if (rc.eq.empty() || !rc.unit) continue;
-        const uint64_t nel = r.n / rc.unit;
-        for (uint32_t w : rc.eq) {
-            (eq_kind(w) == EQ_CONST ? n.consts : n.copies) += nel;
-            if (eq_kind(w) == EQ_EXT) n.external += nel;
-        }
-    }
-    return n;
-}
-static uint64_t perm_cell(uint32_t col, uint64_t row) { return (uint64_t)col << 32 | row; }
-int svdw_permutation_edges(svdw_ctx* c, uint64_t* edges, uint64_t cap, svdw_permutation_layout* out) {
-    return guarded([&] {
-        REQUIRE(c && out, "null argument");
-        REQUIRE(c->phys.valid, "svdw_permutation_edges: call svdw_physical_layout after the witness");
-        REQUIRE(!sharded(c), "svdw_permutation_edges: the witness of a sharded context is partial");
-        REQUIRE(!edges || !c->dry, "svdw_permutation_edges: the edge list needs a device context");
-        auto& P = c->phys;
-        const uint32_t k = P.k;
-        if (k > 28) fail(SVDW_ERANGE, "svdw_permutation_edges: k > 28");
-        const EqCounts n[2] = {eq_counts(c, 0), eq_counts(c, 1)};
-        const uint64_t D = c->consts.size(), rows = 1ull << k;
-        memset(out, 0, sizeof *out);
-        out->k = k;
-        out->advice[0] = (uint32_t)P.start[0].size();
-        out->advice[1] = (uint32_t)P.start[1].size();
-        out->fixed = (uint32_t)((D + rows - 1) >> k);
-        out->break_edges = P.bp[0].size() + P.bp[1].size();
-        out->copy_edges = n[0].copies - n[0].external + n[1].copies - n[1].external;
-        out->const_edges = n[0].consts + n[1].consts;
-        out->external_edges = n[0].external + n[1].external + (c->rlc.n ? 2 : 0);
-        out->external = out->external_edges ? 1 : 0;
-        out->total_cols = out->advice[0] + out->advice[1] + out->fixed + out->external;
-        out->edges = out->break_edges + out->copy_edges + out->const_edges + out->external_edges;
-        out->constants = D;
-        // constant i sits in row i / fixed: the last one has to lie above the blinding rows
-        if (D && (D - 1) / out->fixed >= P.R)
-            fail(SVDW_ERANGE, "svdw_permutation_edges: a constant's fixed row is not usable (raise k)");
-        if (out->total_cols > 65535) fail(SVDW_ERANGE, "svdw_permutation_edges: more than 65535 columns");
-        if (!edges) return;
-        REQUIRE(cap >= out->edges, "svdw_permutation_edges: cap is below the number of edges");
-        sync(c);
-        const uint32_t base[2] = {0, out->advice[0]}, fixed_col = out->advice[0] + out->advice[1],
-                       ext_col = fixed_col + out->fixed;
-        const PcColumns w{k, {base[0], base[1]}, ext_col};
-        // 1. the break cells, and the last edges of 4.: ctx_rlc's two copies (host)
-        std::vector<uint64_t> head, tail;
-        for (uint32_t ph = 0; ph < 2; ++ph)
-            for (size_t j = 0; j < P.bp[ph].size(); ++j) {
-                head.push_back(perm_cell(base[ph] + (uint32_t)j, P.bp[ph][j]));
-                head.push_back(perm_cell(base[ph] + (uint32_t)j + 1, 0));
-            }
-        for (uint32_t i = 0; c->rlc.n && i < 2; ++i) {
-            const uint32_t ph = (uint32_t)(c->rlc.src[i] >> 62);
-            REQUIRE(ph < 2, "internal: ctx_rlc copies a cell outside the streams");
-            const uint64_t p = phys_index(c, ph, c->rlc.src[i] & ((1ull << 62) - 1));
-            tail.push_back(perm_cell(base[ph] + (uint32_t)(p >> k), p & (rows - 1)));
-            tail.push_back(perm_cell(ext_col, i));
-        }
-        uint64_t* o_copy = edges + 2 * out->break_edges;
-        uint64_t* o_const = o_copy + 2 * out->copy_edges;
-        uint64_t* o_ext = o_const + 2 * out->const_edges;
-        if (!head.empty()) hipck(hipMemcpyAsync(edges, head.data(), head.size() * 8, hipMemcpyHostToDevice, c->st), "H2D");
-        if (!tail.empty())
-            hipck(hipMemcpyAsync(o_ext + 2 * (n[0].external + n[1].external), tail.data(), tail.size() * 8,
-                                 hipMemcpyHostToDevice, c->st), "H2D");
-        // the distinct constants, ascending as numbers, and per value the first record that holds it
-        std::vector<std::array<uint64_t, 4>> table;
-        for (const auto& v : c->consts)
-            table.push_back({v[0] | (uint64_t)v[1] << 32, v[2] | (uint64_t)v[3] << 32, v[4] | (uint64_t)v[5] << 32,
-                             v[6] | (uint64_t)v[7] << 32});
-        std::sort(table.begin(), table.end(), [](const std::array<uint64_t, 4>& a, const std::array<uint64_t, 4>& b) {
-            for (int q = 3; q >= 0; --q)
-                if (a[q] != b[q]) return a[q] < b[q];
-            return false;
-        });
-        const uint64_t maxc = std::max(n[0].copies, n[1].copies);
-        const size_t o_first = (D * 32 + 127) / 128 * 128, o_rank = o_first + (D * 8 + 127) / 128 * 128,
-                     o_err = o_rank + (D * 4 + 127) / 128 * 128, o_bsum = o_err + 128;
-        ensure_buf(c, c->eq_fx, o_bsum + std::max<uint64_t>(pc_tiles(maxc), 1) * 8);
-        char* fx = (char*)c->eq_fx.p;
-        unsigned long long* first = (unsigned long long*)(fx + o_first);
-        if (D) hipck(hipMemcpyAsync(fx, table.data(), D * 32, hipMemcpyHostToDevice, c->st), "H2D");
-        hipck(hipMemsetAsync(first, 0xff, o_err - o_first, c->st), "hipMemsetAsync");
-        hipck(hipMemsetAsync(fx + o_err, 0, 4, c->st), "hipMemsetAsync");
-        const auto& s0 = P.start[0];
-        const auto& s1 = P.start[1];
-        ensure_buf(c, c->eq_st, (s0.size() + s1.size() + 1) * sizeof(uint64_t));
-        uint64_t* st = (uint64_t*)c->eq_st.p;
-        if (!s0.empty()) hipck(hipMemcpyAsync(st, s0.data(), s0.size() * 8, hipMemcpyHostToDevice, c->st), "H2D");
-        if (!s1.empty())
-            hipck(hipMemcpyAsync(st + s0.size(), s1.data(), s1.size() * 8, hipMemcpyHostToDevice, c->st), "H2D");
-        // 2. - 4. per phase: the records (k_eq_records), onto the columns (k_eq_phys), into their groups
-        uint64_t g0 = 0;
-        for (uint32_t ph = 0; ph < 2; ++ph) {
-            uint64_t nc = 0, nk = 0;
-            eq_gen_device(c, ph, &nc, &nk);
-            REQUIRE(nc == n[ph].copies && nk == n[ph].consts, "internal: the record counts differ");
-            hipck(launch_eq_phys((uint64_t*)c->eq_cp.p, nc, (uint64_t*)c->eq_ks.p, nk, st, (uint32_t)s0.size(),
-                                 st + s0.size(), (uint32_t)s1.size(), ph, k, c->st), "k_eq_phys");
-            {
-                ProfScope ps(c, c->st, "k_pcw_split", 32.0 * (double)nc, 0);
-                hipck(launch_pcw_split((const uint64_t*)c->eq_cp.p, nc, w, ph, (uint64_t*)(fx + o_bsum), o_copy,
-                                       nc - n[ph].external, o_ext, n[ph].external, (unsigned*)(fx + o_err), c->st),
-                      "k_pcw_split");
-            }
-            {
-                ProfScope ps(c, c->st, "k_pcw_consts", 56.0 * (double)nk, 0);
-                hipck(launch_pcw_consts((const uint64_t*)c->eq_ks.p, nk, (const uint64_t*)fx, (uint32_t)D, g0, w, ph,
-                                        first, o_const, (unsigned*)(fx + o_err), c->st), "k_pcw_consts");
-            }
-            o_copy += 2 * (nc - n[ph].external);
-            o_ext += 2 * n[ph].external;
-            o_const += 2 * nk;
-            g0 += nk;
-            hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");   // the records are the next phase's too
-        }
-        // the constants in the order of their first record (one without a record: after the others)
-        std::vector<unsigned long long> hfirst(D);
-        unsigned err = 0;
-        if (D) hipck(hipMemcpyAsync(hfirst.data(), first, D * 8, hipMemcpyDeviceToHost, c->st), "D2H");
-        hipck(hipMemcpyAsync(&err, fx + o_err, 4, hipMemcpyDeviceToHost, c->st), "D2H");
-        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
-        REQUIRE(!(err & 2), "internal: the external copy records differ from their count");
-        REQUIRE(!err, "svdw_permutation_edges: a constant record's value is not among the context's constants");
-        std::vector<uint32_t> order(D), rank(D);
-        for (uint32_t i = 0; i < D; ++i) order[i] = i;
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return hfirst[a] < hfirst[b]; });
-        P.fixed.assign(D, fr_zero());
-        for (uint32_t i = 0; i < D; ++i) {
-            rank[order[i]] = i;
-            for (int q = 0; q < 8; ++q) P.fixed[i].w[q] = (uint32_t)(table[order[i]][q / 2] >> (32 * (q & 1)));
-        }
-        P.fixed_ready = true;
-        if (D) hipck(hipMemcpyAsync(fx + o_rank, rank.data(), D * 4, hipMemcpyHostToDevice, c->st), "H2D");
-        hipck(launch_pcw_place(edges + 2 * (out->break_edges + out->copy_edges), out->const_edges,
-                               (const uint32_t*)(fx + o_rank), (uint32_t)D, fixed_col, out->fixed, c->st),
-              "k_pcw_place");
-        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
-    });
-}
-int svdw_assign_fixed(svdw_ctx* c, int form, void* fixed) {
-    return guarded([&] {
-        REQUIRE(c, "null argument");
-        check_form(form);
-        need_device(c, "svdw_assign_fixed");
-        auto& P = c->phys;
-        REQUIRE(P.valid && P.fixed_ready,
-                "svdw_assign_fixed: call svdw_permutation_edges with an edge list after svdw_physical_layout");
-        const uint64_t D = P.fixed.size(), rows = 1ull << P.k, F = (D + rows - 1) >> P.k;
-        if (!F) return;
-        REQUIRE(fixed, "null output");
-        sync(c);
-        // column j holds the constants j, j + F, ... from row 0 on
-        std::vector<Fr> cells(D);
-        std::vector<size_t> at(F + 1, 0);
-        for (uint64_t j = 0; j < F; ++j) at[j + 1] = at[j] + (D - j + F - 1) / F;
-        for (uint64_t i = 0; i < D; ++i)
-            cells[at[i % F] + i / F] = form == SVDW_FORM_MONTGOMERY ? fr_to_mont(P.fixed[i]) : P.fixed[i];
-        hipck(hipMemsetAsync(fixed, 0, F * rows * sizeof(Fr), c->st), "hipMemsetAsync");
-        for (uint64_t j = 0; j < F; ++j)
-            if (at[j + 1] > at[j])
-                hipck(hipMemcpyAsync((Fr*)fixed + j * rows, cells.data() + at[j], (at[j + 1] - at[j]) * sizeof(Fr),
-                                     hipMemcpyHostToDevice, c->st), "H2D");
-        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
-    });
-}
-int svdw_rlc_trace(const svdw_ctx* c, uint64_t* cells, uint64_t* copies, uint32_t* n) {
-    return guarded([&] {
-        REQUIRE(c && n, "null argument");
-        *n = c->rlc.n;
-        if (!c->rlc.n) return;
-        REQUIRE(cells && copies, "null output");
-        for (uint32_t k = 0; k < c->rlc.n; ++k)
-            for (int w = 0; w < 4; ++w)
-                cells[4 * k + w] = (uint64_t)c->rlc.cells[k].w[2 * w] | (uint64_t)c->rlc.cells[k].w[2 * w + 1] << 32;
-        copies[0] = c->rlc.src[0];
-        copies[1] = c->rlc.src[1];
-    });
-}
-int svdw_layout(const svdw_ctx* c, svdw_region* out, uint64_t cap, uint64_t* n) {
-    return guarded([&] {
-        REQUIRE(c && n, "null argument");
-        *n = c->layout.size();
-        for (uint64_t i = 0; i < cap && i < c->layout.size(); ++i) out[i] = c->layout[i];
-    });
-}
-int svdw_shard_segments(const svdw_ctx* c, svdw_segment* out, uint64_t cap, uint64_t* n) {
-    return guarded([&] {
-        REQUIRE(c && n, "null argument");
-        *n = c->owned.size();
-        for (uint64_t i = 0; i < c->owned.size() && i < cap && out; ++i)
-            out[i] = svdw_segment{c->owned[i].phase, c->owned[i].lookup, c->owned[i].off,
-                                  c->owned[i].n};
     });
 }
 int svdw_abi_version(void) { return SVDW_ABI_VERSION; }

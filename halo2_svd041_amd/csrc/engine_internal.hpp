@@ -1,10 +1,11 @@
-// What engine.cpp (the witness engine) and prover.cpp (the prover calls) share:
-// the error plumbing of the C ABI, device buffers, the host Fr helpers of the
-// entry points, the prover calls' state, the context (svdw_ctx) and the few
-// engine.cpp functions on it that prover.cpp calls.
+// What engine.cpp (the witness engine), circuit.cpp (the assigned-witness calls)
+// and prover.cpp (the prover calls) share: the C ABI's error plumbing, device
+// buffers, the entries' host Fr helpers, the two families' state, the context
+// (svdw_ctx), the engine.cpp functions the other files call, the staged call.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <array>
 #include <chrono>
@@ -19,7 +20,7 @@
 #include "../../include/svdw.h"
 #include "kernels.hpp"
 
-using namespace svdw;                                      // (both files are the engine's own)
+using namespace svdw;                                      // (the files are the engine's own)
 
 // ------------------------------------------------------------------ errors
 inline thread_local std::string g_err;
@@ -77,13 +78,25 @@ inline bool fr_reduced(const Fr& x) {
     return sub_p(t, x) != 0;                               // x - p borrows: x < p
 }
 
-// ------------------------------------------------- prover calls' state
+inline void need_columns(const std::string& f, uint32_t n, const char* where = "") {   // under the entry's name f
+    if (n > 65535) fail(SVDW_ERANGE, f + ": more than 65535 columns" + where);
+}
+// ------------------------------------------------- the families' state
+// The device scratch of every staged call of either family (stage, below), in the
+// staged-call layout, and the host vector it is uploaded from.
+struct StagedScratch {
+    DBuf buf;
+    std::vector<char> upload;
+};
+// What the assigned-witness calls (circuit.cpp) keep on a context.
+struct CircuitState {
+    DBuf eq_cp, eq_ks;                      // the equality records of one phase (eq_gen_device): live within a call
+    DBuf eq_in;                             // the generator's input: err word, regions, eq words, constants
+    DBuf gateq[2];                          // svdw_assign_columns: the gate-start bits of a phase's virtual stream
+    std::vector<DBuf*> dbufs() { return {&eq_cp, &eq_ks, &eq_in, &gateq[0], &gateq[1]}; }
+};
 // What the prover calls (prover.cpp) keep on a context between calls.
 struct ProverState {
-    // every call's device scratch, in the staged-call layout: counters,
-    // pointers, Fr cells, then the call's own arrays
-    DBuf scratch;
-    std::vector<char> upload;               // host staging of a call's pointers and cells
     std::vector<Fr> omega;                  // host: the two-level omega tables of the domain 2^omega_k
     uint32_t omega_k = 0;
     DBuf ntt_tab, ntt_tmp;                  // transforms (ntt.hpp): the stage and omega tables of ntt_k on the
@@ -95,7 +108,7 @@ struct ProverState {
     DBuf basis, basis_tmp;
     uint32_t basis_k = 0, basis_ek = 0, basis_unusable = 0;
     Fr basis_shift{};
-    std::vector<DBuf*> dbufs() { return {&scratch, &ntt_tab, &ntt_tmp, &basis, &basis_tmp, &commit_ws, &cycles_ws}; }
+    std::vector<DBuf*> dbufs() { return {&ntt_tab, &ntt_tmp, &basis, &basis_tmp, &commit_ws, &cycles_ws}; }
 };
 
 // -------------------------------------------------------------- context
@@ -261,7 +274,7 @@ struct svdw_ctx {
     // after_previous or the captured graph's fork from st, and the pipelined
     // svd_witness (whose side streams do not wait for st) waits explicitly
     hipEvent_t xwait_side = nullptr;
-    DBuf f64in, digA, digB, digC, w1c, w1t, w2c, w2t, bits, gpc, gtab, crtR, gbits, chk, chkg;
+    DBuf f64in, digA, digB, digC, w1c, w1t, w2c, w2t, bits, gpc, gtab, crtR, gbits;
     DBuf gpc_alt, gtab_alt;                 // pipelined svd_witness: gamma tables of the other parity
     DBuf wbc[kMaxScanJobs], wbt[kMaxScanJobs];   // b.v per batched verify_mul (canonical, table)
     // gamma^j (canonical gpc, scaled table gtab, kernels.hpp kTabSlots) of the
@@ -353,7 +366,6 @@ struct svdw_ctx {
         bool fixed_ready = false;
         std::vector<Fr> fixed;
     } phys;
-    DBuf gateq[2];
     std::vector<uint64_t>* gemm_log = nullptr;   // dry run: offsets of honest_prover_mat_mul
     std::vector<hipEvent_t> deps;           // dependency events (no timing)
     size_t dep_next = 0;
@@ -378,13 +390,13 @@ struct svdw_ctx {
     std::vector<Batch> batches;
     // device ingest (svdw_parse_svd_input_device) scratch
     DBuf ing_x, ing_e, ing_c, ing_p10, ing_val, ing_npos, ing_nd, ing_rpos, ing_kpos, ing_err, ing_q;
-    // device equality records (eq_gen_device)
-    DBuf eq_cp, eq_ks, eq_reg, eq_w, eq_k, eq_err, eq_st, eq_fx;
     // read-out (svdw_copy_cells, the host variants of svdw_export_* / svdw_dequantize_*):
     // two staging halves of at most kExportChunk bytes each, and the events that
     // order them ([0..1] half converted, [2..3] half copied out, [4..5] the join
     // of st2 / st3 into st ahead of every read-out)
     DBuf exp_buf[2];
+    StagedScratch staging;                  // every staged call's scratch (circuit.cpp, prover.cpp)
+    CircuitState circuit;                   // the assigned-witness calls (circuit.cpp)
     ProverState prover;                     // the prover calls (prover.cpp)
     hipEvent_t exp_ev[6] = {};
     // ---- captured verify_mul_witness ("graph", vm_graph): the launch sequence of
@@ -415,9 +427,10 @@ struct svdw_ctx {
     } vmg;
 };
 
-// engine.cpp's functions that prover.cpp calls too (the library exports only the C ABI).
+// engine.cpp's functions that circuit.cpp and prover.cpp call too (the library exports only the C ABI).
 #pragma GCC visibility push(hidden)
 void sync(svdw_ctx* c);                                    // every stream of the context has run dry
+void settle(svdw_ctx* c);                                  // st waits for the tail of a pipelined svd_witness
 void ensure_buf(svdw_ctx* c, DBuf& b, size_t bytes);
 void flush_batch(svdw_ctx* c, hipStream_t s, hipStream_t waiter = nullptr, hipEvent_t then_wait = nullptr);
 #pragma GCC visibility pop
@@ -473,3 +486,55 @@ struct ProfScope {
         (void)hipEventRecord(c->recs[idx].e1, s);
     }
 };
+// ------------------------------------------------------- the staged call
+// What a call staged in the context's scratch ("Host code of the calls
+// on a witness and the staged-call layout"): 128 bytes of counters, the pointers
+// padded to 32 bytes, the Fr cells, then the call's own arrays from `free` on.
+struct Staged {
+    unsigned long long* cnt = nullptr;
+    const Fr* const* ptrs = nullptr;
+    const Fr* cells = nullptr;
+    char* free = nullptr;
+};
+// Size the scratch for the na pointers of a then the nb of b, ncells Fr cells
+// (written by fill) and scratch_bytes after them; zero the counters on the
+// stream, and with them the first `zeroed` bytes of free where nothing is
+// uploaded in between; upload pointers and cells in one copy.
+template <class Fill>
+Staged stage(svdw_ctx* c, const void* const* a, uint32_t na, const void* const* b, uint32_t nb, size_t ncells,
+             size_t scratch_bytes, Fill&& fill, size_t zeroed = 0) {
+    StagedScratch& ss = c->staging;
+    const size_t pbytes = ((size_t)(na + nb) * sizeof(void*) + 31) / 32 * 32, up = pbytes + ncells * sizeof(Fr);
+    REQUIRE(!zeroed || !up, "internal: zeroed scratch behind an upload");
+    ss.upload.assign(up, 0);
+    if (na) memcpy(ss.upload.data(), a, na * sizeof(void*));
+    if (nb) memcpy(ss.upload.data() + na * sizeof(void*), b, nb * sizeof(void*));
+    fill((Fr*)(ss.upload.data() + pbytes));
+    ensure_buf(c, ss.buf, 128 + up + scratch_bytes);
+    char* base = (char*)ss.buf.p;
+    hipck(hipMemsetAsync(base, 0, 128 + zeroed, c->st), "hipMemsetAsync");
+    if (up) hipck(hipMemcpyAsync(base + 128, ss.upload.data(), up, hipMemcpyHostToDevice, c->st), "H2D");
+    return Staged{(unsigned long long*)base, (const Fr* const*)(base + 128), (const Fr*)(base + 128 + pbytes),
+                  base + 128 + up};
+}
+// The cells as `bytes` bytes of anything (a call's words, bit tables, indices),
+// copied from src: the kernels read them from Staged::cells on.
+inline Staged stage_bytes(svdw_ctx* c, const void* src, size_t bytes, size_t scratch_bytes = 0) {
+    const auto fill = [&](Fr* t) { if (bytes) memcpy(t, src, bytes); };
+    return stage(c, nullptr, 0, nullptr, 0, (bytes + sizeof(Fr) - 1) / sizeof(Fr), scratch_bytes, fill);
+}
+// The counters alone, and scratch_bytes whose first `zeroed` are zeroed with them.
+inline Staged stage_counters(svdw_ctx* c, size_t scratch_bytes = 0, size_t zeroed = 0) {
+    return stage(c, nullptr, 0, nullptr, 0, 0, scratch_bytes, [](Fr*) {}, zeroed);
+}
+// h[0..n) = the counters, once the stream has run dry.
+inline void read_counters(svdw_ctx* c, const unsigned long long* cnt, unsigned long long* h, size_t n) {
+    hipck(hipMemcpyAsync(h, cnt, n * sizeof *h, hipMemcpyDeviceToHost, c->st), "D2H");
+    hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
+}
+// One launch on the context's stream under its profile label.
+template <class Launch>
+void profiled(svdw_ctx* c, const char* label, double bytes, Launch&& launch) {
+    ProfScope ps(c, c->st, label, bytes, 0);
+    hipck(launch(), label);
+}

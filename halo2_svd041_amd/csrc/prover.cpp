@@ -2,10 +2,11 @@
 // lookup argument, the grand products of the lookup and permutation arguments,
 // the transforms, the commitments, the quotient and the opening. Each entry
 // checks its arguments in the order include/svdw.h documents, stages what its
-// kernels read in the context's prover scratch (Staged below) and queues the
-// kernels on the context's stream. The context (svdw_ctx, engine_internal.hpp) is
-// engine.cpp's: of it this file uses the stream, the profiler, sync, ensure_buf,
-// its own ProverState and the few facts its argument checks read.
+// kernels read in the context's staged scratch (stage, engine_internal.hpp) and
+// queues the kernels on the context's stream. The context (svdw_ctx,
+// engine_internal.hpp) is engine.cpp's: of it this file uses the stream, the
+// profiler, sync, ensure_buf, the staged scratch, its own ProverState and the
+// few facts its argument checks read.
 #include <string.h>
 
 #include <algorithm>
@@ -21,64 +22,16 @@
 #include "quotient.hpp"
 #include "open.hpp"
 
-// ---- what the families share: argument checks, the staged call, profiling
-// The checks several entries repeat, each under the entry's name f.
+// ---- what the families share: argument checks
+// The checks several entries repeat, each under the entry's name f (need_columns: engine_internal.hpp).
 static void need_k(const std::string& f, uint32_t k) {
     if (k < 1 || k > 28) fail(SVDW_ERANGE, f + ": k must be in [1, 28]");
-}
-static void need_columns(const std::string& f, uint32_t n, const char* where = "") {
-    if (n > 65535) fail(SVDW_ERANGE, f + ": more than 65535 columns" + where);
 }
 static void need_pointer(const std::string& f, const void* p) { REQUIRE(p, f + ": null column pointer"); }
 // [o0, o1) (the output `out`) and [i0, i1) (`in`) do not meet.
 static void need_apart(const std::string& f, const char* out, uintptr_t o0, uintptr_t o1, const char* in, uintptr_t i0,
                        uintptr_t i1) {
     REQUIRE(i1 <= o0 || o1 <= i0, f + ": " + out + " overlaps " + in);
-}
-// What a call staged in the context's prover scratch ("Prover calls:
-// host code and the staged-call layout"): 128 bytes of counters, the pointers padded to 32 bytes, the Fr
-// cells, then the call's own arrays from `free` on.
-struct Staged {
-    unsigned long long* cnt = nullptr;
-    const Fr* const* ptrs = nullptr;
-    const Fr* cells = nullptr;
-    char* free = nullptr;
-};
-// Size the scratch for the na pointers of a then the nb of b, ncells Fr cells
-// (written by fill) and scratch_bytes after them; zero the counters on the
-// stream, and with them the first `zeroed` bytes of free where nothing is
-// uploaded in between; upload pointers and cells in one copy.
-template <class Fill>
-static Staged stage(svdw_ctx* c, const void* const* a, uint32_t na, const void* const* b, uint32_t nb, size_t ncells,
-                    size_t scratch_bytes, Fill&& fill, size_t zeroed = 0) {
-    ProverState& ps = c->prover;
-    const size_t pbytes = ((size_t)(na + nb) * sizeof(void*) + 31) / 32 * 32, up = pbytes + ncells * sizeof(Fr);
-    REQUIRE(!zeroed || !up, "internal: zeroed scratch behind an upload");
-    ps.upload.assign(up, 0);
-    if (na) memcpy(ps.upload.data(), a, na * sizeof(void*));
-    if (nb) memcpy(ps.upload.data() + na * sizeof(void*), b, nb * sizeof(void*));
-    fill((Fr*)(ps.upload.data() + pbytes));
-    ensure_buf(c, ps.scratch, 128 + up + scratch_bytes);
-    char* base = (char*)ps.scratch.p;
-    hipck(hipMemsetAsync(base, 0, 128 + zeroed, c->st), "hipMemsetAsync");
-    if (up) hipck(hipMemcpyAsync(base + 128, ps.upload.data(), up, hipMemcpyHostToDevice, c->st), "H2D");
-    return Staged{(unsigned long long*)base, (const Fr* const*)(base + 128), (const Fr*)(base + 128 + pbytes),
-                  base + 128 + up};
-}
-// The counters alone, and scratch_bytes whose first `zeroed` are zeroed with them.
-static Staged stage_counters(svdw_ctx* c, size_t scratch_bytes = 0, size_t zeroed = 0) {
-    return stage(c, nullptr, 0, nullptr, 0, 0, scratch_bytes, [](Fr*) {}, zeroed);
-}
-// h[0..n) = the counters, once the stream has run dry.
-static void read_counters(svdw_ctx* c, const unsigned long long* cnt, unsigned long long* h, size_t n) {
-    hipck(hipMemcpyAsync(h, cnt, n * sizeof *h, hipMemcpyDeviceToHost, c->st), "D2H");
-    hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
-}
-// One launch on the context's stream under its profile label.
-template <class Launch>
-static void profiled(svdw_ctx* c, const char* label, double bytes, Launch&& launch) {
-    ProfScope ps(c, c->st, label, bytes, 0);
-    hipck(launch(), label);
 }
 // ---- lookup argument: multiplicities, permuted columns, their check (lookup.hpp)
 namespace {
