@@ -1646,7 +1646,7 @@ static void gamma_prep(svdw_ctx* c, uint32_t d, const Fr& gamma, hipStream_t s, 
     ensure_buf(c, c->gtab, tab_len(len) * sizeof(Fr));
     GammaTab g;
     memset(&g, 0, sizeof g);
-    const Fr one = fr_to_mont(fr_from_u64(1)), gm = fr_to_mont(gamma);
+    const Fr one = fr_one_mont(), gm = fr_to_mont(gamma);
     g.t[0] = one;
     for (int i = 1; i < 16; ++i) g.t[i] = mont_mul(g.t[i - 1], gm);
     const Fr g16 = mont_mul(g.t[15], gm);

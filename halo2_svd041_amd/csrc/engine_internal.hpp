@@ -19,6 +19,7 @@
 
 #include "../../include/svdw.h"
 #include "kernels.hpp"
+#include "pow_table.hpp"
 
 using namespace svdw;                                      // (the files are the engine's own)
 
@@ -97,10 +98,12 @@ struct CircuitState {
 };
 // What the prover calls (prover.cpp) keep on a context between calls.
 struct ProverState {
-    std::vector<Fr> omega;                  // host: the two-level omega tables of the domain 2^omega_k
-    uint32_t omega_k = 0;
-    DBuf ntt_tab, ntt_tmp;                  // transforms (ntt.hpp): the stage and omega tables of ntt_k on the
-    uint32_t ntt_k = 0;                     // device; the buffer between passes
+    struct DomainSlot {                     // the domain's omega_k table (pow_table.hpp) on the host and on the device
+        std::vector<Fr> cells;
+        DBuf buf;
+        PowTable host{}, dev{};             // the views of cells and of buf
+    } domain[29];                           // by k = 1..28: filled on first use (domain_table, prover.cpp), then kept
+    DBuf ntt_tw, ntt_tmp;                   // transforms (ntt.hpp): the 1024 stage twiddles; the buffer between passes
     DBuf commit_ws;                         // commitments (commit.hpp): the window sums and one batch of tasks
     DBuf cycles_ws;                         // sigma's cycles (permutation_cycles.hpp): the sort's arrays and tables
     // quotient (quotient.hpp): the extended columns of l_0, l_last, l_active (R form) of the key below, and the
@@ -108,7 +111,11 @@ struct ProverState {
     DBuf basis, basis_tmp;
     uint32_t basis_k = 0, basis_ek = 0, basis_unusable = 0;
     Fr basis_shift{};
-    std::vector<DBuf*> dbufs() { return {&ntt_tab, &ntt_tmp, &basis, &basis_tmp, &commit_ws, &cycles_ws}; }
+    std::vector<DBuf*> dbufs() {
+        std::vector<DBuf*> v = {&ntt_tw, &ntt_tmp, &basis, &basis_tmp, &commit_ws, &cycles_ws};
+        for (DomainSlot& s : domain) v.push_back(&s.buf);
+        return v;
+    }
 };
 
 // -------------------------------------------------------------- context

@@ -199,13 +199,14 @@ SVDW_HD Fr fr_mul_small_signed(const Fr& a, const Fr& bs) {
 }
 SVDW_HD Fr fr_to_mont(const Fr& a) { return mont_mul(a, fr_r2()); }
 SVDW_HD Fr fr_from_mont(const Fr& a) { return mont_mul(a, fr_from_u64(1)); }
+SVDW_HD Fr fr_one_mont() { return mont_mul(fr_from_u64(1), fr_r2()); }   // 1 in Montgomery form: R mod p
 // Canonical product.
 SVDW_HD Fr fr_mul(const Fr& a, const Fr& b) { return mont_mul(mont_mul(a, b), fr_r2()); }
 
 // a^e for canonical a (square and multiply over the low `nbits` bits of e).
 SVDW_HD Fr fr_pow_u64(const Fr& a, uint64_t e, int nbits = 64) {
     Fr am = fr_to_mont(a);
-    Fr r = fr_to_mont(fr_from_u64(1));
+    Fr r = fr_one_mont();
     for (int i = nbits - 1; i >= 0; --i) {
         r = mont_mul(r, r);
         if ((e >> i) & 1) r = mont_mul(r, am);
@@ -217,7 +218,7 @@ SVDW_HD Fr fr_inv(const Fr& a) {
     Fr e = fr_p();
     e.w[0] -= 2;   // p - 2 (no borrow: low word is 0xf0000001)
     Fr am = fr_to_mont(a);
-    Fr r = fr_to_mont(fr_from_u64(1));
+    Fr r = fr_one_mont();
     for (int wi = 7; wi >= 0; --wi) {
         // select chain instead of e.w[wi]: a runtime index would spill e to scratch
         uint32_t word = e.w[0];

@@ -41,10 +41,6 @@ __device__ __forceinline__ void ntt_put(uint32_t (*sh)[kNttTile], uint32_t pos, 
 #pragma unroll
     for (int w = 0; w < 8; ++w) sh[w][s] = v.w[w];
 }
-// base^i R from a two-level table: lo[j] = base^j R, hi[j] = base^(j 2^h) R.
-__device__ __forceinline__ Fr ntt_power(const Fr* __restrict__ lo, const Fr* __restrict__ hi, uint32_t h, uint64_t i) {
-    return mont_mul(ld_fr(hi + (i >> h)), ld_fr(lo + (i & ((1ull << h) - 1))));
-}
 
 // ------------------------------------------------------------------- a pass
 __global__ __launch_bounds__(kNttThreads) void k_ntt_pass(const NttPass a) {
@@ -64,7 +60,7 @@ __global__ __launch_bounds__(kNttThreads) void k_ntt_pass(const NttPass a) {
         Fr v = fr_zero();
         if (idx < rows_in) {
             v = ld_fr(in + idx);
-            if (a.pre) v = mont_mul(v, ntt_power(a.flo, a.fhi, a.fh, idx));
+            if (a.pre) v = mont_mul(v, pow_at(a.f, idx));
         }
         ntt_put(sh, e, v);
     }
@@ -101,10 +97,10 @@ __global__ __launch_bounds__(kNttThreads) void k_ntt_pass(const NttPass a) {
         if (!a.last) {
             uint64_t ex = (p * i) << a.ls;                 // < N
             if (a.inverse) ex = (N - ex) & (N - 1);
-            f = ntt_power(a.wlo, a.whi, a.h, ex);
+            f = pow_at(a.w, ex);
             mul = true;
         } else if (a.post == 2) {
-            f = ntt_power(a.flo, a.fhi, a.fh, o);
+            f = pow_at(a.f, o);
             mul = true;
         }
         if (mul) v = mont_mul(v, f);
@@ -116,8 +112,8 @@ hipError_t launch_ntt_pass(const NttPass& a, hipStream_t st) {
     if (!a.ncols) return hipSuccess;
     const uint32_t lt = a.k < kNttLogTile ? a.k : kNttLogTile;
     if ((!a.cols && !a.src) || !a.dst || !a.tw || a.k < 1 || a.k > 28 || a.kin < 1 || a.kin > a.k || a.b < 1 ||
-        a.b > lt || a.ls + a.b > a.k || a.ncols > 65535 || (!a.last && (!a.wlo || !a.whi)) ||
-        ((a.pre || a.post == 2) && (!a.flo || !a.fhi)) || a.post > 2 || (a.last && a.ls + a.b != a.k))
+        a.b > lt || a.ls + a.b > a.k || a.ncols > 65535 || (!a.last && pow_table_bad(a.w, a.k)) ||
+        ((a.pre || a.post == 2) && pow_table_bad(a.f, a.kin)) || a.post > 2 || (a.last && a.ls + a.b != a.k))
         return hipErrorInvalidValue;
     const dim3 g((unsigned)(1u << (a.k - lt)), a.ncols), b(kNttThreads);
     hipLaunchKernelGGL(k_ntt_pass, g, b, 0, st, a);
@@ -211,7 +207,7 @@ hipError_t launch_ntt_eval(const Fr* const* cols, const Fr* src, uint64_t n, uin
         return hipErrorInvalidValue;
     const dim3 g(ntt_eval_blocks(n), npoints, ncols), b(kNttThreads);
     hipLaunchKernelGGL(k_ntt_eval, g, b, 0, st, cols, src, n, ntt_eval_run(n), ntt_bits(n), pts,
-                       fr_to_mont(fr_from_u64(1)), part);
+                       fr_one_mont(), part);
     return hipGetLastError();
 }
 hipError_t launch_ntt_eval_sum(const Fr* part, uint32_t nblocks, uint32_t ncols, uint32_t npoints, uint64_t out_stride,

@@ -31,13 +31,12 @@
 //
 //   tw    omega_1024^(+-j) R, j < 512: the stage twiddle omega_(2 hh)^u is entry
 //         u (512 / hh), one table for every k and radix, one per direction
-//   wlo, whi   the permutation argument's two-level omega_k tables; the factor
-//         between passes is omega_N^e, e = s p i < N (inverse: N - e), one
-//         mont_mul to form and one to apply
-//   flo, fhi   per call, shift^i R two-level like them, the inverse's 2^-k folded
-//         into fhi: applied on the first pass's load (forward) or the last
-//         pass's store (inverse); without a shift the inverse multiplies by the
-//         constant 2^-k R and the forward by nothing. No pass of their own.
+//   w     the domain's omega_k table (pow_table.hpp): the factor between passes is
+//         omega_N^e, e = s p i < N (inverse: N - e), one mont_mul to form, one to apply
+//   f     per call, the table of shift^i R, the inverse's 2^-k its top factor: on
+//         the first pass's load (forward) or the last pass's store (inverse);
+//         without a shift the inverse multiplies by the constant 2^-k R and the
+//         forward by nothing. No pass of their own.
 //
 // LDS layout: word-planar, sh[w][slot], the eight words of a cell in eight
 // planes of 1024 dwords (32 KiB). Lanes at consecutive positions then read
@@ -55,7 +54,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "fr.hpp"
+#include "pow_table.hpp"                                    // Fr, PowTable
 
 namespace svdw {
 
@@ -72,15 +71,16 @@ inline uint32_t ntt_pass_bits(uint32_t k, uint32_t i) {
 
 // One pass. cols: the ncols column pointers of the first pass (device table),
 // else null and src the ncols x 2^k cells of the pass before. post: 0 nothing,
-// 1 the constant fc, 2 the tables flo / fhi (split fh), on the stored cell of
-// the last pass; pre: the tables on the loaded cell (first pass).
+// 1 the constant fc, 2 the table f, on the stored cell of the last pass; pre: f
+// on the loaded cell (first pass).
 struct NttPass {
     const Fr* const* cols;
     const Fr* src;
     Fr* dst;
-    const Fr *tw, *wlo, *whi, *flo, *fhi;
+    const Fr* tw;
+    PowTable w, f;
     Fr fc;
-    uint32_t k, kin, b, ls, h, fh, ncols;
+    uint32_t k, kin, b, ls, ncols;
     uint32_t inverse, last, pre, post;
 };
 hipError_t launch_ntt_pass(const NttPass& a, hipStream_t st);

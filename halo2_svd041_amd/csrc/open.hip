@@ -8,9 +8,8 @@
 
 namespace svdw {
 
-__device__ __forceinline__ Fr open_pow(const OpenPow& p, uint64_t e) {
-    e &= (1ull << p.bits) - 1;                              // beyond the table only where the power meets a zero
-    return mont_mul(ld_fr(p.lo + (e & ((1ull << p.h) - 1))), ld_fr(p.hi + (e >> p.h)));
+__device__ __forceinline__ Fr open_pow(const PowTable& p, uint64_t e) {
+    return pow_at(p, e & ((1ull << p.bits) - 1));           // beyond the table only where the power meets a zero
 }
 
 // --------------------------------------------------------------------- fold
@@ -30,7 +29,7 @@ __global__ __launch_bounds__(kOpenFoldThreads) void k_open_fold(const Fr* const*
 }
 
 // -------------------------------------------------------------------- tiles
-__global__ __launch_bounds__(kOpenThreads) void k_open_tiles(const Fr* __restrict__ a, uint64_t n, const OpenPow pw,
+__global__ __launch_bounds__(kOpenThreads) void k_open_tiles(const Fr* __restrict__ a, uint64_t n, const PowTable pw,
                                                              uint64_t nt, Fr* __restrict__ tot) {
     const unsigned lane = threadIdx.x & 63u;
     const uint64_t t = (uint64_t)blockIdx.x * kOpenWaves + (threadIdx.x >> 6);
@@ -54,7 +53,7 @@ __global__ __launch_bounds__(kOpenThreads) void k_open_tiles(const Fr* __restric
 // first one, and m = s^len R. Returns what enters the thread from above, at its
 // run's end: sum_{j > i} v_j s^(len (j - i - 1)) + s^(len (kOpenThreads - 1 - i)) seed.
 // One call per kernel (wt).
-__device__ __forceinline__ Fr open_block_scan(Fr v, Fr m, const Fr& seed, const OpenPow& pw, uint32_t len) {
+__device__ __forceinline__ Fr open_block_scan(Fr v, Fr m, const Fr& seed, const PowTable& pw, uint32_t len) {
     __shared__ Fr wt[kOpenWaves];
     const unsigned lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
 #pragma unroll 1
@@ -78,7 +77,7 @@ __device__ __forceinline__ Fr open_block_scan(Fr v, Fr m, const Fr& seed, const 
 // last runs may be short or empty: totals past nt are zero): a Horner in S down
 // the run, the block scan over the runs, then down the run again handing each
 // tile what enters it from above.
-__global__ __launch_bounds__(kOpenThreads) void k_open_carry(Fr* __restrict__ tot, uint64_t nt, const OpenPow pw) {
+__global__ __launch_bounds__(kOpenThreads) void k_open_carry(Fr* __restrict__ tot, uint64_t nt, const PowTable pw) {
     const uint64_t rounds = (nt + kOpenCarryCap - 1) / kOpenCarryCap;
     const uint64_t lo = threadIdx.x * rounds < nt ? threadIdx.x * rounds : nt, hi = lo + rounds < nt ? lo + rounds : nt;
     const Fr S = open_pow(pw, kOpenTile);
@@ -97,7 +96,7 @@ __global__ __launch_bounds__(kOpenThreads) void k_open_carry(Fr* __restrict__ to
 
 // -------------------------------------------------------------------- write
 template <bool ACC>
-__global__ __launch_bounds__(kOpenThreads) void k_open_write(const Fr* a, uint64_t n, const OpenPow pw,
+__global__ __launch_bounds__(kOpenThreads) void k_open_write(const Fr* a, uint64_t n, const PowTable pw,
                                                              const Fr* __restrict__ carry, const Fr vR, Fr* out,
                                                              Fr* __restrict__ rem) {
     static_assert(kOpenItems == 4, "four named coefficients per thread");
@@ -120,8 +119,8 @@ __global__ __launch_bounds__(kOpenThreads) void k_open_write(const Fr* a, uint64
 }
 
 // ----------------------------------------------------------------- launches
-static bool open_bad(uint64_t n, const OpenPow& pw) {
-    return !n || n > (1ull << 28) || !pw.lo || !pw.hi || pw.bits < kOpenLogTile || pw.bits > 28 || pw.h > pw.bits ||
+static bool open_bad(uint64_t n, const PowTable& pw) {
+    return !n || n > (1ull << 28) || pw.bits < kOpenLogTile || pw.bits > 28 || pow_table_bad(pw, pw.bits) ||
            (1ull << pw.bits) < n;
 }
 hipError_t launch_open_fold(const Fr* const* cols, const Fr* sc, uint32_t ncols, const Fr* acc, const Fr& cacc,
@@ -133,19 +132,20 @@ hipError_t launch_open_fold(const Fr* const* cols, const Fr* sc, uint32_t ncols,
                        dim3(kOpenFoldThreads), 0, st, cols, sc, ncols, acc, cacc, n, out);
     return hipGetLastError();
 }
-hipError_t launch_open_tiles(const Fr* a, uint64_t n, const OpenPow& pw, Fr* tot, hipStream_t st) {
+hipError_t launch_open_tiles(const Fr* a, uint64_t n, const PowTable& pw, Fr* tot, hipStream_t st) {
     if (open_bad(n, pw) || !a || !tot) return hipErrorInvalidValue;
     const uint64_t nt = open_tiles(n);
     hipLaunchKernelGGL(k_open_tiles, dim3((unsigned)((nt + kOpenWaves - 1) / kOpenWaves)), dim3(kOpenThreads), 0, st,
                        a, n, pw, nt, tot);
     return hipGetLastError();
 }
-hipError_t launch_open_carry(Fr* tot, uint64_t nt, const OpenPow& pw, hipStream_t st) {
-    if (!nt || !tot || !pw.lo || !pw.hi || nt > open_tiles(1ull << pw.bits)) return hipErrorInvalidValue;
+hipError_t launch_open_carry(Fr* tot, uint64_t nt, const PowTable& pw, hipStream_t st) {
+    if (!nt || !tot || pw.bits > 28 || pow_table_bad(pw, pw.bits) || nt > open_tiles(1ull << pw.bits))
+        return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_open_carry, dim3(1), dim3(kOpenThreads), 0, st, tot, nt, pw);
     return hipGetLastError();
 }
-hipError_t launch_open_write(const Fr* a, uint64_t n, const OpenPow& pw, const Fr* carry, const Fr* v, Fr* out,
+hipError_t launch_open_write(const Fr* a, uint64_t n, const PowTable& pw, const Fr* carry, const Fr* v, Fr* out,
                              Fr* rem, hipStream_t st) {
     if (open_bad(n, pw) || !a || !out || (!carry && open_tiles(n) > 1)) return hipErrorInvalidValue;
     const dim3 g((unsigned)open_tiles(n)), b(kOpenThreads);

@@ -34,10 +34,9 @@
 //                the remainder. out may be a: a thread reads its own cells
 //                before it writes them, and no other thread's.
 //
-// Powers of s come from a per-point two-level table (OpenPow), s^e R = lo[e mod
-// 2^h] * hi[e >> h], like the transforms' shift table: one mont_mul to form, one
-// to apply, no multiplication chains per thread. s = 0 and s = 1 are ordinary
-// points of it (0^0 = 1).
+// Powers of s come from a per-point table (PowTable, pow_table.hpp) over
+// 2^open_pow_bits(k) exponents: one mont_mul to form, one to apply, no chains of
+// multiplications per thread. s = 0 and s = 1 are ordinary points of it (0^0 = 1).
 //
 // Powers of R = 2^256 as ntt.hpp explains: a cell is x phi, every constant is
 // held as c R, mont_mul(x phi, c R) = c x phi, sums keep phi: nothing is
@@ -49,7 +48,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "fr.hpp"
+#include "pow_table.hpp"                                    // Fr, PowTable
 
 namespace svdw {
 
@@ -66,24 +65,18 @@ inline uint64_t open_tiles(uint64_t n) { return (n + kOpenTile - 1) / kOpenTile;
 // The exponents a point's table covers for 2^k coefficients: 2^open_pow_bits(k).
 inline uint32_t open_pow_bits(uint32_t k) { return k < kOpenLogTile ? kOpenLogTile : k; }
 
-// s^e R for e < 2^bits: lo[e & (2^h - 1)] * hi[e >> h] (domain_power_tables).
-struct OpenPow {
-    const Fr *lo, *hi;
-    uint32_t h, bits;
-};
-
 // out[r] = sum_{j < ncols} sc[j] cols[j][r] + (acc ? cacc acc[r] : 0), r < n.
 // cols, sc: device tables; sc[j] and cacc as c R.
 hipError_t launch_open_fold(const Fr* const* cols, const Fr* sc, uint32_t ncols, const Fr* acc, const Fr& cacc,
                             uint64_t n, Fr* out, hipStream_t st);
 // tot[t] = the value of tile t of a[0..n) at its first coefficient, t < open_tiles(n).
-hipError_t launch_open_tiles(const Fr* a, uint64_t n, const OpenPow& pw, Fr* tot, hipStream_t st);
+hipError_t launch_open_tiles(const Fr* a, uint64_t n, const PowTable& pw, Fr* tot, hipStream_t st);
 // In place: tot[t] becomes the carry of tile t, what the tiles above it are worth
 // at its end.
-hipError_t launch_open_carry(Fr* tot, uint64_t nt, const OpenPow& pw, hipStream_t st);
+hipError_t launch_open_carry(Fr* tot, uint64_t nt, const PowTable& pw, hipStream_t st);
 // out[0..n) = the quotient of a by (X - s), or out v + it with v (as v R) given;
 // carry: launch_open_carry's, null for a single tile. rem, if given, gets a(s).
-hipError_t launch_open_write(const Fr* a, uint64_t n, const OpenPow& pw, const Fr* carry, const Fr* v, Fr* out,
+hipError_t launch_open_write(const Fr* a, uint64_t n, const PowTable& pw, const Fr* carry, const Fr* v, Fr* out,
                              Fr* rem, hipStream_t st);
 
 }  // namespace svdw

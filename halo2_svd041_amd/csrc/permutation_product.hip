@@ -22,9 +22,6 @@
 
 namespace svdw {
 
-__device__ __forceinline__ Fr pp_omega(const Fr* __restrict__ wlo, const Fr* __restrict__ whi, uint32_t h, uint64_t r) {
-    return mont_mul(ld_fr(whi + (r >> h)), ld_fr(wlo + (r & ((1ull << h) - 1))));
-}
 // The leaf. The cursor is w = omega^r R, from the table.
 struct PpLeaf {
     PpArgs a;
@@ -35,7 +32,7 @@ struct PpLeaf {
     __device__ __forceinline__ uint64_t rows() const { return a.rows; }
     __device__ __forceinline__ uint64_t usable() const { return a.usable; }
     __device__ __forceinline__ Fr one() const { return a.one; }
-    __device__ __forceinline__ Cursor cursor(uint64_t r) const { return {pp_omega(a.wlo, a.whi, a.h, r)}; }
+    __device__ __forceinline__ Cursor cursor(uint64_t r) const { return {pow_at(a.w, r)}; }
     // The factors of row r < usable of set s, the columns [j0, j1). j counts over
     // all columns: the identity term of column j is delta^j omega^r.
     __device__ __forceinline__ void factors(uint32_t s, uint64_t r, const Cursor& c, Fr& n, Fr& d) const {
@@ -118,10 +115,10 @@ __global__ __launch_bounds__(kGpThreads) void k_pp_fold(Fr* __restrict__ tp, con
 
 // ------------------------------------------------------------------- values
 __global__ __launch_bounds__(kGpThreads) void k_pp_values(const uint64_t* __restrict__ mapping,
-                                                          const Fr* __restrict__ dl, const Fr* __restrict__ wlo,
-                                                          const Fr* __restrict__ whi, uint32_t h, uint32_t first_col,
-                                                          uint32_t total_cols, uint64_t rows, uint64_t cells,
-                                                          Fr* __restrict__ out, unsigned long long* cnt) {
+                                                          const Fr* __restrict__ dl, const PowTable w,
+                                                          uint32_t first_col, uint32_t total_cols, uint64_t rows,
+                                                          uint64_t cells, Fr* __restrict__ out,
+                                                          unsigned long long* cnt) {
     __shared__ uint32_t bad;
     if (threadIdx.x == 0) bad = 0;
     __syncthreads();
@@ -139,7 +136,7 @@ __global__ __launch_bounds__(kGpThreads) void k_pp_values(const uint64_t* __rest
             row = i % rows;
         }
         Fr v = fr_zero();
-        if (col < total_cols && row < rows) v = mont_mul(pp_omega(wlo, whi, h, row), ld_fr(dl + col));
+        if (col < total_cols && row < rows) v = mont_mul(pow_at(w, row), ld_fr(dl + col));
         else ++nb;
         st_fr(out + i, v);
     }
@@ -150,9 +147,9 @@ __global__ __launch_bounds__(kGpThreads) void k_pp_values(const uint64_t* __rest
 
 // ----------------------------------------------------------------- launches
 static bool pp_bad(const PpArgs& a, int form) {
-    return !a.cols || !a.sig || !a.bd || !a.wlo || !a.whi || !a.ncols || !a.chunk || a.ncols > 65535 ||
+    return !a.cols || !a.sig || !a.bd || !a.ncols || !a.chunk || a.ncols > 65535 ||
            a.nsets != pp_sets(a.ncols, a.chunk) || a.usable >= a.rows || a.rows > (1ull << 31) ||
-           (a.rows & (a.rows - 1)) || a.h > 31 || (1ull << a.h) > a.rows ||
+           (a.rows & (a.rows - 1)) || pow_table_bad(a.w, (uint32_t)__builtin_ctzll(a.rows)) ||
            (form != kFormCanonical && form != kFormMontgomery);
 }
 
@@ -194,16 +191,16 @@ hipError_t launch_pp_check(const PpArgs& a, int form, const Fr* z, const Fr& wst
     hipLaunchKernelGGL(k_gp_check<PpCheckLeaf>, g, b, 0, st, leaf, z, cnt);
     return hipGetLastError();
 }
-hipError_t launch_pp_values(const uint64_t* mapping, const Fr* dl, const Fr* wlo, const Fr* whi, uint32_t h,
-                            uint32_t first_col, uint32_t ncols, uint32_t total_cols, uint64_t rows, Fr* out,
-                            unsigned long long* cnt, hipStream_t st) {
+hipError_t launch_pp_values(const uint64_t* mapping, const Fr* dl, const PowTable& w, uint32_t first_col,
+                            uint32_t ncols, uint32_t total_cols, uint64_t rows, Fr* out, unsigned long long* cnt,
+                            hipStream_t st) {
     if (!ncols) return hipSuccess;
-    if (!dl || !wlo || !whi || !out || !cnt || !rows || (rows & (rows - 1)) || rows > (1ull << 31) ||
-        (1ull << h) > rows || ncols > 65535 || total_cols > 65535)
+    if (!dl || !out || !cnt || !rows || (rows & (rows - 1)) || rows > (1ull << 31) ||
+        pow_table_bad(w, (uint32_t)__builtin_ctzll(rows)) || ncols > 65535 || total_cols > 65535)
         return hipErrorInvalidValue;
     const uint64_t cells = (uint64_t)ncols * rows, nb = (cells + kGpThreads - 1) / kGpThreads;
     hipLaunchKernelGGL(k_pp_values, dim3((unsigned)(nb < 65536 ? nb : 65536)), dim3(kGpThreads), 0, st, mapping, dl,
-                       wlo, whi, h, first_col, total_cols, rows, cells, out, cnt);
+                       w, first_col, total_cols, rows, cells, out, cnt);
     return hipGetLastError();
 }
 

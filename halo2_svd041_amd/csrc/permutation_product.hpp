@@ -35,30 +35,27 @@
 // the same power, which the set's inverse cancels. The starts are kept as
 // start R and meet the inverse in one mont_mul.
 //
-// omega^r comes from a two-level table made on the host per k, omega^(hi 2^h) R
-// and omega^lo R with h = ceil(k / 2), one mont_mul per row, shared by the set's
-// columns; k_pp_check takes the table for a thread's first row only and steps by
-// omega^(its grid stride) from there.
+// omega^r comes from the domain's omega_k table (PowTable, pow_table.hpp), one
+// mont_mul per row, shared by the set's columns; k_pp_check takes the table for
+// a thread's first row only and steps by omega^(its grid stride) from there.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "fr.hpp"
 #include "grand_product.hpp"
+#include "pow_table.hpp"                                    // Fr, PowTable
 
 namespace svdw {
 
 // What the row kernels read, all in device memory. cols / sig: ncols column
-// base pointers each; bd[j] = beta delta^j phi; wlo[i] = omega^i R for
-// i < 2^h, whi[i] = omega^(i 2^h) R for i < 2^(k - h). bR = beta R,
-// g = gamma phi, one = R.
+// base pointers each; bd[j] = beta delta^j phi; w the omega_k table of the
+// rows' k. bR = beta R, g = gamma phi, one = R.
 struct PpArgs {
     const Fr* const* cols;
     const Fr* const* sig;
     const Fr* bd;
-    const Fr* wlo;
-    const Fr* whi;
-    uint32_t h, ncols, chunk, nsets;
+    PowTable w;
+    uint32_t ncols, chunk, nsets;
     uint64_t rows, usable;
     Fr bR, g, one;
 };
@@ -89,10 +86,10 @@ hipError_t launch_pp_check(const PpArgs& a, int form, const Fr* z, const Fr& wst
                            hipStream_t st);
 // out (ncols x rows cells in `form`): delta^col omega^row of mapping[i] =
 // col << 32 | row, or of (first_col + i / rows, i % rows) without a mapping;
-// dl[c] = delta^c phi for c < total_cols. An entry with col >= total_cols or
-// row >= rows is written as zero; cnt[0] += those.
-hipError_t launch_pp_values(const uint64_t* mapping, const Fr* dl, const Fr* wlo, const Fr* whi, uint32_t h,
-                            uint32_t first_col, uint32_t ncols, uint32_t total_cols, uint64_t rows, Fr* out,
-                            unsigned long long* cnt, hipStream_t st);
+// dl[c] = delta^c phi for c < total_cols, w the rows' omega table. An entry with
+// col >= total_cols or row >= rows is written as zero; cnt[0] += those.
+hipError_t launch_pp_values(const uint64_t* mapping, const Fr* dl, const PowTable& w, uint32_t first_col,
+                            uint32_t ncols, uint32_t total_cols, uint64_t rows, Fr* out, unsigned long long* cnt,
+                            hipStream_t st);
 
 }  // namespace svdw

@@ -209,7 +209,7 @@ static bool lp_args(svdw_ctx* c, const char* fn, uint32_t phase, uint32_t unusab
     a->ch.gx = mont ? fr_to_mont(g) : g;
     a->ch.g2 = fr_to_mont(fr_to_mont(g));
     a->ch.t2 = fr_to_mont(fr_to_mont(fr_from_u64(1ull << 32)));
-    a->ch.one = fr_to_mont(fr_from_u64(1));
+    a->ch.one = fr_one_mont();
     return any;
 }
 int svdw_lookup_product(svdw_ctx* c, uint32_t phase, uint32_t unusable_rows, int form, const void* columns,
@@ -280,7 +280,7 @@ static const DomainConsts& domain_consts() {
         e.w[0] -= 1;
         for (int i = 0; i < 8; ++i) e.w[i] = (e.w[i] >> 28) | (i < 7 ? e.w[i + 1] << 4 : 0u);
         const Fr g = fr_to_mont(fr_from_u64(7));
-        Fr w = fr_to_mont(fr_from_u64(1)), d = g;
+        Fr w = fr_one_mont(), d = g;
         for (int i = 255; i >= 0; --i) {
             w = mont_mul(w, w);
             if ((e.w[i >> 5] >> (i & 31)) & 1) w = mont_mul(w, g);
@@ -296,27 +296,19 @@ static Fr domain_omega_mont(uint32_t k) {
     for (uint32_t i = k; i < 28; ++i) w = mont_mul(w, w);
     return w;
 }
-static uint32_t domain_split(uint32_t k) { return (k + 1) / 2; }
-// The two-level power table of a base b (as b R) over 2^k exponents, h = domain_split(k):
-// b^i R for i < 2^h, then top b^(i 2^h) for i < 2^(k - h) (top = R: plain powers).
-static void domain_power_tables(const Fr& bR, const Fr& top, uint32_t k, Fr* out) {
-    const uint32_t h = domain_split(k);
-    const size_t nlo = (size_t)1 << h, nhi = (size_t)1 << (k - h);
-    out[0] = fr_to_mont(fr_from_u64(1));
-    for (size_t i = 1; i < nlo; ++i) out[i] = mont_mul(out[i - 1], bR);
-    const Fr bh = mont_mul(out[nlo - 1], bR);
-    out[nlo] = top;
-    for (size_t i = 1; i < nhi; ++i) out[nlo + i] = mont_mul(out[nlo + i - 1], bh);
-}
-// The context's omega tables for k (host): domain_power_tables of omega_k.
-static const std::vector<Fr>& domain_tables(svdw_ctx* c, uint32_t k) {
-    ProverState& ps = c->prover;
-    if (ps.omega_k == k && !ps.omega.empty()) return ps.omega;
-    std::vector<Fr> t(((size_t)1 << domain_split(k)) + ((size_t)1 << (k - domain_split(k))));
-    domain_power_tables(domain_omega_mont(k), fr_to_mont(fr_from_u64(1)), k, t.data());
-    ps.omega.swap(t);
-    ps.omega_k = k;
-    return ps.omega;
+// The context's slot of omega_k's table (pow_table.hpp), host and device views: filled and uploaded on the first
+// use of k, never again. The upload is ordered on the stream before the caller's kernels; the slot keeps its source.
+static const ProverState::DomainSlot& domain_table(svdw_ctx* c, uint32_t k) {
+    ProverState::DomainSlot& s = c->prover.domain[k];
+    if (!s.buf.p) {
+        s.cells.resize(pow_table_cells(k));
+        pow_table_fill(domain_omega_mont(k), fr_one_mont(), k, s.cells.data());
+        ensure_buf(c, s.buf, s.cells.size() * sizeof(Fr));
+        hipck(hipMemcpyAsync(s.buf.p, s.cells.data(), s.cells.size() * sizeof(Fr), hipMemcpyHostToDevice, c->st), "H2D");
+        s.host = pow_table_view(s.cells.data(), k);
+        s.dev = pow_table_view((const Fr*)s.buf.p, k);
+    }
+    return s;
 }
 // x delta^j phi for j < n (phi = 1 canonical, R Montgomery), x canonical.
 static void pp_delta_powers(const Fr& x, int form, uint32_t n, Fr* out) {
@@ -347,18 +339,13 @@ int svdw_permutation_values(svdw_ctx* c, uint32_t k, int form, const uint64_t* m
         if (!ncols) return;
         REQUIRE(out, "null output");
         sync(c);
-        const std::vector<Fr>& w = domain_tables(c, k);
-        const uint32_t h = domain_split(k);
-        const size_t nd = std::max(total_cols, 1u);
-        // the staged cells: delta^j phi for j < total_cols (one cell at least), then the omega tables
-        const Staged d = stage(c, nullptr, 0, nullptr, 0, nd + w.size(), 0, [&](Fr* t) {
-            pp_delta_powers(fr_from_u64(1), form, total_cols, t);
-            memcpy(t + nd, w.data(), w.size() * sizeof(Fr));
-        });
-        const Fr* dl = d.cells;
+        const PowTable w = domain_table(c, k).dev;
+        // the staged cells: delta^j phi for j < total_cols (one cell at least)
+        const Staged d = stage(c, nullptr, 0, nullptr, 0, std::max(total_cols, 1u), 0,
+                               [&](Fr* t) { pp_delta_powers(fr_from_u64(1), form, total_cols, t); });
         profiled(c, "k_pp_values", (mapping ? 40.0 : 32.0) * ncols * (double)(1ull << k), [&] {
-            return launch_pp_values(mapping, dl, dl + nd, dl + nd + ((size_t)1 << h), h, first_col, ncols, total_cols,
-                                    1ull << k, (Fr*)out, d.cnt, c->st);
+            return launch_pp_values(mapping, d.cells, w, first_col, ncols, total_cols, 1ull << k, (Fr*)out, d.cnt,
+                                    c->st);
         });
         unsigned long long bad = 0;
         read_counters(c, d.cnt, &bad, 1);
@@ -366,7 +353,7 @@ int svdw_permutation_values(svdw_ctx* c, uint32_t k, int form, const uint64_t* m
     });
 }
 // The argument checks of both entries, in the order include/svdw.h gives, and
-// the device tables; false: no columns, nothing to do.
+// what the kernels read on the device; false: no columns, nothing to do.
 static bool pp_args(svdw_ctx* c, const char* fn, uint32_t k, uint32_t unusable_rows, int form,
                     const void* const* columns, const void* const* sigma, uint32_t ncols, uint32_t chunk_len,
                     const uint64_t beta[4], const uint64_t gamma[4], const void* z, bool scratch, PpDev* d) {
@@ -394,23 +381,18 @@ static bool pp_args(svdw_ctx* c, const char* fn, uint32_t k, uint32_t unusable_r
     }
     sync(c);
     const bool mont = form == SVDW_FORM_MONTGOMERY;
-    const std::vector<Fr>& w = domain_tables(c, k);
-    a.h = domain_split(k);
+    a.w = domain_table(c, k).dev;
     a.bR = fr_to_mont(b);
     a.g = mont ? fr_to_mont(g) : g;
-    a.one = fr_to_mont(fr_from_u64(1));
-    // the staged cells: beta delta^j phi for j < ncols, then the omega tables
+    a.one = fr_one_mont();
+    // the staged cells: beta delta^j phi for j < ncols
     const uint64_t cells = scratch ? pp_scratch_cells(a.nsets, rows) : 0;
-    const Staged s = stage(c, columns, ncols, sigma, ncols, ncols + w.size(), cells * sizeof(Fr), [&](Fr* t) {
-        pp_delta_powers(b, form, ncols, t);
-        memcpy(t + ncols, w.data(), w.size() * sizeof(Fr));
-    });
+    const Staged s = stage(c, columns, ncols, sigma, ncols, ncols, cells * sizeof(Fr),
+                           [&](Fr* t) { pp_delta_powers(b, form, ncols, t); });
     d->cnt = s.cnt;
     a.cols = s.ptrs;
     a.sig = a.cols + ncols;
     a.bd = s.cells;
-    a.wlo = a.bd + ncols;
-    a.whi = a.wlo + ((size_t)1 << a.h);
     d->sv = (Fr*)s.free;
     d->xs = d->sv + 2 * (uint64_t)a.nsets;
     d->tp = d->xs + 2 * (uint64_t)kGpThreads * a.nsets;
@@ -632,26 +614,19 @@ static bool ntt_args(svdw_ctx* c, const char* fn, uint32_t k_in, uint32_t k, int
     }
     return true;
 }
-// The device tables of k, made once per k: omega_1024^j R and omega_1024^-j R
-// for j < 512, then the two-level omega_k tables of domain_tables.
-static const Fr* ntt_tables(svdw_ctx* c, uint32_t k) {
-    ProverState& ps = c->prover;
-    const std::vector<Fr>& w = domain_tables(c, k);
-    const size_t cells = 1024 + w.size();
-    const bool grown = ps.ntt_tab.cap < cells * sizeof(Fr);
-    ensure_buf(c, ps.ntt_tab, cells * sizeof(Fr));
-    if (grown || ps.ntt_k != k) {
-        std::vector<Fr> t(cells);
-        const Fr w10 = domain_omega_mont(10);
-        t[0] = t[512] = fr_to_mont(fr_from_u64(1));
-        for (size_t j = 1; j < 512; ++j) t[j] = mont_mul(t[j - 1], w10);
-        for (size_t j = 1; j < 512; ++j) t[512 + j] = fr_neg(t[512 - j]);   // omega^-j = -omega^(512 - j)
-        memcpy(t.data() + 1024, w.data(), w.size() * sizeof(Fr));
-        hipck(hipMemcpyAsync(ps.ntt_tab.p, t.data(), cells * sizeof(Fr), hipMemcpyHostToDevice, c->st), "H2D");
-        hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
-        ps.ntt_k = k;
-    }
-    return (const Fr*)ps.ntt_tab.p;
+// The stage twiddles on the device, the same for every k and made once:
+// omega_1024^j R, then omega_1024^-j R, for j < 512.
+static const Fr* ntt_twiddles(svdw_ctx* c) {
+    DBuf& b = c->prover.ntt_tw;
+    if (b.p) return (const Fr*)b.p;
+    std::vector<Fr> t(1024, fr_one_mont());
+    const Fr w10 = domain_omega_mont(10);
+    for (size_t j = 1; j < 512; ++j) t[j] = mont_mul(t[j - 1], w10);
+    for (size_t j = 1; j < 512; ++j) t[512 + j] = fr_neg(t[512 - j]);   // omega^-j = -omega^(512 - j)
+    ensure_buf(c, b, t.size() * sizeof(Fr));
+    hipck(hipMemcpyAsync(b.p, t.data(), t.size() * sizeof(Fr), hipMemcpyHostToDevice, c->st), "H2D");
+    hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");   // t goes away
+    return (const Fr*)b.p;
 }
 uint32_t svdw_ntt_passes(uint32_t k) { return ntt_passes(k); }
 // The transform of a checked call with columns: in (a.ncols pointers) to out.
@@ -659,15 +634,16 @@ static void ntt_run(svdw_ctx* c, const NttCall& a, const void* const* in, void* 
     sync(c);
     const uint32_t k = a.k, k_in = a.k_in, ncols = a.ncols;
     const int inverse = a.inverse;
-    const uint32_t P = ntt_passes(k), h = domain_split(k), kk = inverse ? k : k_in, fh = domain_split(kk);
+    const uint32_t P = ntt_passes(k), kk = inverse ? k : k_in;
     const uint64_t N = 1ull << k;
-    const Fr* tab = ntt_tables(c, k);
-    const Fr scale = inverse ? fr_to_mont(fr_inv(fr_from_u64(N))) : fr_to_mont(fr_from_u64(1));   // 2^-k R
-    const size_t fcells = a.shifted ? ((size_t)1 << fh) + ((size_t)1 << (kk - fh)) : 0;
+    const Fr* tw = ntt_twiddles(c);
+    const PowTable w = domain_table(c, k).dev;
+    const Fr scale = inverse ? fr_to_mont(fr_inv(fr_from_u64(N))) : fr_one_mont();   // 2^-k R
+    const size_t fcells = a.shifted ? pow_table_cells(kk) : 0;
     if (P > 1) ensure_buf(c, c->prover.ntt_tmp, (size_t)ncols * N * sizeof(Fr));   // the buffer between passes
-    // the staged cells: the two-level table of the shift's powers, its top level times the scale
+    // the staged cells: the table of the shift's powers over the input's rows, the scale its top factor
     const Staged d = stage(c, in, ncols, nullptr, 0, fcells, 0, [&](Fr* t) {
-        if (a.shifted) domain_power_tables(fr_to_mont(a.shift), scale, kk, t);
+        if (a.shifted) pow_table_fill(fr_to_mont(a.shift), scale, kk, t);
     });
     Fr* tmp = (Fr*)c->prover.ntt_tmp.p;
     uint32_t ls = 0;
@@ -677,18 +653,14 @@ static void ntt_run(svdw_ctx* c, const NttCall& a, const void* const* in, void* 
         // the buffers alternate so that the last pass writes out
         p.src = i ? ((P - i) % 2 ? tmp : (const Fr*)out) : nullptr;
         p.dst = (P - 1 - i) % 2 ? tmp : (Fr*)out;
-        p.tw = tab + (inverse ? 512 : 0);
-        p.wlo = tab + 1024;
-        p.whi = p.wlo + ((size_t)1 << h);
-        p.flo = a.shifted ? d.cells : nullptr;
-        p.fhi = a.shifted ? d.cells + ((size_t)1 << fh) : nullptr;
+        p.tw = tw + (inverse ? 512 : 0);
+        p.w = w;
+        if (a.shifted) p.f = pow_table_view(d.cells, kk);
         p.fc = scale;
         p.k = k;
         p.kin = i ? k : k_in;
         p.b = ntt_pass_bits(k, i);
         p.ls = ls;
-        p.h = h;
-        p.fh = fh;
         p.ncols = ncols;
         p.inverse = (uint32_t)inverse;
         p.last = i + 1 == P;
@@ -769,17 +741,14 @@ int svdw_check_ntt(svdw_ctx* c, uint32_t k_in, uint32_t k, int form, int inverse
         if (!any) return;
         sync(c);
         // the points: shift omega^j (forward), omega^j / shift (inverse), as x R
-        const std::vector<Fr>& w = domain_tables(c, k);
-        const uint32_t h = domain_split(k);
+        const PowTable w = domain_table(c, k).host;
         const uint64_t S = 1ull << log_samples, n = 1ull << (inverse ? k : k_in);
         const Fr sR = fr_to_mont(inverse ? fr_inv(a.shift) : a.shift);
         const uint32_t chunk = (uint32_t)std::min<uint64_t>(S, kNttPointChunk);
         const size_t vals = (size_t)ncols * chunk * sizeof(Fr), part = vals * ntt_eval_blocks(n);
         const Staged d = stage(c, in, ncols, nullptr, 0, S, vals + part, [&](Fr* t) {
             for (uint64_t s = 0; s < S; ++s) {
-                const uint64_t j = ntt_sample_row(k, log_samples, seed, s);
-                const Fr wj = mont_mul(w[((size_t)1 << h) + (j >> h)], w[j & (((size_t)1 << h) - 1)]);
-                t[s] = mont_mul(wj, sR);
+                t[s] = mont_mul(pow_at(w, ntt_sample_row(k, log_samples, seed, s)), sR);
             }
         });
         Fr* dv = (Fr*)d.free;
@@ -1005,7 +974,7 @@ static bool q_args(svdw_ctx* c, const char* fn, const svdw_quotient_args* a, con
     {
         Fr t = fr_to_mont(q->shift);                       // shift^N == 1: shift^n is an E-th root of unity
         for (uint32_t i = 0; i < q->ek; ++i) t = mont_mul(t, t);
-        REQUIRE(!fr_eq(t, fr_to_mont(fr_from_u64(1))), f + ": shift^n is an E-th root of unity (a zero divisor)");
+        REQUIRE(!fr_eq(t, fr_one_mont()), f + ": shift^n is an E-th root of unity (a zero divisor)");
     }
     need_device(c, f);
     need_columns(f, std::max({a->n_gate, a->n_perm, a->n_lookup}), " in a family");
@@ -1047,7 +1016,7 @@ static const Fr* q_basis(svdw_ctx* c, const QCall& q, uint32_t unusable_rows) {
     ensure_buf(c, ps.basis_tmp, 6 * q.n * sizeof(Fr));
     Fr *lag = (Fr*)ps.basis_tmp.p, *cf = lag + 3 * q.n;
     profiled(c, "k_quotient_basis", 96.0 * q.n, [&] {
-        return launch_quotient_basis(lag, q.n, q.usable, fr_to_mont(fr_from_u64(1)), c->st);
+        return launch_quotient_basis(lag, q.n, q.usable, fr_one_mont(), c->st);
     });
     const void* in[3] = {lag, lag + q.n, lag + 2 * q.n};
     const void* mid[3] = {cf, cf + q.n, cf + 2 * q.n};
@@ -1075,9 +1044,7 @@ int svdw_quotient(svdw_ctx* c, const svdw_quotient_args* args, void* h_ext, svdw
         const bool mont = args->form == SVDW_FORM_MONTGOMERY;
         const uint32_t ng = args->n_gate, np = args->n_perm, nl = args->n_lookup, E = 1u << q.le;
         const Fr* l = (np | nl) ? q_basis(c, q, args->unusable_rows) : nullptr;
-        const uint32_t h = domain_split(q.ek);
-        const Fr* tab = ntt_tables(c, q.ek);
-        const Fr one = fr_to_mont(fr_from_u64(1));
+        const Fr one = fr_one_mont();
         // the staged cells: beta delta^j phi for j < np, then the E inverses of the divisor as c R
         const Staged d = stage(c, q.ptrs.data(), (uint32_t)q.ptrs.size(), nullptr, 0, (size_t)np + E, 0, [&](Fr* t) {
             pp_delta_powers(q.beta, args->form, np, t);
@@ -1106,8 +1073,7 @@ int svdw_quotient(svdw_ctx* c, const svdw_quotient_args* args, void* h_ext, svdw
         a.ptrs = d.ptrs;
         a.bd = d.cells;
         a.inv = d.cells + np;
-        a.wlo = tab + 1024;
-        a.whi = a.wlo + ((size_t)1 << h);
+        a.w = domain_table(c, q.ek).dev;
         a.l0 = l;
         a.llast = l ? l + q.N : nullptr;
         a.lact = l ? l + 2 * q.N : nullptr;
@@ -1120,7 +1086,6 @@ int svdw_quotient(svdw_ctx* c, const svdw_quotient_args* args, void* h_ext, svdw
         a.one = mont ? one : fr_from_u64(1);
         a.ek = q.ek;
         a.le = q.le;
-        a.h = h;
         a.ng = ng;
         a.np = np;
         a.chunk = args->chunk_len;
@@ -1151,7 +1116,7 @@ int svdw_check_quotient(svdw_ctx* c, const svdw_quotient_args* args, const void*
         sync(c);
         const bool mont = args->form == SVDW_FORM_MONTGOMERY;
         const uint32_t ng = args->n_gate, np = args->n_perm, nl = args->n_lookup, ns = q.nsets;
-        const Fr one = fr_to_mont(fr_from_u64(1));
+        const Fr one = fr_one_mont();
         // the points x omega^r R, r in {0, 1, 2, 3, -1, usable}
         constexpr uint32_t kPts = 6;
         const Fr xR = fr_to_mont(q.x), w = domain_omega_mont(q.k);
@@ -1280,7 +1245,7 @@ static bool om_in(const std::vector<Fr>& set, const Fr& x) {
 }
 // prod over the points s of `of` that are not in `without` of (x - s), as R-form.
 static Fr om_vanish(const std::vector<Fr>& of, const std::vector<Fr>* without, const Fr& xR) {
-    Fr z = fr_to_mont(fr_from_u64(1));
+    Fr z = fr_one_mont();
     for (const Fr& s : of)
         if (!without || !om_in(*without, s)) z = mont_mul(z, fr_sub(xR, s));
     return z;
@@ -1363,7 +1328,7 @@ static bool open_args(svdw_ctx* c, const char* fn, uint32_t k, int form, const v
 // The slots' scalars of the fold per set: y^(m - 1 - pos) R for position pos of a set's m columns.
 static void open_fold_scalars(const OpenCall& q, Fr* sc) {
     for (uint32_t i = 0; i < q.nsets; ++i) {
-        Fr p = fr_to_mont(fr_from_u64(1));
+        Fr p = fr_one_mont();
         for (uint32_t s = q.first[i + 1]; s-- > q.first[i];) {
             sc[s] = p;
             p = mont_mul(p, q.y);
@@ -1373,25 +1338,16 @@ static void open_fold_scalars(const OpenCall& q, Fr* sc) {
 // c_i v^(nsets - 1 - i) R per set, c_i = Z_{T \ S_i}(at) / Z_{T \ S_0}(at) (norm) or Z_{T \ S_i}(at).
 static std::vector<Fr> open_set_weights(const OpenCall& q, const Fr& at, bool norm) {
     std::vector<Fr> w(q.nsets);
-    const Fr z0i = norm ? om_inv(om_vanish(q.T, &q.S[0], at)) : fr_to_mont(fr_from_u64(1));
-    Fr p = fr_to_mont(fr_from_u64(1));
+    const Fr z0i = norm ? om_inv(om_vanish(q.T, &q.S[0], at)) : fr_one_mont();
+    Fr p = fr_one_mont();
     for (uint32_t i = q.nsets; i-- > 0;) {
         w[i] = mont_mul(mont_mul(om_vanish(q.T, &q.S[i], at), z0i), p);
         p = mont_mul(p, q.v);
     }
     return w;
 }
-// The power table of the point sR for the call's k at `out`, and the kernels' view of its device copy at dev.
-static uint32_t open_table_cells(uint32_t k) {
-    const uint32_t b = open_pow_bits(k), h = domain_split(b);
-    return (1u << h) + (1u << (b - h));
-}
-static OpenPow open_table(uint32_t k, const Fr* dev) {
-    const uint32_t b = open_pow_bits(k), h = domain_split(b);
-    return OpenPow{dev, dev + ((size_t)1 << h), h, b};
-}
 // One division of a[0..n) by (X - s) on the stream: out = the quotient, or out v + it.
-static void open_divide(svdw_ctx* c, const Fr* a, uint64_t n, const OpenPow& pw, Fr* tot, const Fr* v, Fr* out,
+static void open_divide(svdw_ctx* c, const Fr* a, uint64_t n, const PowTable& pw, Fr* tot, const Fr* v, Fr* out,
                         Fr* rem) {
     const uint64_t nt = open_tiles(n);
     if (nt > 1) {
@@ -1422,7 +1378,7 @@ int svdw_open_quotient(svdw_ctx* c, uint32_t k, int form, const void* const* col
         if (!any) return;
         sync(c);
         const uint64_t n = q.n, nt = open_tiles(n);
-        const size_t tc = open_table_cells(k);
+        const uint32_t pb = open_pow_bits(k), tc = (uint32_t)pow_table_cells(pb);
         // the staged cells: the slots' scalars, then a power table per point in the order of the divisions
         const Staged d = stage(c, q.ptrs.data(), ncols, nullptr, 0, ncols + q.passes * tc, (n + nt) * sizeof(Fr),
                                [&](Fr* t) {
@@ -1430,7 +1386,7 @@ int svdw_open_quotient(svdw_ctx* c, uint32_t k, int form, const void* const* col
                                    Fr* tab = t + ncols;
                                    for (const auto& s : q.S)
                                        for (const Fr& x : s) {
-                                           domain_power_tables(x, fr_to_mont(fr_from_u64(1)), open_pow_bits(k), tab);
+                                           pow_table_fill(x, fr_one_mont(), pb, tab);
                                            tab += tc;
                                        }
                                });
@@ -1443,7 +1399,7 @@ int svdw_open_quotient(svdw_ctx* c, uint32_t k, int form, const void* const* col
             });
             for (size_t p = 0; p < q.S[i].size(); ++p, tab += tc) {
                 const bool last = p + 1 == q.S[i].size();   // h1 <- h1 v + Q_i; set 0 starts h1
-                open_divide(c, F, n, open_table(k, tab), tot, last && i ? &q.v : nullptr, last ? (Fr*)h1_out : F,
+                open_divide(c, F, n, pow_table_view(tab, pb), tot, last && i ? &q.v : nullptr, last ? (Fr*)h1_out : F,
                             nullptr);
             }
         }
@@ -1469,18 +1425,18 @@ int svdw_open_linearise(svdw_ctx* c, uint32_t k, int form, const void* const* co
         if (!any) return;
         sync(c);
         const uint64_t n = q.n, nt = open_tiles(n);
-        const size_t tc = open_table_cells(k);
+        const uint32_t pb = open_pow_bits(k), tc = (uint32_t)pow_table_cells(pb);
         // the staged cells: the slots' scalars of G, then the power table of u
         const Staged d = stage(c, q.ptrs.data(), ncols, nullptr, 0, ncols + tc, nt * sizeof(Fr), [&](Fr* t) {
             open_g_scalars(q, t);
-            domain_power_tables(q.u, fr_to_mont(fr_from_u64(1)), open_pow_bits(k), t + ncols);
+            pow_table_fill(q.u, fr_one_mont(), pb, t + ncols);
         });
         const Fr cacc = fr_neg(om_vanish(q.S[0], nullptr, q.u));   // -Z_{S_0}(u) R
         Fr *G = (Fr*)h2_out, *rem = (Fr*)d.cnt;            // G is built in h2_out and divided in place
         profiled(c, "k_open_fold", 32.0 * (ncols + 2) * (double)n, [&] {
             return launch_open_fold(d.ptrs, d.cells, ncols, (const Fr*)h1, cacc, n, G, c->st);
         });
-        open_divide(c, G, n, open_table(k, d.cells + ncols), (Fr*)d.free, nullptr, G, rem);
+        open_divide(c, G, n, pow_table_view(d.cells + ncols, pb), (Fr*)d.free, nullptr, G, rem);
         Fr r;
         hipck(hipMemcpyAsync(&r, rem, sizeof r, hipMemcpyDeviceToHost, c->st), "D2H");
         hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
@@ -1502,7 +1458,7 @@ int svdw_check_open(svdw_ctx* c, uint32_t k, int form, const void* const* cols, 
         sync(c);
         const bool mont = form == SVDW_FORM_MONTGOMERY;
         const uint64_t n = q.n;
-        const Fr one = fr_to_mont(fr_from_u64(1));
+        const Fr one = fr_one_mont();
         // points[0..np) R then t R at the nc columns ptrs: nc x (np + 1) values, as x R
         auto evaluate = [&](const void* const* ptrs, uint32_t nc, const Fr* pts, uint32_t np, Fr* vals) {
             const uint32_t nq = np + 1;

@@ -45,8 +45,7 @@ __global__ __launch_bounds__(kQuotientThreads) void k_quotient(const QuotientArg
             const Fr* const* __restrict__ pz = sig + a.np;
             const uint64_t ru = (j + (a.usable << a.le)) & mask;   // omega^usable X
             // X_j R = omega_e^j shift R
-            const Fr xs = mont_mul(mont_mul(ld_fr(a.whi + (j >> a.h)), ld_fr(a.wlo + (j & ((1ull << a.h) - 1)))),
-                                   a.shift);
+            const Fr xs = mont_mul(pow_at(a.w, j), a.shift);
             h = q_fold(h, a.y, mont_mul(l0, fr_sub(a.one, ld_fr(pz[0] + j))));
             {
                 const Fr z = ld_fr(pz[a.nsets - 1] + j);
@@ -102,7 +101,7 @@ __global__ __launch_bounds__(kQuotientThreads) void k_quotient(const QuotientArg
 hipError_t launch_quotient(const QuotientArgs& a, int form, hipStream_t st) {
     if (!a.ng && !a.np && !a.nl) return hipSuccess;
     if (!a.ptrs || !a.inv || !a.out || a.ek < 1 || a.ek > 28 || a.le > a.ek || a.ng > 65535 || a.np > 65535 ||
-        a.nl > 65535 || (a.np && (!a.chunk || !a.bd || !a.wlo || !a.whi || a.h > a.ek ||
+        a.nl > 65535 || (a.np && (!a.chunk || !a.bd || pow_table_bad(a.w, a.ek) ||
                                   a.nsets != (a.np + a.chunk - 1) / a.chunk)) ||
         (!a.np && a.nsets) || ((a.np | a.nl) && (!a.l0 || !a.llast || !a.lact)) ||
         a.usable >= (1ull << (a.ek - a.le)) || (form != kFormCanonical && form != kFormMontgomery))

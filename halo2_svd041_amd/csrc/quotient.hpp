@@ -24,7 +24,7 @@
 // form adds:
 //
 //   a gate                   3   (+2)   a1 a2, q (..), the fold
-//   the permutation          2          X_j R from the two-level omega_e tables
+//   the permutation          2          X_j R from the omega_e table (pow_table.hpp)
 //                                       and the shift (once per row)
 //                          + 5   (+1)   l_0 (1 - Z_0), l_last Z (Z - 1), two folds
 //                          + 2          per set after the first: the chain and its fold
@@ -42,7 +42,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "fr.hpp"
+#include "pow_table.hpp"                                    // Fr, PowTable
 
 namespace svdw {
 
@@ -54,13 +54,13 @@ struct QuotientArgs {
     // of the lookups, [nl] each
     const Fr* const* ptrs;
     const Fr* bd;                       // beta delta^j phi, j < np
-    const Fr *wlo, *whi;                // omega_e^i R two-level (split h), as the transforms keep them
+    PowTable w;                         // the omega_e table of the extended domain
     const Fr* inv;                      // (shift^n (omega_e^n)^i - 1)^-1 R, i < E
     const Fr *l0, *llast, *lact;        // N cells each, l(X_j) R
     Fr* out;                            // N cells, h_ext phi
     Fr y, beta, shift;                  // c R
     Fr gamma, betaf, one;               // c phi
-    uint32_t ek, le, h, ng, np, chunk, nsets, nl;
+    uint32_t ek, le, ng, np, chunk, nsets, nl;
     uint64_t usable;
 };
 // form: kFormCanonical / kFormMontgomery of the cells and of out.

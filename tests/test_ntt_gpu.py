@@ -381,8 +381,8 @@ def test_no_columns_and_overlap(ctx):
 
 # ------------------------------------- 9. the prover calls alternate on one context
 def test_families_share_one_context(gpu_ctx_factory):
-    """The prover calls stage in one scratch and share the omega tables of the
-    last k: transforms, a permutation product, a commitment and a lookup
+    """The prover calls stage in one scratch and share the context's omega
+    tables: transforms, a permutation product, a commitment and a lookup
     permutation in turn on one context, each against its Python-integer
     restatement, and the first transform again, byte for byte as before."""
     import torch
