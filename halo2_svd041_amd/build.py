@@ -11,13 +11,13 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libsvdw.so")
-SOURCES = ["kernels.hip", "ingest_dev.hip", "export.hip", "lookup.hip", "lookup_product.hip",
+SOURCES = ["kernels.hip", "gemm.hip", "ingest_dev.hip", "export.hip", "lookup.hip", "lookup_product.hip",
            "permutation_product.hip", "permutation_cycles.hip", "ntt.hip", "quotient.hip", "commit.hip", "open.hip",
-           "engine.cpp", "circuit.cpp", "prover.cpp"]
-HEADERS = ["fr.hpp", "pow_table.hpp", "prog.hpp", "kernels.hpp", "crt_tables.hpp", "ingest.hpp", "ingest_dev.hpp",
-           "export.hpp", "lookup.hpp", "grand_product.hpp", "lookup_product.hpp", "permutation_product.hpp",
-           "permutation_cycles.hpp", "ntt.hpp", "quotient.hpp", "fq.hpp", "g1.hpp", "commit.hpp", "open.hpp",
-           "engine_internal.hpp"]
+           "engine.cpp", "gemm.cpp", "circuit.cpp", "prover.cpp"]
+HEADERS = ["fr.hpp", "pow_table.hpp", "prog.hpp", "kernels.hpp", "kernel_common.hpp", "gemm.hpp", "crt_tables.hpp",
+           "ingest.hpp", "ingest_dev.hpp", "export.hpp", "lookup.hpp", "grand_product.hpp", "lookup_product.hpp",
+           "permutation_product.hpp", "permutation_cycles.hpp", "ntt.hpp", "quotient.hpp", "fq.hpp", "g1.hpp",
+           "commit.hpp", "open.hpp", "engine_internal.hpp"]
 ARCH = os.environ.get("SVDW_OFFLOAD_ARCH", "gfx950")
 
 

@@ -24,6 +24,7 @@
 #include <array>
 
 #include "engine_internal.hpp"
+#include "gemm.hpp"                                         // set_debug_trace, for svdw_debug_trace
 #include "ingest.hpp"
 #include "ingest_dev.hpp"
 #include "export.hpp"
@@ -433,15 +434,6 @@ struct OnStream {
     }
     bool on() const { return slot != nullptr; }
 };
-static svdw_mat transposed(const svdw_mat& m) {
-    return svdw_mat{m.phase, m.cols, m.rows, m.off, m.cs, m.rs};
-}
-static uint32_t clog2(uint32_t k) {                    // least l with 2^l >= k
-    uint32_t l = 0;
-    while ((1ull << l) < k) ++l;
-    return l;
-}
-static uint32_t ceil_to(uint32_t x, uint32_t a) { return (x + a - 1) / a * a; }
 static bool same_cells(const svdw_mat& a, const svdw_mat& b) {
     if (a.phase != b.phase || a.off != b.off) return false;
     return (a.rows == b.rows && a.cols == b.cols && a.rs == b.rs && a.cs == b.cs) ||
@@ -479,11 +471,6 @@ static void host_mark(svdw_ctx* c, const char* what) {
     if (!c->opt.host_trace || c->dry) return;
     const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - c->ht0).count();
     fprintf(stderr, "[svdw host] %9.1f us  %s\n", us, what);
-}
-// rows of a row-parallel stage (R rows) that this rank computes / owns
-static void shard_rows(const svdw_ctx* c, uint64_t R, uint64_t* r0, uint64_t* r1) {
-    *r0 = R * c->opt.shard_rank / c->opt.shard_world;
-    *r1 = R * (c->opt.shard_rank + 1) / c->opt.shard_world;
 }
 static void own(svdw_ctx* c, uint32_t phase, bool lookup, uint64_t off, uint64_t n) {
     if (sharded(c) && n) c->owned.push_back({phase, lookup ? 1u : 0u, off, n});
@@ -662,7 +649,6 @@ static void append(svdw_ctx* c, uint32_t phase, uint64_t n, uint64_t nl, uint64_
     s.n += n;
     s.nl += nl;
 }
-static Fr* cellp(svdw_ctx* c, uint32_t phase, uint64_t off) { return c->ph[phase].adv + off; }
 
 // Device pointers into the cell streams (views) are taken while a gadget is
 // being built; a stream reallocation in between would leave them pointing at
@@ -690,7 +676,7 @@ static constexpr uintptr_t kDryBase = (uintptr_t)1 << 44;
 static const Fr* dry_ptr(uint32_t phase, uint64_t off) {
     return reinterpret_cast<const Fr*>(kDryBase * (phase + 1) + off * sizeof(Fr));
 }
-static DView view_of(svdw_ctx* c, const svdw_mat& m) {
+DView view_of(svdw_ctx* c, const svdw_mat& m) {
     DView v;
     memset(&v, 0, sizeof v);
     v.ptr = c->dry ? dry_ptr(m.phase, m.off) : cellp(c, m.phase, m.off);
@@ -1256,205 +1242,6 @@ static svdw_vec zkvector_mul(svdw_ctx* c, uint32_t phase, const svdw_vec& self, 
     return first;
 }
 
-// Balanced base-256 digits needed for |x| < 2^bits.
-static int digits_for_bits(uint32_t bits) {
-    for (int D = 1; D <= 16; ++D) {
-        // max representable magnitude 127 * (256^D - 1) / 255 >= 2^bits - 1 ?
-        long double maxv = 127.0L * (powl(256.0L, D) - 1.0L) / 255.0L;
-        if (maxv >= powl(2.0L, bits) - 1.0L) return D;
-    }
-    return 99;
-}
-static int round_digits(int need) {
-    if (need <= 5) return 5;
-    if (need <= 8) return 8;
-    if (need <= 9) return 9;
-    return 0;
-}
-static bool is_transpose_of(const svdw_mat& b, const svdw_mat& a) {
-    return a.phase == b.phase && a.off == b.off && a.rows == b.cols && a.cols == b.rows &&
-           a.rs == b.cs && a.cs == b.rs;
-}
-static std::vector<uint32_t> maxbits_many(svdw_ctx* c, const std::vector<svdw_mat>& ms) {
-    std::vector<uint32_t> out(ms.size(), 0);
-    if (c->dry || ms.empty()) return out;
-    settle(c);                                  // a pipelined witness's row scans read c->bits
-    const size_t words = ms.size() * kMaxBitBlocks;
-    ensure_buf(c, c->bits, words * sizeof(unsigned));
-    std::vector<uint32_t> nb(ms.size());
-    for (size_t i = 0; i < ms.size(); ++i) {
-        const uint64_t n = (uint64_t)ms[i].rows * ms[i].cols;
-        nb[i] = (uint32_t)std::min<uint64_t>((n + 255) / 256, kMaxBitBlocks);
-        hipck(launch_maxbits(view_of(c, ms[i]), ms[i].rows, ms[i].cols,
-                             (unsigned*)c->bits.p + i * kMaxBitBlocks, c->st), "k_maxbits");
-    }
-    std::vector<unsigned> h(words);
-    hipck(hipMemcpyAsync(h.data(), c->bits.p, words * sizeof(unsigned), hipMemcpyDeviceToHost,
-                         c->st), "D2H");
-    sync(c);
-    for (size_t i = 0; i < ms.size(); ++i)
-        for (uint32_t b = 0; b < nb[i]; ++b) out[i] = std::max(out[i], h[i * kMaxBitBlocks + b]);
-    return out;
-}
-// field_mat_mul (src/matrix/mod.rs:510-537) on stream `s`: c_s = a * b written
-// as canonical cells at `out` (row-major). Exact: balanced base-256 digit planes
-// + v_dot4c_i32_i8 when |entries| fit 9 digits, else Montgomery per MAC.
-// With device bit-length words (sa, sb: one word each) the digit counts are
-// read by the kernels themselves and the host needs no operand bounds.
-// quantized: both operands are ZkMatrix::new cells (|x| < 2^128 by the u128
-// saturation), so the CRT path always applies and no fallback is queued.
-// CRT path residue reuse (prelaunched products of check_svd_phase0): b_cover
-// makes b's planes (kept in digB) also valid for the product (b, b); a_from_b
-// takes a's planes from digB (a is that b) instead of recomputing them.
-// bbuf: where b's planes live (default digB); b_ready: they are already there
-// (row-sharded v.v^T after m.v^T: same b, planes built with b_cover).
-static void gemm_exec(svdw_ctx* c, hipStream_t s, const svdw_mat& a, const svdw_mat& b, Fr* out,
-                      uint32_t bits_a, uint32_t bits_b, const unsigned* sa = nullptr,
-                      const unsigned* sb = nullptr, bool quantized = false,
-                      const unsigned* b_cover = nullptr, bool a_from_b = false,
-                      DBuf* bbuf = nullptr, bool b_ready = false) {
-    DBuf& BB = bbuf ? *bbuf : c->digB;
-    const uint32_t N = a.rows, K = a.cols, M = b.cols;
-    const bool sym = is_transpose_of(b, a);
-    if (!sa && !sb && c->opt.gemm_crt && c->opt.gemm_impl == SVDW_GEMM_MFMA && bits_a <= 128 &&
-        bits_b <= 128 && K <= 8192 && !c->dry) {
-        // host-known bounds: hand them to the CRT kernels as device words
-        // (stream-ordered memsets, one pair per stream)
-        const int slot = s == c->st2 ? 2 : 0;
-        ensure_buf(c, c->gbits, 4 * sizeof(unsigned));
-        unsigned* w = (unsigned*)c->gbits.p + slot;
-        hipck(hipMemsetD32Async((hipDeviceptr_t)w, bits_a, 1, s), "hipMemsetD32Async");
-        hipck(hipMemsetD32Async((hipDeviceptr_t)(w + 1), bits_b, 1, s), "hipMemsetD32Async");
-        sa = w;
-        sb = w + 1;
-    }
-    if (sa && sb && c->opt.gemm_crt && K <= 8192) {   // |acc| <= K 2^14 <= 2^27 (bias in k_gemm_crt)
-        // multi-modular path: residue planes, one int8 GEMM per modulus, CRT
-        uint32_t lk = 0;
-        while ((1ull << lk) < K) ++lk;
-        const uint32_t kpad = (K + 255) / 256 * 256;      // whole groups of four 64-k chunks
-        const uint32_t rpa = (N + 127) / 128 * 128, rpb = (M + 127) / 128 * 128;
-        ensure_buf(c, c->crtR, crt_scratch_bytes(N, M));
-        const uint8_t* Ar;
-        if (a_from_b && sym) {
-            Ar = (const uint8_t*)BB.p;                    // planes of this operand already built
-        } else {
-            ensure_buf(c, c->digA, (size_t)kCrtMaxResidues * rpa * kpad);
-            ProfScope ps(c, s, "k_to_residues", 32.0 * N * K, 0);
-            hipck(launch_to_residues(view_of(c, a), N, K, rpa, kpad, (uint32_t*)c->digA.p, sa,
-                                     sym ? sa : sb, lk, s), "k_to_residues");
-            Ar = (const uint8_t*)c->digA.p;
-        }
-        const uint8_t* Br = Ar;
-        if (!sym && !b_ready) {
-            ensure_buf(c, BB, (size_t)kCrtMaxResidues * rpb * kpad);
-            svdw_mat bt = b;   // Bt(j, k) = b(k, j)
-            bt.rows = b.cols; bt.cols = b.rows; bt.rs = b.cs; bt.cs = b.rs;
-            ProfScope ps(c, s, "k_to_residues", 32.0 * M * K, 0);
-            hipck(launch_to_residues(view_of(c, bt), M, K, rpb, kpad, (uint32_t*)BB.p, sa, sb,
-                                     lk, s, b_cover), "k_to_residues");
-        }
-        if (!sym) Br = (const uint8_t*)BB.p;
-        {
-            ProfScope ps(c, s, std::string("k_gemm_crt") + (sym ? ":s" : ""), 32.0 * N * M,
-                         (double)N * M * K);
-            hipck(launch_gemm_crt(sym, Ar, Br, N, M, rpa, sym ? rpa : rpb,
-                                  kpad, (uint8_t*)c->crtR.p, out, M, 1, sa, sym ? sa : sb, lk, s,
-                                  c->opt.gemm_kern >= 0 ? (uint32_t)c->opt.gemm_kern : (c->gemm_solo ? 3u : 0u)),
-                  "k_gemm_crt");
-        }
-        if (!quantized)
-            hipck(launch_gemm_mont(view_of(c, a), view_of(c, b), N, K, M, out, M, 1, s, sa,
-                                   sym ? sa : sb, (int)lk), "k_gemm_mont");
-        return;
-    }
-    if (sa && sb && K <= 8192) {
-        const uint32_t kcn = (K + 63) / 64;
-        const uint32_t npad = (N + 31) / 32 * 32, mpad = (M + 31) / 32 * 32;
-        ensure_buf(c, c->digA, (size_t)npad * kcn * 9 * 64);
-        {
-            ProfScope ps(c, s, "k_to_digits_mf", 32.0 * N * K + 64.0 * npad * kcn * 9, 0);
-            hipck(launch_to_digits_mf(view_of(c, a), N, K, 9, npad, kcn, (uint32_t*)c->digA.p, s, sa),
-                  "k_to_digits_mf");
-        }
-        const uint8_t* Bd = (const uint8_t*)c->digA.p;
-        if (!sym) {
-            ensure_buf(c, c->digB, (size_t)mpad * kcn * 9 * 64);
-            svdw_mat bt = b;   // Bt(j, k) = b(k, j)
-            bt.rows = b.cols; bt.cols = b.rows; bt.rs = b.cs; bt.cs = b.rs;
-            ProfScope ps(c, s, "k_to_digits_mf", 32.0 * M * K + 64.0 * mpad * kcn * 9, 0);
-            hipck(launch_to_digits_mf(view_of(c, bt), M, K, 9, mpad, kcn, (uint32_t*)c->digB.p, s, sb),
-                  "k_to_digits_mf");
-            Bd = (const uint8_t*)c->digB.p;
-        }
-        {
-            ProfScope ps(c, s, std::string("k_gemm_mfma:rt") + (sym ? "s" : ""),
-                         32.0 * N * M, (double)N * M * K);
-            hipck(launch_gemm_mfma_rt(sym, (const uint8_t*)c->digA.p, Bd, N, M, kcn, out, M, 1, sa,
-                                      sym ? sa : sb, s), "k_gemm_mfma_rt");
-        }
-        hipck(launch_gemm_mont(view_of(c, a), view_of(c, b), N, K, M, out, M, 1, s, sa,
-                               sym ? sa : sb), "k_gemm_mont");
-        return;
-    }
-    int DA = round_digits(digits_for_bits(bits_a)), DB = round_digits(digits_for_bits(bits_b));
-    const bool digits_ok = DA && DB && K <= 8192 && gemm_digits_supported(DA, DB);
-    if (digits_ok && c->opt.gemm_impl == SVDW_GEMM_MFMA) {
-        const uint32_t kcn = (K + 63) / 64;
-        const uint32_t npad = (N + 31) / 32 * 32, mpad = (M + 31) / 32 * 32;
-        ensure_buf(c, c->digA, (size_t)npad * kcn * DA * 64);
-        {
-            ProfScope ps(c, s, "k_to_digits_mf", 32.0 * N * K + 64.0 * npad * kcn * DA, 0);
-            hipck(launch_to_digits_mf(view_of(c, a), N, K, DA, npad, kcn, (uint32_t*)c->digA.p, s),
-                  "k_to_digits_mf");
-        }
-        const uint8_t* Bd = (const uint8_t*)c->digA.p;
-        if (!sym) {
-            ensure_buf(c, c->digB, (size_t)mpad * kcn * DB * 64);
-            svdw_mat bt = b;   // Bt(j, k) = b(k, j)
-            bt.rows = b.cols; bt.cols = b.rows; bt.rs = b.cs; bt.cs = b.rs;
-            ProfScope ps(c, s, "k_to_digits_mf", 32.0 * M * K + 64.0 * mpad * kcn * DB, 0);
-            hipck(launch_to_digits_mf(view_of(c, bt), M, K, DB, mpad, kcn, (uint32_t*)c->digB.p, s),
-                  "k_to_digits_mf");
-            Bd = (const uint8_t*)c->digB.p;
-        }
-        ProfScope ps(c, s, std::string("k_gemm_mfma:") + std::to_string(DA) + "x" +
-                               std::to_string(DB) + (sym ? "s" : ""),
-                     64.0 * kcn * ((double)npad * DA + (sym ? 0.0 : (double)mpad * DB)) + 32.0 * N * M,
-                     (double)N * M * K);
-        hipck(launch_gemm_mfma(DA, DB, sym, (const uint8_t*)c->digA.p, Bd, N, M, kcn, out, M, 1, s),
-              "k_gemm_mfma");
-    } else if (digits_ok) {
-        const uint32_t kg = ((K + 3) / 4 + 7) / 8 * 8;
-        const uint32_t npad = (N + 31) / 32 * 32, mpad = (M + 31) / 32 * 32;
-        ensure_buf(c, c->digA, (size_t)npad * kg * DA * 4);
-        {
-            ProfScope ps(c, s, "k_to_digits", 32.0 * N * K + 4.0 * npad * kg * DA, 0);
-            hipck(launch_to_digits(view_of(c, a), N, K, DA, npad, kg, (uint32_t*)c->digA.p, s),
-                  "k_to_digits");
-        }
-        const uint32_t* Bd = (const uint32_t*)c->digA.p;
-        if (!sym) {
-            ensure_buf(c, c->digB, (size_t)mpad * kg * DB * 4);
-            svdw_mat bt = b;   // Bt(j, k) = b(k, j)
-            bt.rows = b.cols; bt.cols = b.rows; bt.rs = b.cs; bt.cs = b.rs;
-            ProfScope ps(c, s, "k_to_digits", 32.0 * M * K + 4.0 * mpad * kg * DB, 0);
-            hipck(launch_to_digits(view_of(c, bt), M, K, DB, mpad, kg, (uint32_t*)c->digB.p, s),
-                  "k_to_digits");
-            Bd = (const uint32_t*)c->digB.p;
-        }
-        ProfScope ps(c, s, std::string("k_gemm_dot4:") + std::to_string(DA) + "x" +
-                               std::to_string(DB) + (sym ? "s" : ""),
-                     4.0 * kg * ((double)npad * DA + (sym ? 0.0 : (double)mpad * DB)) + 32.0 * N * M,
-                     (double)N * M * K);
-        hipck(launch_gemm_digits(DA, DB, sym, (const uint32_t*)c->digA.p, Bd, N, M, kg, out, M, 1, s),
-              "k_gemm_dot4");
-    } else {
-        ProfScope ps(c, s, "k_gemm_mont", 32.0 * ((double)N * K + (double)K * M + (double)N * M),
-                     (double)N * M * K);
-        hipck(launch_gemm_mont(view_of(c, a), view_of(c, b), N, K, M, out, M, 1, s), "k_gemm_mont");
-    }
-}
 // rows [r0, r1) of a matrix view
 static svdw_mat row_block(const svdw_mat& a, uint64_t r0, uint64_t r1) {
     return svdw_mat{a.phase, (uint32_t)(r1 - r0), a.cols, a.off + r0 * a.rs, a.rs, a.cs};
@@ -1827,7 +1614,7 @@ static void verify_mul_many(svdw_ctx* c, uint32_t phase, const VMul* vm, int n, 
     const Fr* wt[kMaxVerifyBatch];
     // b = X^T of an f64 input of svd_witness: X, else null
     auto f64_of = [&](const svdw_mat& b) -> const svdw_ctx::F64Src* {
-        if (b.cols > 8192) return nullptr;
+        if (b.cols > kCrtMaxK) return nullptr;
         for (auto& s : c->call.f64src)
             if (is_transpose_of(b, s.m) && s.m.rs == (int64_t)s.m.cols && s.m.cs == 1) return &s;
         return nullptr;
@@ -1985,47 +1772,13 @@ static BigU scale_err(double err, uint32_t p) {
     return big_from_u128((unsigned __int128)x);
 }
 
-// The three products of check_svd_phase0 (A[g] * B[g], B = transposes) on st2
-// from residue planes built in one k_residues_f64 launch over svd_witness's f64
-// inputs: m (this rank's rows) into digA, v into digB (covering m.v^T and
-// v.v^T), u into digC. Planes of v and u carry 128 rows of slack so a row block
-// (sharded rank) reads its A tiles as a slice of the full planes. log[g]: the
-// products' stream offsets (dry replay); W: the device bit-length words of m, u, v.
+// The three products of check_svd_phase0 (A[g] * B[g], B = transposes) on pst
+// from svd_witness's f64 inputs (gemm.cpp). log[g]: the products' stream
+// offsets (dry replay); W: the device bit-length words of m, u, v.
 static void prelaunch_products_f64(svdw_ctx* c, const svdw_mat (&A)[3], const svdw_mat (&B)[3],
                                    const std::vector<uint64_t>& log, uint32_t phase,
-                                   unsigned* W, hipStream_t pst) {
-    const uint32_t N = A[0].rows, M = A[0].cols;
-    const uint32_t lkM = clog2(M), lkN = clog2(N), kpM = ceil_to(M, 256), kpN = ceil_to(N, 256);
-    uint64_t rr0[3], rr1[3];
-    for (int g = 0; g < 3; ++g) {
-        rr0[g] = 0; rr1[g] = A[g].rows;
-        if (sharded(c)) shard_rows(c, A[g].rows, &rr0[g], &rr1[g]);
-    }
-    const uint32_t rows_m = (uint32_t)(rr1[0] - rr0[0]);
-    const uint32_t rp_m = ceil_to(std::max(rows_m, 1u), 128), rp_v = ceil_to(M, 128) + 128,
-                   rp_u = ceil_to(N, 128) + 128;
-    ensure_buf(c, c->digA, (size_t)kCrtMaxResidues * rp_m * kpM);
-    ensure_buf(c, c->digB, (size_t)kCrtMaxResidues * rp_v * kpM);
-    ensure_buf(c, c->digC, (size_t)kCrtMaxResidues * rp_u * kpN);
-    ResSegs q;
-    memset(&q, 0, sizeof q);
-    auto seg = [&](const double* in, uint32_t rows, uint32_t cols, uint32_t rp, uint32_t kp,
-                   DBuf& out, std::initializer_list<std::array<int, 3>> pairs) {
-        ResSeg& g = q.seg[q.nseg++];
-        g.in = in; g.out = (uint32_t*)out.p;
-        g.rows = rows; g.cols = cols; g.ld = cols; g.rows_pad = rp; g.kw = kp / 4;
-        g.wa[0] = g.wa[1] = g.wb[0] = g.wb[1] = -1;
-        int k = 0;
-        for (auto& pr : pairs) { g.wa[k] = (int16_t)pr[0]; g.wb[k] = (int16_t)pr[1]; g.lk[k] = (uint32_t)pr[2]; ++k; }
-    };
-    if (rows_m) seg(c->call.svd_f64[0] + rr0[0] * M, rows_m, M, rp_m, kpM, c->digA, {{0, 2, (int)lkM}});
-    seg(c->call.svd_f64[2], M, M, rp_v, kpM, c->digB, {{0, 2, (int)lkM}, {2, 2, (int)lkM}});
-    seg(c->call.svd_f64[1], N, N, rp_u, kpN, c->digC, {{1, 1, (int)lkN}});
-    {
-        ProfScope ps(c, pst, "k_residues_f64",
-                     8.0 * ((double)rows_m * M + (double)M * M + (double)N * N), 0);
-        hipck(launch_residues_f64(q, W, (int)c->P, pst), "k_residues_f64");
-    }
+                                   const unsigned* W, hipStream_t pst) {
+    svd_residues_f64(c, A, W, pst);
     // the stages beside the products wait for the residue planes, which then
     // run alone instead of beside the first (HBM-saturating) stages (same box:
     // 512^2 0.427 -> 0.422 ms, 1024^2 2.098 -> 2.072 ms, 8-way rank 0.36 -> 0.35)
@@ -2037,61 +1790,12 @@ static void prelaunch_products_f64(svdw_ctx* c, const svdw_mat (&A)[3], const sv
     const bool rw = c->opt.res_wait >= 0 ? c->opt.res_wait != 0 : sharded(c);
     if (rw || !c->call.in_pipe || !c->opt.f64_views || c->call.f64reg.empty())
         stream_dep(c, pst, pst != c->st ? c->st : c->st2);
-    const uint8_t* P[3] = {(const uint8_t*)c->digA.p, (const uint8_t*)c->digC.p,
-                           (const uint8_t*)c->digB.p};                 // A planes of m, u, v
-    const uint32_t stride[3] = {rp_m, rp_u, rp_v}, kp[3] = {kpM, kpN, kpM}, lk[3] = {lkM, lkN, lkM};
-    const int wa[3] = {0, 1, 2}, wb[3] = {2, 1, 2};
-    // one launch each for the three GEMMs and combines (same box, tools/probes/probe_opts.sh:
-    // 512^2 P=32 0.43 -> 0.41 ms, 1024^2 P=63 2.10 -> 2.07 ms; row-sharded ranks too)
-    {
-        // the three products in one GEMM launch and one combine launch (each its
-        // own residue scratch): one step of the st2 chain instead of three
-        CrtBatch b;
-        memset(&b, 0, sizeof b);
-        size_t rbytes[3], rtot = 0;
-        for (int g = 0; g < 3; ++g) {
-            rbytes[g] = crt_scratch_bytes(std::max<uint32_t>((uint32_t)(rr1[g] - rr0[g]), 1), B[g].cols);
-            rtot += rbytes[g];
-        }
-        ensure_buf(c, c->crtR, rtot);
-        size_t roff = 0;
-        double bytes = 0, ops = 0;
-        for (int g = 0; g < 3; ++g) {
-            const uint32_t rows = (uint32_t)(rr1[g] - rr0[g]), cols = B[g].cols;
-            if (rows) {
-                const bool sym = !sharded(c) && g > 0;
-                CrtJob& q = b.job[b.njobs++];
-                q.Ar = P[g] + (g == 0 ? 0 : rr0[g] * (uint64_t)kp[g]);
-                q.Br = g == 0 ? (const uint8_t*)c->digB.p : P[g];
-                q.R = (uint8_t*)c->crtR.p + roff;
-                q.out = cellp(c, phase, log[g] + rr0[g] * cols);
-                q.bits_a = W + wa[g];
-                q.bits_b = W + wb[g];
-                q.ors = cols;
-                q.ocs = 1;
-                q.astride = stride[g];
-                q.bstride = g == 0 ? rp_v : stride[g];
-                q.kpad = kp[g];
-                q.N = rows;
-                q.M = cols;
-                q.lk = lk[g];
-                q.sym = sym;
-                bytes += 32.0 * rows * cols;
-                ops += (double)rows * cols * A[g].cols;
-            }
-            roff += rbytes[g];
-        }
-        c->call.gemm_batched = true;
-        b.kern = c->opt.gemm_kern >= 0 ? (uint32_t)c->opt.gemm_kern : 0u;
-        if (b.njobs) {
-            ProfScope ps(c, pst, "k_gemm_crt:multi", bytes, ops);
-            hipck(launch_gemm_crt_multi(b, pst), "k_gemm_crt_multi");
-        }
-        const hipEvent_t done = stream_dep(c, pst, nullptr);   // one completion point
-        for (int g = 0; g < 3; ++g) {
-            c->call.pre.push_back({log[g], done, pst});
-            c->call.gemm_done.push_back(done);
-        }
+    c->call.gemm_batched = true;
+    svd_products_f64(c, A, B, log, phase, W, pst);
+    const hipEvent_t done = stream_dep(c, pst, nullptr);   // one completion point
+    for (int g = 0; g < 3; ++g) {
+        c->call.pre.push_back({log[g], done, pst});
+        c->call.gemm_done.push_back(done);
     }
 }
 
@@ -2123,9 +1827,8 @@ static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const s
         if (!on_device) fetch_bits(c);
         // residue planes straight from svd_witness's f64 inputs (one launch for m,
         // u and v) when they are on the device and the CRT path applies
-        const bool from_f64 = on_device && dev_quantized && c->opt.res_f64 && c->opt.gemm_crt &&
-                              c->call.svd_f64[0] && c->call.svd_f64[1] && c->call.svd_f64[2] && N <= 8192 &&
-                              M <= 8192;
+        const bool from_f64 = on_device && dev_quantized && crt_product_f64(c, std::max(N, M)) &&
+                              c->call.svd_f64[0] && c->call.svd_f64[1] && c->call.svd_f64[2];
         std::vector<uint64_t> key = {n0[0], n0[1], nl0[0], nl0[1], d.phase, d.len, d.off,
                                      (uint64_t)d.stride, f64_key(err_svd), f64_key(err_u), max_bits_d};
         for (const svdw_mat* x : {&m, &u, &v})
@@ -2147,7 +1850,7 @@ static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const s
         // loads of m, u, v done: the quantization event when svd_witness recorded
         // one (the cell stream may already hold later stages), else st's position
         // products on the cell stream (prod_cell): already behind the loads there
-        c->call.prod_on_cell = from_f64 && c->bits_pending && (c->opt.prod_cell > 0 || (c->opt.prod_cell < 0 && sharded(c)));
+        c->call.prod_on_cell = from_f64 && c->bits_pending && products_on_cell_stream(c);
         hipStream_t pst = c->call.prod_on_cell ? c->st : c->st2;
         if (c->call.prod_on_cell) {
         } else if (c->bits_pending) {
@@ -2164,7 +1867,7 @@ static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const s
         const unsigned* sa[3] = {sl[0], sl[1], sl[2]};
         const unsigned* sb[3] = {sl[2], sl[1], sl[2]};
         if (from_f64) {
-            prelaunch_products_f64(c, A, B, log, m.phase, const_cast<unsigned*>(dev_bits), pst);   // (c->bits)
+            prelaunch_products_f64(c, A, B, log, m.phase, dev_bits, pst);   // (c->bits)
             c->call.prelaunched = true;
             host_mark(c, "products queued");
             return;
@@ -2430,9 +2133,8 @@ static svdw_counts svd_witness(svdw_ctx* c, const double* m, const double* u, co
         // at most 60 % of the device memory (1024^2 P=63: 2 x 9.3 GB; 4096^2
         // P=63, 2 x 148 GB, runs unpipelined)
         const double wbytes = 32.0 * (double)(c->plan_val[0] + c->plan_val[1] + c->plan_val[2] + c->plan_val[3]);
-        const bool qualifies = c->opt.pipeline && on_device && c->opt.overlap && c->opt.res_f64 && c->opt.gemm_crt &&
-                               c->opt.gemm_impl == SVDW_GEMM_MFMA && N <= 8192 && M <= 8192 &&
-                               (c->opt.prod_cell > 0 || (c->opt.prod_cell < 0 && sharded(c)));
+        const bool qualifies = c->opt.pipeline && on_device && c->opt.overlap && crt_product_f64(c, std::max(N, M)) &&
+                               products_on_cell_stream(c);
         // The other cell set must already hold this witness, or its growth must
         // fit in the device's free memory now (other contexts, the lane's state
         // and torch's allocations count) with 10 % of the device to spare for
@@ -2552,10 +2254,8 @@ static svdw_counts svd_witness(svdw_ctx* c, const double* m, const double* u, co
     QuantSegs* qp = &qs;
     svdw_mat zm = zkmatrix_new(c, 0, m, N, M, on_device, dbits ? dbits + 64 : nullptr, qp, true);
     // (u, v: the rank's rows and column block only, when b.g comes from the f64
-    // inputs and so do the products' residue planes: no kernel reads the rest;
-    // the conditions of f64_of and of check_svd_phase0's from_f64 prelaunch)
-    const bool part = sharded(c) && on_device && N <= 8192 && M <= 8192 && c->opt.overlap && c->opt.res_f64 &&
-                      c->opt.gemm_crt && c->opt.gemm_impl == SVDW_GEMM_MFMA;
+    // inputs and so do the products' residue planes: no kernel reads the rest)
+    const bool part = sharded(c) && on_device && c->opt.overlap && crt_product_f64(c, std::max(N, M));
     svdw_mat zu = zkmatrix_new(c, 0, u, N, N, on_device, dbits ? dbits + 64 + nbm : nullptr, qp, false, part);
     svdw_mat zv = zkmatrix_new(c, 0, v, M, M, on_device, dbits ? dbits + 64 + nbm + nbu : nullptr, qp, false,
                                part);
@@ -2760,37 +2460,11 @@ static svdw_counts verify_mul_witness(svdw_ctx* c, const double* a, const double
     // (one launch), the GEMM and combine on st, and verify_mul on the third
     // stream from the loads on: its one / gamma-power cells and the b and a
     // scans run beside the product, only the c_s scans wait for it
-    const bool f64 = on_device && !c->dry && c->opt.res_f64 && c->opt.gemm_crt && c->opt.gemm_impl == SVDW_GEMM_MFMA &&
-                     K <= 8192 && qs.nseg == 2;
+    const bool f64 = on_device && !c->dry && crt_product_f64(c, K) && qs.nseg == 2;
     hipEvent_t loaded = nullptr;
     if (f64) {
         loaded = stream_dep(c, c->st, nullptr);
-        const uint32_t kpad = ceil_to(K, 256), rpa = ceil_to(N, 128), rpb = ceil_to(M, 128);
-        ensure_buf(c, c->digA, (size_t)kCrtMaxResidues * rpa * kpad);
-        ensure_buf(c, c->digB, (size_t)kCrtMaxResidues * rpb * kpad);
-        ensure_buf(c, c->crtR, crt_scratch_bytes(N, M));
-        ResSegs q;
-        memset(&q, 0, sizeof q);
-        auto seg = [&](const double* in, uint32_t rows, uint32_t ld, uint32_t rp, DBuf& out, uint32_t tr) {
-            ResSeg& g = q.seg[q.nseg++];
-            g.in = in; g.out = (uint32_t*)out.p;
-            g.rows = rows; g.cols = K; g.ld = ld; g.rows_pad = rp; g.kw = kpad / 4; g.tr = tr;
-            g.wa[0] = 0; g.wb[0] = 1; g.lk[0] = lk;
-            g.wa[1] = g.wb[1] = -1;
-        };
-        seg(a, N, K, rpa, c->digA, 0);
-        seg(b, M, M, rpb, c->digB, 1);                    // b^T(j, k) = b[k * M + j]
-        {
-            ProfScope ps(c, c->st, "k_residues_f64", 8.0 * ((double)N * K + (double)K * M), 0);
-            hipck(launch_residues_f64(q, dbits, (int)c->P, c->st), "k_residues_f64");
-        }
-        {
-            ProfScope ps(c, c->st, "k_gemm_crt", 32.0 * N * M, (double)N * M * K);
-            hipck(launch_gemm_crt(false, (const uint8_t*)c->digA.p, (const uint8_t*)c->digB.p, N, M, rpa, rpb,
-                                  kpad, (uint8_t*)c->crtR.p, cellp(c, 0, off), M, 1, dbits, dbits + 1, lk,
-                                  c->st, c->opt.gemm_kern >= 0 ? (uint32_t)c->opt.gemm_kern : 0u),
-                  "k_gemm_crt");
-        }
+        product_f64(c, c->st, a, b, N, K, M, cellp(c, 0, off), dbits);
     } else if (!c->dry) {
         gemm_exec(c, c->st, za, zb, cellp(c, 0, off), ~0u, ~0u, dbits, dbits + 1, true);
     }

@@ -1,7 +1,8 @@
-// What engine.cpp (the witness engine), circuit.cpp (the assigned-witness calls)
-// and prover.cpp (the prover calls) share: the C ABI's error plumbing, device
-// buffers, the entries' host Fr helpers, the two families' state, the context
-// (svdw_ctx), the engine.cpp functions the other files call, the staged call.
+// What engine.cpp (the witness engine), gemm.cpp (the exact field product),
+// circuit.cpp (the assigned-witness calls) and prover.cpp (the prover calls)
+// share: the C ABI's error plumbing, device buffers, the entries' host Fr
+// helpers, the two families' state, the context (svdw_ctx), the functions that
+// cross a file boundary, the staged call.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -434,14 +435,54 @@ struct svdw_ctx {
     } vmg;
 };
 
-// engine.cpp's functions that circuit.cpp and prover.cpp call too (the library exports only the C ABI).
+// engine.cpp's functions that the other files call too, and gemm.cpp's that
+// engine.cpp calls (the library exports only the C ABI).
 #pragma GCC visibility push(hidden)
 void sync(svdw_ctx* c);                                    // every stream of the context has run dry
 void settle(svdw_ctx* c);                                  // st waits for the tail of a pipelined svd_witness
 void ensure_buf(svdw_ctx* c, DBuf& b, size_t bytes);
 void flush_batch(svdw_ctx* c, hipStream_t s, hipStream_t waiter = nullptr, hipEvent_t then_wait = nullptr);
+DView view_of(svdw_ctx* c, const svdw_mat& m);             // the cells of m as a kernel's operand
+// ---- gemm.cpp: the exact field product c_s = a * b
+extern const uint32_t kCrtMaxK;                            // largest inner dimension of the integer GEMMs
+// The rules of a witness call's products: the CRT path applies (inner dimension
+// K); the residue planes also come straight from the f64 inputs, dims = the
+// largest inner dimension of the call's products ("res_f64", matrix cores);
+// "prod_cell"'s value with -1 resolved.
+bool crt_product(const svdw_ctx* c, uint32_t K);
+bool crt_product_f64(const svdw_ctx* c, uint32_t dims);
+bool products_on_cell_stream(const svdw_ctx* c);
+bool is_transpose_of(const svdw_mat& b, const svdw_mat& a);
+// max over each matrix of bit-length(|signed(x)|), read back (the host waits)
+std::vector<uint32_t> maxbits_many(svdw_ctx* c, const std::vector<svdw_mat>& ms);
+void gemm_exec(svdw_ctx* c, hipStream_t s, const svdw_mat& a, const svdw_mat& b, Fr* out, uint32_t bits_a,
+               uint32_t bits_b, const unsigned* sa = nullptr, const unsigned* sb = nullptr, bool quantized = false,
+               const unsigned* b_cover = nullptr, bool a_from_b = false, DBuf* bbuf = nullptr, bool b_ready = false);
+// check_svd_phase0's three products from the f64 inputs in two steps, so the
+// caller orders other streams between the residue planes and the GEMMs
+void svd_residues_f64(svdw_ctx* c, const svdw_mat (&A)[3], const unsigned* W, hipStream_t pst);
+void svd_products_f64(svdw_ctx* c, const svdw_mat (&A)[3], const svdw_mat (&B)[3], const std::vector<uint64_t>& log,
+                      uint32_t phase, const unsigned* W, hipStream_t pst);
+// verify_mul_witness's product from its f64 inputs
+void product_f64(svdw_ctx* c, hipStream_t s, const double* a, const double* b, uint32_t N, uint32_t K, uint32_t M,
+                 Fr* out, const unsigned* dbits);
 #pragma GCC visibility pop
 inline bool sharded(const svdw_ctx* c) { return c->opt.shard_world > 1; }
+// rows of a row-parallel stage (R rows) that this rank computes / owns
+inline void shard_rows(const svdw_ctx* c, uint64_t R, uint64_t* r0, uint64_t* r1) {
+    *r0 = R * c->opt.shard_rank / c->opt.shard_world;
+    *r1 = R * (c->opt.shard_rank + 1) / c->opt.shard_world;
+}
+inline Fr* cellp(svdw_ctx* c, uint32_t phase, uint64_t off) { return c->ph[phase].adv + off; }
+inline svdw_mat transposed(const svdw_mat& m) {
+    return svdw_mat{m.phase, m.cols, m.rows, m.off, m.cs, m.rs};
+}
+inline uint32_t clog2(uint32_t k) {                        // least l with 2^l >= k
+    uint32_t l = 0;
+    while ((1ull << l) < k) ++l;
+    return l;
+}
+inline uint32_t ceil_to(uint32_t x, uint32_t a) { return (x + a - 1) / a * a; }
 // The check every device entry makes, under the entry's name f.
 inline void need_device(const svdw_ctx* c, const std::string& f) { REQUIRE(!c->dry, f + " needs a device context"); }
 

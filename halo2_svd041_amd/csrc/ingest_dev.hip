@@ -183,7 +183,7 @@ __global__ __launch_bounds__(kThreads) void k_pass2(const uint8_t* __restrict__ 
     const uint64_t b0 = (uint64_t)blockIdx.x * kChunk + (uint64_t)threadIdx.x * kPer;
     Entry e = thread_entry(t, n, entry, sx, b0);
     uint32_t cn = 0, cr = 0, ck = 0;
-    uint8_t p = b0 ? t[b0 - 1] : ' ';
+    uint8_t p = b0 && b0 - 1 < n ? t[b0 - 1] : ' ';   // (a thread past the end reads nothing: spaces, as word_at)
     for (int wi = 0; wi < kPer / 4; ++wi) {
         const uint32_t w = word_at(t, n, b0 + 4 * wi);
 #pragma unroll
@@ -371,7 +371,7 @@ __global__ __launch_bounds__(kThreads) void k_pass3(const uint8_t* __restrict__ 
     const uint64_t c0 = (uint64_t)blockIdx.x * kChunk;
     const uint64_t b0 = c0 + (uint64_t)threadIdx.x * kPer;
     const Entry e0 = thread_entry(t, n, entry, sx, b0);
-    const uint8_t p0 = b0 ? t[b0 - 1] : ' ';
+    const uint8_t p0 = b0 && b0 - 1 < n ? t[b0 - 1] : ' ';
     Entry e = e0;
     uint32_t cn = 0, cr = 0, ck = 0, cs = 0;
     uint8_t p = p0;

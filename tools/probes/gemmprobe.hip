@@ -7,7 +7,7 @@
 // with the shipped kernel's.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/probes/gemmprobe.hip -o tools/probes/gemmprobe
 //   tools/probes/gemmprobe [n=1024] [reps=20]
-#include "../../halo2_svd041_amd/csrc/kernels.hip"
+#include "../../halo2_svd041_amd/csrc/gemm.hip"
 
 #include <stdio.h>
 #include <stdlib.h>
