@@ -1079,7 +1079,7 @@ void svdw_commit_plan(uint32_t k, uint32_t* window_bits, uint32_t* windows);
  * the result have been read back. Scratch is the engine's: the window sums
  * and one batch of (column, window) tasks at a time, a batch kept under
  * 1 GiB (option "commit_scratch_mib") unless a single task needs more: about
- * 21 B per row and 136 B per bucket, 2^(window_bits - 1) buckets, per task. */
+ * 21 B per row and 140 B per bucket, 2^(window_bits - 1) buckets, per task. */
 int svdw_commit(svdw_ctx* ctx, uint32_t k, int form, int bases_form, const void* bases, const void* const* cols,
                 uint32_t ncols, void* out, svdw_commit_result* result);
 typedef struct {

@@ -1,8 +1,10 @@
 """The oracle of the commitment tests, Python integers only: BN254 G1 in
 Jacobian coordinates, a naive multi-scalar multiplication, the SRS file parser,
-"progression" bases P_i = [a0 + i d] G whose MSM has a closed form, and the
-signed-digit split the device documents (include/svdw.h, commit.hpp), restated
-here to place test cases, never to produce an expected value."""
+"progression" bases P_i = [a0 + i d] G whose MSM has a closed form (also tiled),
+and, restated here to place test cases, never to produce an expected value: the
+signed-digit split the device documents (include/svdw.h, commit.hpp) with the
+scalars at its edges, the regimes the code goes through as the size grows, and
+the list of device cases that reach them."""
 import os
 import re
 
@@ -138,7 +140,126 @@ def signed_digits(s: int, c: int, windows: int):
     return out
 
 
-def kernel_constant(name: str) -> int:
-    """A constexpr of csrc/commit.hpp, so that a test placed by it follows it."""
-    src = open(os.path.join(ROOT, "halo2_svd041_amd", "csrc", "commit.hpp")).read()
-    return int(re.search(r"\b%s\s*=\s*(\d+)" % re.escape(name), src).group(1))
+def _source(file: str) -> str:
+    return open(os.path.join(ROOT, "halo2_svd041_amd", "csrc", file)).read()
+
+
+def kernel_constant(name: str, file: str = "commit.hpp") -> int:
+    """A constexpr of csrc/commit.hpp (or a named integer of another source
+    file), so that a test placed by it follows it."""
+    return int(re.search(r"\b%s\s*=\s*(\d+)" % re.escape(name), _source(file)).group(1))
+
+
+def tiled_msm(tile: int, a0: int, d: int, scalars):
+    """The MSM over the bases P_i = progression(tile, a0, d)[i mod tile] as one
+    scalar multiplication: [sum_i (a0 + (i mod tile) d) s_i] G."""
+    return mul(G, sum((a0 + j * d) * sum(scalars[j::tile]) for j in range(min(tile, len(scalars)))) % R)
+
+
+# ---- the size-dependent regimes of svdw_commit / svdw_check_commit, restated from
+# commit.hpp's constants and prover.cpp's literals: to place and to assert cases,
+# never to produce an expected point
+POINT_BYTES = 128                                          # a G1Xyzz accumulator: X, Y, ZZ, ZZZ of 32 bytes
+
+
+def task_cap() -> int:
+    """The tasks of one batch at the most (the grid's y limit), prover.cpp."""
+    return int(re.search(r"min<uint64_t>\(tasks,\s*(\d+)\)", _source("prover.cpp")).group(1))
+
+
+def check_partial_bytes() -> int:
+    """The partial sums svdw_check_commit holds at a time, prover.cpp."""
+    return int(re.search(r"\(\(size_t\)(\d+) << 20\) / per", _source("prover.cpp")).group(1)) << 20
+
+
+def default_scratch_mib() -> int:
+    return kernel_constant("commit_scratch_mib", "engine_internal.hpp")
+
+
+def _plan(k: int):
+    max_bits, best = kernel_constant("kCommitMaxBits"), 2
+    for kk in range(1, k + 1):
+        cost = {c: -(-255 // c) * (2 ** kk + 1.4 * 2.0 * 2 ** (c - 1)) for c in range(best, max_bits + 1)}
+        best = min(cost, key=lambda c: (cost[c], c))       # the smallest c among equal costs, as a strict < keeps it
+    return best
+
+
+def commit_regimes(k: int, c=None, ncols: int = 1, scratch_mib=None) -> dict:
+    """What the code does at size 2^k with window c (None: the plan's), ncols
+    columns and the workspace cap scratch_mib (None: the default):
+    c, W, B = 2^(c-1) buckets, chunks per task and the trips of
+    k_commit_window's strided loop over them, the most significant bit of a
+    chunk's first bucket j0, levels of the slot tree above the slots, buckets per
+    thread of k_commit_scan, commit_check_blocks and the trips of
+    k_commit_check_bits's stride loop, commit_task_bytes, tasks, cap / per, the
+    tasks T of a full batch, and the columns svdw_check_commit checks at a time."""
+    run, fan, chunk = kernel_constant("kCommitRun"), kernel_constant("kCommitFan"), kernel_constant("kCommitChunk")
+    threads, tree = kernel_constant("kCommitThreads"), kernel_constant("kCommitTreeThreads")
+    n = 1 << k
+    c = _plan(k) if c is None else c
+    W, B = -(-255 // c), 1 << (c - 1)
+    chunks = -(-B // chunk)
+    ns = 2 * -(-n // run)
+    slots, levels = ns, 0
+    while ns > fan:
+        ns = -(-ns // fan)
+        slots, levels = slots + ns, levels + 1
+    blocks = min(-(-n // tree), kernel_constant("kCommitCheckBlocks"))
+    per = 4 * B + 4 * (B + 1 + 3) + 4 * n + POINT_BYTES * (slots + B + chunks)
+    cap = (default_scratch_mib() if scratch_mib is None else scratch_mib) << 20
+    tasks = ncols * W
+    part = kernel_constant("kCommitScalarBits") * blocks * POINT_BYTES
+    return {"c": c, "W": W, "B": B, "chunks": chunks, "window_trips": -(-chunks // tree),
+            "j0_top_bit": ((chunks - 1) * chunk).bit_length() - 1, "levels": levels,
+            "scan_per_thread": -(-B // threads), "check_blocks": blocks, "check_trips": -(-n // (blocks * tree)),
+            "task_bytes": per, "row_bytes": 4 * n + POINT_BYTES * slots, "tasks": tasks, "cap_over_per": cap // per,
+            "T": min(max(cap // per, 1), tasks, task_cap()),
+            "check_columns": min(max(check_partial_bytes() // part, 1), ncols)}
+
+
+def top_digit(s: int, c: int) -> int:
+    return signed_digits(s, c, -(-255 // c))[-1]
+
+
+def digit_edge_scalars(c: int) -> list:
+    """Values below r at the edges of the signed-digit split with window c: the
+    last positive digit 2^(c-1), the first negative one 2^(c-1) + 1, the
+    all-ones digit 2^c - 1, 2^c; 2^253 - 1, whose every digit is all ones, so
+    that the carry ripples from window 0 to the top; r - 1, the largest value
+    and (the top digit is monotone in the value) the one with the largest top
+    digit; the smallest value with that top digit, which reaches it through a
+    carry; and the first three shifted into a middle window and into the
+    windows that hold bit 32 and bit 64 of the cell."""
+    W, half = -(-255 // c), 1 << (c - 1)
+    first = [half, half + 1, (1 << c) - 1]
+    # the largest value whose digits below the top are all 2^(c-1): one more carries into the top window
+    below = sum(half << (c * i) for i in range(W - 1))
+    top = top_digit(R - 1, c)
+    assert top >= 1
+    out = first + [1 << c, (1 << 253) - 1, R - 1, ((top - 1) << (c * (W - 1))) + below + 1]
+    for w in (W // 2, 32 // c, 64 // c):
+        out += [v << (c * w) for v in first]
+    assert all(0 < v < R for v in out)
+    return list(dict.fromkeys(out))
+
+
+def _gpu_cases():
+    """(name, k, c or None for the plan's, columns, scratch MiB or None for the
+    default) of every case test_commit_gpu.py adds for the regimes above; that
+    file takes its parameters from here, test_commit_cpu.py asserts what the
+    list covers."""
+    max_bits = kernel_constant("kCommitMaxBits")
+    cases = [("window", 10, c, 3, None) for c in range(2, max_bits + 1)]
+    cases += [("window_srs", 8, c, 3, None) for c in (2, 3, max_bits - 1, max_bits)]
+    cases += [("few_rows", k, max_bits, 3, None) for k in (1, 2)]
+    cases += [("deep", k, None, 3, None) for k in (16, 18, 20)]
+    cases += [("task_cap", 1, None, 600, None), ("one_task", 16, None, 2, 1)]
+    cases += [("checker", 13, None, 33, None), ("checker", 14, None, 2, None)]
+    return cases
+
+
+GPU_CASES = _gpu_cases()
+
+
+def gpu_cases(name: str) -> list:
+    return [case[1:] for case in GPU_CASES if case[0] == name]

@@ -1,11 +1,14 @@
 """The commitments without a GPU: what the reference's SRS file holds (layout,
 curve membership, the Lagrange sum, Lagrange / coefficient agreement through
 ntt_cases.ntt_inverse), the oracle's group law on its edge cases, the
-progression closed form; the new C entries exist, keep the ABI version and check
+progression closed form and its tiled variant; the regimes restated from
+commit.hpp against svdw_commit_plan and the documented workspace figures, the
+digit-edge scalars, and what the device cases cover; the new C entries exist, keep the ABI version and check
 their arguments in the documented order on a planning context; svdw_commit_plan;
 read_srs; the wrappers refuse wrong shapes and dtypes."""
 import ctypes as ct
 import os
+import re
 
 import numpy as np
 import pytest
@@ -13,9 +16,10 @@ import pytest
 import halo2_svd041_amd as hs
 from halo2_svd041_amd import _lib
 from halo2_svd041_amd.srs import read_srs
-from commit_cases import (G, IDENTITY, JID, Q, R, SRS8, jadd, jdouble, jmul, kernel_constant, msm, mul, neg,
-                          on_curve, parse_srs, point_bytes, points_from_bytes, progression, progression_msm,
-                          signed_digits, to_affine, to_jac)
+from commit_cases import (G, GPU_CASES, IDENTITY, JID, Q, R, ROOT, SRS8, commit_regimes, digit_edge_scalars, jadd,
+                          jdouble, jmul, kernel_constant, msm, mul, neg, on_curve, parse_srs, point_bytes,
+                          points_from_bytes, progression, progression_msm, signed_digits, task_cap, tiled_msm,
+                          to_affine, to_jac)
 from ntt_cases import ntt_inverse
 
 ENTRIES = ("svdw_commit", "svdw_check_commit", "svdw_commit_plan", "svdw_commit_add_probe")
@@ -91,6 +95,98 @@ def test_signed_digits_restate_the_scalar():
             d = signed_digits(s, c, w)
             assert sum(x << (c * i) for i, x in enumerate(d)) == s
             assert all(-(1 << (c - 1)) < x <= 1 << (c - 1) for x in d)
+
+
+def test_tiled_closed_form_equals_the_naive_msm():
+    a0, d = 987654321, 2 ** 199 + 5
+    for n, tile in ((64, 16), (32, 32), (8, 1)):
+        bases = progression(tile, a0, d)
+        s = _scalars(n, n + tile)
+        s[1], s[n - 1] = 0, R - 1
+        assert tiled_msm(tile, a0, d, s) == msm([bases[i % tile] for i in range(n)], s), (n, tile)
+    assert tiled_msm(32, a0, d, s[:8]) == progression_msm(8, a0, d, s[:8])   # fewer rows than the tile
+
+
+# ------------------------------------------------------------ the regimes
+def test_regimes_restate_the_plan():
+    for k in range(1, 29):
+        r = commit_regimes(k)
+        assert (r["c"], r["W"]) == hs.commit_plan(k), k
+        assert r["B"] == 1 << (r["c"] - 1) and r["W"] * r["c"] >= 255 > (r["W"] - 1) * r["c"]
+    # what DESIGN.md says of the table and of the tree
+    assert [commit_regimes(k)["c"] for k in (10, 14, 16, 18, 20, 28)] == [8, 11, 13, 15, 16, 16]
+    levels = [commit_regimes(k)["levels"] for k in (7, 8, 11, 12, 15, 16, 19, 20, 23, 24)]
+    assert levels == [0, 1, 1, 2, 2, 3, 3, 4, 4, 5]
+    assert commit_regimes(20)["chunks"] == 1024 and commit_regimes(13)["check_blocks"] == 64
+    assert commit_regimes(13)["check_trips"] == 1 and commit_regimes(14)["check_trips"] == 2
+
+
+def test_regimes_reproduce_the_documented_task_bytes():
+    """include/svdw.h gives a task's workspace in whole bytes per row and per
+    bucket; commit_task_bytes, restated, rounds to those from the sizes on at
+    which the tree's and the chunks' own rounding is below half a byte."""
+    text = open(os.path.join(ROOT, "include", "svdw.h")).read()
+    row, bucket = map(int, re.search(r"about\s+\*?\s*(\d+) B per row and (\d+) B per bucket", text).groups())
+    for k in range(8, 29):
+        for c in {commit_regimes(k)["c"], 7, kernel_constant("kCommitMaxBits")}:
+            r = commit_regimes(k, c)
+            assert abs(r["row_bytes"] / (1 << k) - row) <= 0.5, (k, c)
+            assert abs((r["task_bytes"] - r["row_bytes"]) / r["B"] - bucket) <= 0.5, (k, c)
+    # under the default cap one task is the whole batch from k = 26 on
+    assert [commit_regimes(k)["cap_over_per"] == 0 for k in (25, 26, 28)] == [False, True, True]
+
+
+@pytest.mark.parametrize("c", range(2, 17))
+def test_digit_edge_scalars_hit_every_edge(c):
+    w, half, full = -(-255 // c), 1 << (c - 1), 1 << c
+    edges = digit_edge_scalars(c)
+    assert len(set(edges)) == len(edges) and all(0 < s < R for s in edges)
+    digits = {s: signed_digits(s, c, w) for s in edges}    # asserts that no carry leaves the top window
+    raw = {s: [(s >> (c * i)) & (full - 1) for i in range(w)] for s in edges}
+    flat = [(i, d, raw[s][i]) for s in edges for i, d in enumerate(digits[s])]
+    for s in edges:
+        assert sum(d << (c * i) for i, d in enumerate(digits[s])) == s
+    # the last positive and the first negative digit: in window 0, in a middle window, and in the windows that hold
+    # bit 32 and bit 64 of the cell
+    for at in (0, w // 2, 32 // c, 64 // c):
+        assert {half, -(half - 1)} <= {d for i, d, _ in flat if i == at}, (c, at)
+    # an all-ones digit that receives a carry: magnitude 0, and the carry goes on
+    assert any(d == 0 and r == full - 1 for _, d, r in flat)
+    # the carry ripples through every window whose bits are all ones
+    ripple = digits[(1 << 253) - 1]
+    ones = 253 // c
+    assert ripple[0] == -1 and ripple[1:ones] == [0] * (ones - 1) and any(ripple[ones:])
+    # the top window: non-zero, at its largest, and reached through a carry into it by the smallest such value
+    top = digits[R - 1][-1]
+    assert top > 0 and all(d[-1] <= top for d in digits.values())
+    reached = [s for s in edges if digits[s][-1] == top]
+    assert any(raw[s][-1] == top - 1 for s in reached) and signed_digits(min(reached) - 1, c, w)[-1] == top - 1
+
+
+def test_gpu_cases_cover_every_regime():
+    """The cases test_commit_gpu.py takes from GPU_CASES reach every window
+    size, every depth of the slot tree up to k = 20's, the loops that take a
+    second trip only at size, both ends of the batch size and the checker's
+    column chunks."""
+    reg = [dict(commit_regimes(k, c, ncols, mib), k=k, name=name, ncols=ncols) for name, k, c, ncols, mib in GPU_CASES]
+    max_bits = kernel_constant("kCommitMaxBits")
+    assert {r["c"] for r in reg} >= set(range(2, max_bits + 1))
+    assert {r["c"] * r["W"] for r in reg if r["c"] >= max_bits - 1} == {255, 256}      # the workload's two top windows
+    assert {r["levels"] for r in reg} >= set(range(commit_regimes(20)["levels"] + 1))
+    assert commit_regimes(20)["levels"] == 4 and max(r["k"] for r in reg) == 20
+    assert any(r["chunks"] > kernel_constant("kCommitTreeThreads") and r["window_trips"] > 1 for r in reg)
+    assert any(r["j0_top_bit"] == max_bits - 2 for r in reg)
+    assert max(r["scan_per_thread"] for r in reg) == (1 << (max_bits - 1)) // kernel_constant("kCommitThreads") > 4
+    assert any(r["check_blocks"] == kernel_constant("kCommitCheckBlocks") and r["check_trips"] >= 2
+               for r in reg if r["name"] == "checker")
+    assert any(1 < r["check_columns"] < r["ncols"] < 2 * r["check_columns"] for r in reg if r["name"] == "checker")
+    # a batch at the grid's limit, with a column split between it and the next; one task larger than the cap
+    assert any(r["T"] == task_cap() < r["tasks"] and r["T"] % r["W"] for r in reg)
+    assert any(r["cap_over_per"] == 0 and r["T"] == 1 < r["tasks"] for r in reg)
+    # the plan's own window on the deep trees
+    deep = {r["k"]: r for r in reg if r["name"] == "deep"}
+    assert (deep[16]["levels"], deep[18]["c"], deep[18]["chunks"]) == (3, 15, 512)
+    assert (deep[20]["c"], deep[20]["levels"], deep[20]["chunks"]) == (16, 4, 1024)
 
 
 # ------------------------------------------------------------ the C entries

@@ -4,18 +4,23 @@ coefficient commitments through the device's own transform, skewed and
 degenerate scalars, degenerate bases (every addition a doubling or a
 cancellation), the sizes at which the plan changes its window, the checker
 against tampering, the pieces of h, the columns and Z of an SVD witness end to
-end, and the edge arguments. Sizes beyond the SRS use progression bases, whose
-MSM is one scalar multiplication. Outputs are prefilled with a sentinel byte;
-both cell forms and both base forms unless noted; comparisons byte for byte
-after conversion."""
+end, the edge arguments, and the regimes that depend on the size (commit_cases.
+GPU_CASES: every window size through the option "commit_window_bits" with the
+digit edges placed, slot trees up to k = 20's, a batch at the grid's limit, a
+task larger than the workspace cap, the checker where its blocks are capped and
+its columns chunked). Sizes beyond the SRS use progression bases, whose MSM is
+one scalar multiplication, tiled beyond 2^14. Outputs are prefilled with a
+sentinel byte; both cell forms and both base forms unless noted; comparisons
+byte for byte after conversion."""
 import ctypes as ct
 import functools
 
 import numpy as np
 import pytest
 
-from commit_cases import (G, IDENTITY, Q, R, kernel_constant, msm, mul, neg, parse_srs, point_bytes,
-                          points_from_bytes, progression, progression_msm, signed_digits)
+from commit_cases import (G, IDENTITY, Q, R, commit_regimes, digit_edge_scalars, gpu_cases, kernel_constant, msm, mul,
+                          neg, parse_srs, point_bytes, points_from_bytes, progression, progression_msm, signed_digits,
+                          task_cap, tiled_msm)
 from conftest import gamma_for, gen_svd_input
 from lookup_perm_cases import cell_values
 from ntt_cases import inv, ntt_inverse
@@ -59,11 +64,12 @@ def _cells(vals) -> np.ndarray:
     return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), dtype=np.uint8).reshape(-1, 32).copy()
 
 
-def _device(cols, form: str):
-    """Value lists -> [n, rows, 32] u8 device tensor in `form`."""
+def _device(cols, form: str, cells=None):
+    """Value lists (or their canonical cells [n, rows, 32] u8, where the caller
+    has them) -> [n, rows, 32] u8 device tensor in `form`."""
     import torch
     import halo2_svd041_amd as hs
-    a = np.ascontiguousarray(np.stack([_cells(c) for c in cols]))
+    a = np.ascontiguousarray(np.stack([_cells(c) for c in cols])) if cells is None else cells
     if form == "montgomery":
         a = hs.fr_convert(a.view("<u8").reshape(-1, 4), "canonical", "montgomery").view(np.uint8).reshape(a.shape)
     return torch.from_numpy(a).cuda()
@@ -83,21 +89,27 @@ def _prefilled(n: int):
     return torch.full((n, 64), SENTINEL, dtype=torch.uint8, device="cuda")
 
 
-def _commit_all(ctx, cols, bases, k: int, want: list, counts=None, split: bool = False):
-    """Every combination of forms: the device's points are `want`, byte for byte."""
+def _commit_all(ctx, cols, bases, k: int, want: list, counts=None, split: bool = False, plan=None, combos=COMBOS,
+                cells=None, repeat: int = 1, outs=None):
+    """Every combination of forms: the device's points are `want`, byte for byte.
+    plan: the (c, W) the call must report where an option overrides
+    svdw_commit_plan's. repeat: the bases are `bases` that many times over.
+    outs: collects (form, bases' form, cells, bases, points) on the device."""
     import halo2_svd041_amd as hs
-    c, w = hs.commit_plan(k)
-    for form, bf in COMBOS:
-        dc = _device(cols, form)
+    c, w = plan or hs.commit_plan(k)
+    for form, bf in combos:
+        dc, db = _device(cols, form, cells), _bases(bases, bf).repeat(repeat, 1)
         arg = [dc[:1].contiguous(), dc[1:].contiguous()] if split and len(cols) > 1 else dc
-        out, res = ctx.commit(arg, _bases(bases, bf), k, form=form, bases_form=bf, out=_prefilled(len(cols)))
+        out, res = ctx.commit(arg, db, k, form=form, bases_form=bf, out=_prefilled(len(cols)))
         assert out.cpu().numpy().tobytes() == point_bytes(want, bf), (k, form, bf, _points(out, bf), want)
         assert (res["columns"], res["rows"], res["window_bits"], res["windows"]) == (len(cols), 1 << k, c, w)
         assert res["zero_scalars"] == sum(v == 0 for col in cols for v in col)
         assert res["identity_outputs"] == sum(p == IDENTITY for p in want)
-        assert res["identity_bases"] == sum(p == IDENTITY for p in bases)
+        assert res["identity_bases"] == repeat * sum(p == IDENTITY for p in bases)
         if counts is not None:
             counts.append(res)
+        if outs is not None:
+            outs.append((form, bf, dc, db, out))
 
 
 # ------------------------------------------------------ 1. small sizes on the SRS
@@ -175,7 +187,7 @@ def test_batches_under_a_small_workspace_cap(ctx):
     k = 12
     n = 1 << k
     c, w = hs.commit_plan(k)
-    task_bytes = 21 * n + 136 * (1 << (c - 1))             # include/svdw.h, "commitments"
+    task_bytes = 21 * n + 140 * (1 << (c - 1))             # include/svdw.h, "commitments"
     cols = dict(_skewed(n, 12), random=_rand(n, 120), spike=[0] * (n - 1) + [R - 1])
     assert (1 << 20) // task_bytes < w and (len(cols) * w * task_bytes) >> 20 >= 20
     want = [_closed(col) for col in cols.values()]
@@ -386,3 +398,216 @@ def test_no_columns_overlap_and_out_in_place(ctx):
     assert got is dst and dst.cpu().numpy().tobytes() == point_bytes([msm(g, _rand(n, 9))], "montgomery")
     with pytest.raises(hs.SvdwError):
         ctx.commit(cols, db, k, out=_prefilled(2))
+
+
+# ------------------------------------- 10. the regimes that depend on the size
+# The cases and their parameters are commit_cases.GPU_CASES; test_commit_cpu.py
+# asserts what they cover. Each is placed by commit_regimes, which restates the
+# constants of commit.hpp, and expects what the integer oracle gives.
+TILE = 1 << 14                                             # beyond 2^14 rows the bases are _progression() over and over
+
+
+def _tiled(scalars):
+    return tiled_msm(TILE, A0, D, scalars)
+
+
+def _rand_many(n: int, seed: int) -> list:
+    """_rand for many values: one draw of bytes."""
+    raw = np.random.RandomState(seed).bytes(32 * n)
+    return [int.from_bytes(raw[i:i + 32], "little") % R for i in range(0, 32 * n, 32)]
+
+
+def _small_cells(vals) -> np.ndarray:
+    """_cells for values below 2^63."""
+    a = np.zeros((len(vals), 4), dtype="<u8")
+    a[:, 0] = vals
+    return a.view(np.uint8).reshape(-1, 32)
+
+
+def _reported_plan(ctx, k: int):
+    """The (c, W) a call without columns reports."""
+    import torch
+    n = 1 << k
+    _, res = ctx.commit(torch.empty((0, n, 32), dtype=torch.uint8, device="cuda"),
+                        torch.zeros((n, 64), dtype=torch.uint8, device="cuda"), k)
+    return res["window_bits"], res["windows"]
+
+
+def _edge_column(c: int, n: int) -> list:
+    """digit_edge_scalars(c) among zeros: each value alone, and on two adjacent
+    rows (two entries of one bucket side by side in every window)."""
+    col = [0] * n
+    for i, v in enumerate(digit_edge_scalars(c)):
+        col[7 * i + 3] = col[7 * i + 5] = col[7 * i + 6] = v
+    return col
+
+
+@functools.lru_cache(maxsize=None)
+def _window_shared(k: int, srs: bool):
+    """The bases, and the two columns every window size shares with their sums."""
+    n = 1 << k
+    bases = _srs()[1][:n] if srs else _progression()[:n]
+    cols = [_rand(n, 300 + k), [1] * n]
+    return bases, cols, [msm(bases, c) if srs else _closed(c) for c in cols]
+
+
+def _window_case(ctx, k: int, c: int, ncols: int, srs: bool):
+    import halo2_svd041_amd as hs
+    bases, (wide, ones), (want_wide, want_ones) = _window_shared(k, srs)
+    edge = _edge_column(c, 1 << k)
+    assert sum(v != 0 for v in edge) == 3 * len(digit_edge_scalars(c)) and ncols == 3
+    want = [want_wide, msm(bases, edge) if srs else _closed(edge), want_ones]
+    assert IDENTITY not in want
+    ctx.set_option("commit_window_bits", c)
+    try:
+        assert _reported_plan(ctx, k) == (c, -(-255 // c))
+        _commit_all(ctx, [wide, edge, ones], bases, k, want, plan=(c, -(-255 // c)))
+    finally:
+        ctx.set_option("commit_window_bits", 0)
+    assert _reported_plan(ctx, k) == hs.commit_plan(k)      # option 0: the plan's figures again
+
+
+@pytest.mark.parametrize("k,c,ncols,mib", gpu_cases("window"))
+def test_every_window_size(ctx, k, c, ncols, mib):
+    """A full-width column, the digit edges of this c and an all-ones column
+    under the option "commit_window_bits", against the closed form."""
+    _window_case(ctx, k, c, ncols, srs=False)
+
+
+@pytest.mark.parametrize("k,c,ncols,mib", gpu_cases("window_srs"))
+def test_window_sizes_on_the_srs(ctx, k, c, ncols, mib):
+    """The same on bases that are no progression, against the naive sum."""
+    _window_case(ctx, k, c, ncols, srs=True)
+
+
+@pytest.mark.parametrize("k,c,ncols,mib", gpu_cases("few_rows"))
+def test_few_rows_against_the_most_buckets(ctx, k, c, ncols, mib):
+    """2 or 4 rows and 2^15 buckets: nearly every bucket, chunk and slot is the identity."""
+    import halo2_svd041_amd as hs
+    n, half = 1 << k, 1 << (c - 1)
+    reg = commit_regimes(k, c)
+    assert reg["B"] == half >= 1024 * n and reg["levels"] == 0 and reg["chunks"] > kernel_constant("kCommitTreeThreads")
+    cols = [_rand(n, 400 + k), [half, half + 1, 2 * half - 1, R - 1][:n], [0] * (n - 1) + [1]]
+    assert len(cols) == ncols
+    ctx.set_option("commit_window_bits", c)
+    try:
+        _commit_all(ctx, cols, _progression()[:n], k, [_closed(col) for col in cols], plan=(c, reg["W"]))
+    finally:
+        ctx.set_option("commit_window_bits", 0)
+    assert _reported_plan(ctx, k) == hs.commit_plan(k)
+
+
+def _staircase(n: int) -> list:
+    """Cells 1, 2, 3, ... in runs of these lengths, round after round over a
+    quarter of the rows, the rest one long run and a short one: window 0's
+    sorted list is one spanning bucket after another, which begin and end on
+    both sides of the multiples of 16, 256 and 4096 (a round is 1 mod 16), and
+    the long one spans most of the list and ends short of it."""
+    lengths = (1, 15, 16, 17, 255, 256, 257, 4095, 4097)
+    out, v = [], 1
+    for _ in range(max(1, n // (4 * sum(lengths)))):
+        for m in lengths:
+            out += [v] * m
+            v += 1
+    return out + [v] * (n - len(out) - 37) + [v + 1] * 37
+
+
+@pytest.mark.parametrize("k,c,ncols,mib", gpu_cases("deep"))
+def test_deep_slot_trees(ctx, k, c, ncols, mib):
+    """The plan's own window at sizes whose slot trees have three and four
+    levels, on tiled bases: a full-width column, an all-ones column (one bucket
+    over every run: slots_sum climbs to the top level) and the staircase; then
+    the checker on the same points."""
+    n = 1 << k
+    reg = commit_regimes(k)
+    assert c is None and mib is None and n % TILE == 0
+    assert {16: reg["levels"] == 3, 18: (reg["c"], reg["chunks"]) == (15, 512),
+            20: (reg["c"], reg["levels"]) == (16, 4)}[k], reg
+    stairs = _staircase(n)
+    assert max(stairs) < reg["B"]                           # window 0 only
+    # its buckets hold whole nodes of every level below the top one (which has two nodes: the all-ones column's),
+    # with partial nodes on both sides
+    ends = np.cumsum(np.bincount(stairs)[1:]).tolist()
+    spans = list(zip([0] + ends[:-1], ends))
+    node = kernel_constant("kCommitRun") * kernel_constant("kCommitFan") // 2      # entries under a node of level 1
+    for level in range(1, reg["levels"]):
+        assert any(s % node and e % node and e // node > -(-s // node) for s, e in spans), (k, level)
+        node *= kernel_constant("kCommitFan")
+    cols = [_rand_many(n, 200 + k), [1] * n, stairs]
+    cells = np.stack([_cells(cols[0]), _small_cells(cols[1]), _small_cells(cols[2])])
+    want = [_tiled(col) for col in cols]
+    assert len(cols) == ncols and IDENTITY not in want
+    outs = []
+    _commit_all(ctx, cols, _progression(), k, want, combos=COMBOS if k == 16 else COMBOS[1:2], cells=cells,
+                repeat=n // TILE, outs=outs)
+    form, bf, dc, db, out = outs[-1]
+    assert ctx.check_commit(dc, db, out, k, form=form, bases_form=bf) == \
+        {"columns_checked": ncols, "commit_failures": 0, "bases_checked": n, "bases_off_curve": 0}
+
+
+def test_a_batch_at_the_task_cap(ctx):
+    """More tasks than a grid has rows: the first batch holds 65535 of them and
+    ends inside a column, whose other windows the second batch sums."""
+    (k, c, ncols, mib), = gpu_cases("task_cap")
+    reg = commit_regimes(k, c, ncols, mib)
+    split, inside = divmod(reg["T"], reg["W"])
+    assert reg["T"] == task_cap() == 65535 < reg["tasks"] <= 2 * reg["T"] and (split, inside) == (511, 127)
+    bases = [G, mul(G, 77)]
+    fixed = {1: [0, R - 1], 2: [1, 1]}                      # the split column is a random one
+    cols = [fixed.get((j - split) % 3) or _rand(2, 500 + j) for j in range(ncols)]
+    sums = {j: msm(bases, col) for j, col in fixed.items()}
+    want = [sums.get((j - split) % 3) or msm(bases, col) for j, col in enumerate(cols)]
+    assert cols[split] not in fixed.values() and IDENTITY not in want
+    counts = []
+    _commit_all(ctx, cols, bases, k, want, counts)
+    assert all(r["zero_scalars"] == ncols // 3 and r["columns"] == ncols for r in counts)
+
+
+def test_one_task_larger_than_the_cap(ctx):
+    """A cap below one task's workspace: the task runs all the same, one per batch."""
+    from commit_cases import default_scratch_mib
+    (k, c, ncols, mib), = gpu_cases("one_task")
+    reg = commit_regimes(k, c, ncols, mib)
+    assert reg["task_bytes"] > mib << 20 and reg["cap_over_per"] == 0 and reg["T"] == 1 < reg["tasks"]
+    n = 1 << k
+    cols = [_rand_many(n, 600 + j) for j in range(ncols)]
+    ctx.set_option("commit_scratch_mib", mib)
+    try:
+        _commit_all(ctx, cols, _progression(), k, [_tiled(col) for col in cols], combos=(COMBOS[1], COMBOS[2]),
+                    repeat=n // TILE)
+    finally:
+        ctx.set_option("commit_scratch_mib", default_scratch_mib())
+
+
+@pytest.mark.parametrize("k,c,ncols,mib", gpu_cases("checker"))
+def test_checker_at_size(ctx, k, c, ncols, mib):
+    """The checker where its row blocks are capped (every thread strides over
+    the rows, twice from k = 14) and where the columns are checked in chunks:
+    clean on the commitments, and a flipped byte fails exactly its column, in
+    the first chunk, at its end and in the second."""
+    n = 1 << k
+    reg = commit_regimes(k, c, ncols, mib)
+    blocks, tree = kernel_constant("kCommitCheckBlocks"), kernel_constant("kCommitTreeThreads")
+    chunk = reg["check_columns"]
+    assert reg["check_blocks"] == blocks and (ncols > chunk or reg["check_trips"] >= 2)
+    form, bf = COMBOS[1] if ncols > chunk else COMBOS[2]
+    cols = [_rand_many(n, 700 + 40 * k + j) for j in range(ncols)]
+    outs = []
+    _commit_all(ctx, cols, _progression()[:n], k, [_closed(col) for col in cols], combos=[(form, bf)], outs=outs)
+    _, _, dc, db, out = outs[0]
+    clean = {"columns_checked": ncols, "commit_failures": 0, "bases_checked": n, "bases_off_curve": 0}
+    assert ctx.check_commit(dc, db, out, k, form=form, bases_form=bf) == clean
+    tampered = sorted({0, chunk - 1, chunk} & set(range(ncols)))
+    assert tampered == ([0, chunk - 1, chunk] if ncols > chunk else [0, ncols - 1])
+    for col in tampered:
+        bad = out.clone()
+        bad[col, (17 * col + 3) % 64] ^= 0x04
+        assert ctx.check_commit(dc, db, bad, k, form=form, bases_form=bf) == dict(clean, commit_failures=1), col
+        for j in range(ncols):
+            got = ctx.check_commit(dc[j:j + 1], db, bad[j:j + 1].contiguous(), k, form=form, bases_form=bf)
+            assert got == dict(clean, columns_checked=1, commit_failures=int(j == col)), (col, j)
+    if reg["check_trips"] >= 2:                             # a cell only the second trip of the stride loop reads
+        for row in (blocks * tree, n - 1):
+            cells = dc.clone()
+            cells[ncols - 1, row] = _device([[12345]], form)[0, 0]
+            assert ctx.check_commit(cells, db, out, k, form=form, bases_form=bf) == dict(clean, commit_failures=1), row
