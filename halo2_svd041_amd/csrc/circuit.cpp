@@ -66,18 +66,18 @@ int svdw_check_gates(svdw_ctx* c, svdw_check_result* out) {
         // every region's check words, back to back in one upload (a scan's: its gates); region k's from w0[k] on
         std::vector<uint32_t> words;
         std::vector<size_t> w0(1, 0);
-        for (size_t k = 0; k < c->layout.size(); ++k) {
-            const RegionChecks& rc = c->layout_chk[k];
+        for (size_t k = 0; k < c->wit.layout.size(); ++k) {
+            const RegionChecks& rc = c->wit.layout_chk[k];
             if (!rc.scan) words.insert(words.end(), rc.words.begin(), rc.words.end());
-            const std::vector<uint8_t> bit = rc.scan ? gate_starts(c->layout[k], rc) : std::vector<uint8_t>();
+            const std::vector<uint8_t> bit = rc.scan ? gate_starts(c->wit.layout[k], rc) : std::vector<uint8_t>();
             for (size_t o = 0; o < bit.size(); ++o)
                 if (bit[o]) words.push_back(chk_gate((uint32_t)o));
             w0.push_back(words.size());
         }
         const Staged d = stage_bytes(c, words.data(), words.size() * sizeof(uint32_t));
-        for (size_t k = 0; k < c->layout.size(); ++k) {
-            const svdw_region& r = c->layout[k];
-            const RegionChecks& rc = c->layout_chk[k];
+        for (size_t k = 0; k < c->wit.layout.size(); ++k) {
+            const svdw_region& r = c->wit.layout[k];
+            const RegionChecks& rc = c->wit.layout_chk[k];
             for (const auto& sg : held(c, r.phase, true, r.loff, r.nl))
                 hipck(launch_check_lookups(c->ph[r.phase].lk + sg.first, sg.second, c->LB, d.cnt + 2, c->st),
                       "k_check_lookups");
@@ -116,10 +116,10 @@ struct GateIndex {               // q(i): does a basic gate start at virtual cel
     };
     std::vector<Reg> regs;       // the regions with gates, ascending offsets
     GateIndex(const svdw_ctx* c, uint32_t phase) {
-        for (size_t k = 0; k < c->layout.size(); ++k) {
-            const svdw_region& r = c->layout[k];
+        for (size_t k = 0; k < c->wit.layout.size(); ++k) {
+            const svdw_region& r = c->wit.layout[k];
             if (r.phase != phase || !r.n) continue;
-            Reg g{r.off, r.n, gate_starts(r, c->layout_chk[k])};
+            Reg g{r.off, r.n, gate_starts(r, c->wit.layout_chk[k])};
             if (std::find(g.bit.begin(), g.bit.end(), 1) != g.bit.end()) regs.push_back(std::move(g));
         }
     }
@@ -169,8 +169,8 @@ int svdw_physical_layout(svdw_ctx* c, uint32_t k, uint32_t minimum_rows, svdw_ph
             out->columns_used[ph] = (uint32_t)P.start[ph].size();
             out->num_lookup_advice[ph] = (uint32_t)((TL + R - 1) / R);
         }
-        out->constants = c->consts.size();
-        out->num_fixed = (uint32_t)((c->consts.size() + (1ull << k) - 1) >> k);
+        out->constants = c->wit.consts.size();
+        out->num_fixed = (uint32_t)((c->wit.consts.size() + (1ull << k) - 1) >> k);
         P.valid = true;
     });
 }
@@ -292,9 +292,9 @@ struct EqRegions {
 }  // namespace
 static EqRegions eq_regions(const svdw_ctx* c, uint32_t phase) {
     EqRegions all;
-    for (size_t k = 0; k < c->layout.size(); ++k) {
-        const svdw_region& r = c->layout[k];
-        const RegionChecks& rc = c->layout_chk[k];
+    for (size_t k = 0; k < c->wit.layout.size(); ++k) {
+        const svdw_region& r = c->wit.layout[k];
+        const RegionChecks& rc = c->wit.layout_chk[k];
         if (r.phase != phase || !r.n) continue;
         EqRegionDev d;
         memset(&d, 0, sizeof d);
@@ -359,8 +359,8 @@ static void eq_lists(const svdw_ctx* c, uint32_t phase, const EqRegions& all, st
     const uint64_t me = (uint64_t)phase << 62;
     for (size_t q = 0; q < all.regs.size(); ++q) {
         const EqRegionDev& g = all.regs[q];
-        const RegionChecks& rc = c->layout_chk[all.at[q]];
-        const uint64_t units = g.scan ? c->layout[all.at[q]].rows : g.nitems;
+        const RegionChecks& rc = c->wit.layout_chk[all.at[q]];
+        const uint64_t units = g.scan ? c->wit.layout[all.at[q]].rows : g.nitems;
         for (uint64_t e = 0; e < units; ++e) {
             const uint64_t base = g.off + e * g.unit;
             if (g.scan) {
@@ -384,7 +384,7 @@ static void eq_lists(const svdw_ctx* c, uint32_t phase, const EqRegions& all, st
                     copies->push_back(base + at);
                     break;
                 default:                                  // EQ_EXT: init_rand's RLC cell
-                    copies->push_back(c->ext_off | 2ull << 62); copies->push_back(base + at); break;
+                    copies->push_back(c->wit.ext_off | 2ull << 62); copies->push_back(base + at); break;
                 }
             }
         }
@@ -411,7 +411,7 @@ static void eq_gen_device(svdw_ctx* c, uint32_t phase, const EqRegions& all) {
     char* dev = (char*)cs.eq_in.p;
     hipck(hipMemcpyAsync(dev, in.data(), bytes, hipMemcpyHostToDevice, c->st), "H2D");
     hipck(launch_eq_records((const EqRegionDev*)(dev + o_reg), (uint32_t)all.regs.size(), all.items,
-                            (const uint32_t*)(dev + o_w), (const Fr*)(dev + o_k), phase, c->ext_off,
+                            (const uint32_t*)(dev + o_w), (const Fr*)(dev + o_k), phase, c->wit.ext_off,
                             (uint64_t*)cs.eq_cp.p, (uint64_t*)cs.eq_ks.p, (unsigned*)dev, c->st), "k_eq_records");
     unsigned long long err = 0;                            // (the word and the zeros behind it)
     read_counters(c, (const unsigned long long*)dev, &err, 1);
@@ -510,7 +510,7 @@ int svdw_permutation_edges(svdw_ctx* c, uint64_t* edges, uint64_t cap, svdw_perm
         const uint32_t k = P.k;
         if (k > 28) fail(SVDW_ERANGE, "svdw_permutation_edges: k > 28");
         const EqRegions n[2] = {eq_regions(c, 0), eq_regions(c, 1)};
-        const uint64_t D = c->consts.size(), rows = 1ull << k;
+        const uint64_t D = c->wit.consts.size(), rows = 1ull << k;
         memset(out, 0, sizeof *out);
         out->k = k;
         out->advice[0] = (uint32_t)P.start[0].size();
@@ -556,7 +556,7 @@ int svdw_permutation_edges(svdw_ctx* c, uint64_t* edges, uint64_t cap, svdw_perm
                                  hipMemcpyHostToDevice, c->st), "H2D");
         // the distinct constants, ascending as numbers, and per value the first record that holds it
         std::vector<std::array<uint64_t, 4>> table;
-        for (const auto& v : c->consts) {
+        for (const auto& v : c->wit.consts) {
             Fr x;
             memcpy(x.w, v.data(), sizeof x.w);
             fr_store_words(x, table.emplace_back().data());
@@ -663,8 +663,8 @@ int svdw_rlc_trace(const svdw_ctx* c, uint64_t* cells, uint64_t* copies, uint32_
 int svdw_layout(const svdw_ctx* c, svdw_region* out, uint64_t cap, uint64_t* n) {
     return guarded([&] {
         REQUIRE(c && n, "null argument");
-        *n = c->layout.size();
-        for (uint64_t i = 0; i < cap && i < c->layout.size(); ++i) out[i] = c->layout[i];
+        *n = c->wit.layout.size();
+        for (uint64_t i = 0; i < cap && i < c->wit.layout.size(); ++i) out[i] = c->wit.layout[i];
     });
 }
 int svdw_shard_segments(const svdw_ctx* c, svdw_segment* out, uint64_t cap, uint64_t* n) {

@@ -1,10 +1,14 @@
-// Host engine + C ABI (include/svdw.h) of the SVD-verify witness engine: the
-// context, the program builder, the witness calls, the captured graph, read-out,
-// ingest, options and profiling. The calls on a finished witness (checker,
-// physical layout, equality records, edge list) are in circuit.cpp, the prover
-// calls (lookup argument, grand products, transforms, commitments, quotient,
-// opening) in prover.cpp; engine_internal.hpp holds what the three files share,
-// the definition of svdw_ctx included.
+// The witness engine of the SVD-verify library and its C ABI entries
+// (include/svdw.h): the program builder, cell-stream memory, views, stage
+// launches and batches, the checker's notes, the reference functions, the two
+// witness calls, the captured graph and the reference entries. The context's
+// lifetime, lanes, options, stream hand-off, marks and profiling are in
+// context.cpp, read-out in export.cpp, text ingest in ingest.cpp, the exact
+// product in gemm.cpp, the calls on a finished witness (checker, physical
+// layout, equality records, edge list) in circuit.cpp, the prover calls (lookup
+// argument, grand products, transforms, commitments, quotient, opening) in
+// prover.cpp; engine_internal.hpp holds what the files share, the definition of
+// svdw_ctx included.
 //
 // Each reference function (src/matrix/mod.rs, src/svd/mod.rs) becomes:
 //   1. a data-independent cell program built on the host by replaying the
@@ -20,15 +24,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <algorithm>
-#include <array>
-
 #include "engine_internal.hpp"
-#include "gemm.hpp"                                         // set_debug_trace, for svdw_debug_trace
-#include "ingest.hpp"
-#include "ingest_dev.hpp"
-#include "export.hpp"
-#include "commit.hpp"                                       // kCommitMaxBits, for the "commit_window_bits" option
 
 // ------------------------------------------------------- host big integers
 // Unsigned 256-bit integers (BigUint bounds of the range checks).
@@ -344,43 +340,11 @@ struct PB {
     }
 };
 
-// ------------------------------------- context (svdw_ctx: engine_internal.hpp)
+// ---------------------- stream dependencies, bit bounds, cell-stream memory
 // debug logs (read once: getenv scans the environment)
 static bool env_flag(const char* name) { const char* v = getenv(name); return v && *v && *v != '0'; }
 static const bool g_batch_log = env_flag("SVDW_BATCH_LOG");
 static const bool g_stage_log = env_flag("SVDW_STAGE_LOG");
-void sync(svdw_ctx* c) {
-    if (c->dry) return;
-    REQUIRE(!c->call.capturing, "internal: synchronisation during graph capture");
-    hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
-    hipck(hipStreamSynchronize(c->st2), "hipStreamSynchronize");
-    if (c->st3) hipck(hipStreamSynchronize(c->st3), "hipStreamSynchronize");
-    c->tail_pending = false;
-    if (c->lane) sync(c->lane);
-}
-// After a pipelined svd_witness its tail (st2, st3) is not joined into st:
-// anything else queued on the context waits for it first.
-void settle(svdw_ctx* c) {
-    if (c->dry || !c->tail_pending || c->call.in_pipe) return;
-    for (int k = 0; k < 2; ++k)
-        hipck(hipStreamWaitEvent(c->st, c->tail_ev[c->tail_last][k], 0), "hipStreamWaitEvent");
-    c->tail_pending = false;
-}
-// Device bytes held by a set of cell streams (both phases, advice + lookups).
-static double set_bytes(const Stream (&s)[2]) {
-    return 32.0 * (double)(s[0].cap + s[0].lcap + s[1].cap + s[1].lcap);
-}
-// Free the pipeline's other cell set (after the work that may read it).
-static void release_alt(svdw_ctx* c) {
-    if (c->dry || set_bytes(c->alt) == 0) return;
-    sync(c);
-    for (auto& s : c->alt) {
-        if (s.adv) hipck(hipFree(s.adv), "hipFree");
-        if (s.lk) hipck(hipFree(s.lk), "hipFree");
-        s = Stream{};
-    }
-    ++c->epoch;
-}
 // Dependency recorded on `from`; `to` waits for it (cross-stream dependency).
 // The returned handle is waited on later with dep_wait. (Round 4 measured the
 // alternative of stream values, hipStreamWriteValue32 / hipStreamWaitValue32,
@@ -441,14 +405,14 @@ static bool same_cells(const svdw_mat& a, const svdw_mat& b) {
 }
 static void reg_bits(svdw_ctx* c, const svdw_mat& m, uint32_t bits) {
     if (bits == ~0u) return;
-    for (auto& r : c->mbits)
+    for (auto& r : c->wit.mbits)
         if (same_cells(r.m, m)) { r.bits = bits; return; }
-    c->mbits.push_back({m, bits});
+    c->wit.mbits.push_back({m, bits});
 }
 static uint32_t bits_of(const svdw_ctx* c, const svdw_mat& m) {
-    for (auto& r : c->mbits)
+    for (auto& r : c->wit.mbits)
         if (same_cells(r.m, m)) return r.bits;
-    for (auto& p : c->prods)
+    for (auto& p : c->wit.prods)
         if (same_cells(p.cs, m)) {
             const uint32_t ba = bits_of(c, p.a), bb = bits_of(c, p.b);
             if (ba != ~0u && bb != ~0u) return ba + bb + p.lk;
@@ -460,7 +424,7 @@ static void fetch_bits(svdw_ctx* c) {
     hipck(hipEventSynchronize(c->ev_bits), "hipEventSynchronize");
     // the words are final once the event has fired: read them now (no copy is
     // queued on st per witness, the device-side consumers read the words directly)
-    hipck(hipMemcpy(c->hbits, c->dbitw, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H");
+    hipck(hipMemcpy(c->hbits, c->wit.dbitw, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H");
     c->bits_pending = false;
     for (int i = 0; i < 3; ++i) {
         c->qbits[i] = c->hbits[i];
@@ -474,35 +438,6 @@ static void host_mark(svdw_ctx* c, const char* what) {
 }
 static void own(svdw_ctx* c, uint32_t phase, bool lookup, uint64_t off, uint64_t n) {
     if (sharded(c) && n) c->owned.push_back({phase, lookup ? 1u : 0u, off, n});
-}
-static void clear_streams(svdw_ctx* c) {
-    c->owned.clear();
-    c->layout.clear();
-    c->layout_chk.clear();
-    c->ext_off = 0;
-    c->consts.clear();
-    c->phys.valid = false;
-    c->bits_pending = false;
-    for (auto& s : c->ph) { s.n = 0; s.nl = 0; }
-    c->mbits.clear();
-    c->prods.clear();
-    c->dwords.clear();
-    c->dbitw = nullptr;
-    c->gamma_slots.clear();
-}
-void ensure_buf(svdw_ctx* c, DBuf& b, size_t bytes) {
-    if (c->dry || b.cap >= bytes) return;
-    REQUIRE(!c->call.capturing, "internal: allocation during graph capture");
-    ++c->epoch;
-    sync(c);
-    if (b.p) hipck(hipFree(b.p), "hipFree");
-    b.p = nullptr;
-    size_t cap = std::max(bytes, b.cap + b.cap / 2);
-    if (hipMalloc(&b.p, cap) != hipSuccess) {
-        b.cap = 0;
-        fail(SVDW_ENOMEM, "device allocation failed (scratch)");
-    }
-    b.cap = cap;
 }
 // The bit-length words out[0 .. nred) folded inside the quantize launch
 // (BitFold) when its first nred segments carry block maxima laid out back to
@@ -644,8 +579,8 @@ static void append(svdw_ctx* c, uint32_t phase, uint64_t n, uint64_t nl, uint64_
     r.nl = nl;
     r.rows = rows ? rows : 1;
     snprintf(r.tag, sizeof r.tag, "%s", tag);
-    c->layout.push_back(r);
-    c->layout_chk.emplace_back();
+    c->wit.layout.push_back(r);
+    c->wit.layout_chk.emplace_back();
     s.n += n;
     s.nl += nl;
 }
@@ -653,20 +588,23 @@ static void append(svdw_ctx* c, uint32_t phase, uint64_t n, uint64_t nl, uint64_
 // Device pointers into the cell streams (views) are taken while a gadget is
 // being built; a stream reallocation in between would leave them pointing at
 // the freed buffer. Every ABI entry point that appends after taking a view
-// therefore sizes the streams first from a dry replay of itself (layouts are
-// data independent), so nothing reallocates inside the call.
+// therefore runs through here: the streams are sized first from a dry replay of
+// fn (layouts are data independent), so nothing reallocates inside the call;
+// then fn runs on the context, and its result is returned.
 template <class F>
-static void pregrow(svdw_ctx* c, F&& fn) {
-    if (c->dry) return;
-    svdw_ctx plan;
-    plan.P = c->P;
-    plan.LB = c->LB;
-    for (int p = 0; p < 2; ++p) { plan.ph[p].n = c->ph[p].n; plan.ph[p].nl = c->ph[p].nl; }
-    fn(&plan);
-    for (int p = 0; p < 2; ++p) {
-        grow(c, c->ph[p].adv, c->ph[p].n, c->ph[p].cap, plan.ph[p].n);
-        grow(c, c->ph[p].lk, c->ph[p].nl, c->ph[p].lcap, plan.ph[p].nl);
+static auto run_sized(svdw_ctx* c, F&& fn) {
+    if (!c->dry) {
+        svdw_ctx plan;
+        plan.P = c->P;
+        plan.LB = c->LB;
+        for (int p = 0; p < 2; ++p) { plan.ph[p].n = c->ph[p].n; plan.ph[p].nl = c->ph[p].nl; }
+        fn(&plan);
+        for (int p = 0; p < 2; ++p) {
+            grow(c, c->ph[p].adv, c->ph[p].n, c->ph[p].cap, plan.ph[p].n);
+            grow(c, c->ph[p].lk, c->ph[p].nl, c->ph[p].lcap, plan.ph[p].nl);
+        }
     }
+    return fn(c);
 }
 
 // --------------------------------------------------------------- views
@@ -708,20 +646,6 @@ static DView f64_view(const svdw_ctx* c, const DView& v) {
     }
     return v;
 }
-static svdw_mat mat_of_vec(const svdw_vec& v) {   // len x 1 column
-    return svdw_mat{v.phase, v.len, 1, v.off, v.stride, 0};
-}
-static void check_mat(const svdw_ctx* c, const svdw_mat& m) {
-    REQUIRE(m.phase < 2, "matrix phase must be 0 or 1");
-    REQUIRE(m.rows >= 1 && m.cols >= 1, "empty matrix");
-    // every referenced cell must already exist
-    int64_t lo = (int64_t)m.off, hi = (int64_t)m.off;
-    int64_t er = (int64_t)(m.rows - 1) * m.rs, ec = (int64_t)(m.cols - 1) * m.cs;
-    lo += std::min<int64_t>(er, 0) + std::min<int64_t>(ec, 0);
-    hi += std::max<int64_t>(er, 0) + std::max<int64_t>(ec, 0);
-    REQUIRE(lo >= 0 && (uint64_t)hi < c->ph[m.phase].n, "matrix view outside its phase stream");
-}
-static void check_vec(const svdw_ctx* c, const svdw_vec& v) { check_mat(c, mat_of_vec(v)); }
 
 // ------------------------------------------------------- stage launches
 // Appends the stage's cells for `nelem` elements; returns the advice offset.
@@ -901,7 +825,7 @@ static uint64_t f64_key(double x) {
 static void note_const(svdw_ctx* c, const Fr& v) {
     std::array<uint32_t, 8> w;
     for (int i = 0; i < 8; ++i) w[i] = v.w[i];
-    c->consts.insert(w);
+    c->wit.consts.insert(w);
 }
 // the last appended region is `nelem` copies of pb's program: record its gates
 // (views: the source cells as (phase, offset), strided views into the cell
@@ -944,7 +868,7 @@ static RegionChecks::EqSrc eqsrc_vec(const svdw_vec& v) {   // cells v.off + t v
     return eqsrc_chain(v.phase, v.off, v.phase, v.off + v.stride, v.stride);
 }
 static void note_gates(svdw_ctx* c, const PB& pb, uint32_t cols = 1, size_t reg = ~size_t(0)) {
-    RegionChecks& r = reg == ~size_t(0) ? c->layout_chk.back() : c->layout_chk.at(reg);
+    RegionChecks& r = reg == ~size_t(0) ? c->wit.layout_chk.back() : c->wit.layout_chk.at(reg);
     r.eq = pb.eq;
     r.eqk.assign(pb.a.K, pb.a.K + pb.a.nk);
     for (int k = 0; k < kMaxViews; ++k) {             // the loaded values' source cells
@@ -1124,7 +1048,7 @@ static void check_mat_diff_views(svdw_ctx* c, uint32_t phase, const DView& a, co
     run_stage(c, phase, pb, rows * cols, cols, "check_mat_diff");
     // equality sources of the padded / diagonal entries: the zero padding
     // constant (check_svd_phase0), check_mat_id's zero and scalar_id cells
-    RegionChecks& r = c->layout_chk.back();
+    RegionChecks& r = c->wit.layout_chk.back();
     if (pad_a.phase >= 0) { r.esrc[0].pad_phase = pad_a.phase; r.esrc[0].pad_off = pad_a.off; }
     if (b.mode != VIEW_STRIDED) {
         r.esrc[1] = RegionChecks::EqSrc();
@@ -1265,7 +1189,7 @@ static svdw_mat honest_prover_mat_mul(svdw_ctx* c, uint32_t phase, const svdw_ma
     {   // |c_s| <= K * 2^bits_a * 2^bits_b, resolved when the operand bounds are known
         uint32_t lk = 0;
         while ((1ull << lk) < a.cols) ++lk;
-        c->prods.push_back({cs, a, b, lk});
+        c->wit.prods.push_back({cs, a, b, lk});
     }
     if (bits_a == ~0u) bits_a = bits_of(c, a);
     if (bits_b == ~0u) bits_b = bits_of(c, b);
@@ -1312,13 +1236,13 @@ static int scan_na(const svdw_ctx* c, const svdw_mat& a) {
 // a product of two of them (bits_a + bits_b + lk); wa = -1: unknown.
 static NaSpec scan_spec(const svdw_ctx* c, const svdw_mat& a) {
     auto word = [&](const svdw_mat& m) -> int16_t {
-        for (auto& r : c->dwords)
+        for (auto& r : c->wit.dwords)
             if (same_cells(r.m, m)) return r.word;
         return -1;
     };
     const int16_t w = word(a);
     if (w >= 0) return NaSpec{w, -1, 0, 0};
-    for (auto& p : c->prods)
+    for (auto& p : c->wit.prods)
         if (same_cells(p.cs, a)) {
             const int16_t wa = word(p.a), wb = word(p.b);
             if (wa >= 0 && wb >= 0) return NaSpec{wa, wb, (uint16_t)p.lk, 0};
@@ -1336,7 +1260,7 @@ static NaSpec job_spec(const svdw_ctx* c, const svdw_mat& a) {
 // the jobs' specs (job_spec), so the host needs no operand bounds
 static int batch_na_host(const svdw_ctx* c, const svdw_mat* ms, int n) {
     int na = 1;
-    bool host = true, dev = c->dbitw != nullptr;
+    bool host = true, dev = c->wit.dbitw != nullptr;
     for (int i = 0; i < n; ++i) {
         if (bits_of(c, ms[i]) != ~0u) na = std::max(na, scan_na(c, ms[i]));
         else host = false;
@@ -1360,7 +1284,7 @@ static ScaleTab scale_tab() {
 // field_mat_vec_mul with the vector given as canonical copy + scaled table.
 // the equality sources of an inner-product row region: a's row i, the vector w
 static void note_scan(svdw_ctx* c, const svdw_mat& a, const RegionChecks::EqSrc& w) {
-    RegionChecks& r = c->layout_chk.back();
+    RegionChecks& r = c->wit.layout_chk.back();
     r.scan = true;
     r.unit = 3 * a.cols + 1;
     r.esrc[0] = eqsrc_mat(a);
@@ -1506,9 +1430,9 @@ static void verify_mul_many(svdw_ctx* c, uint32_t phase, const VMul* vm, int n, 
             append(c, phase, (uint64_t)(d - 1) * p.pows.a.C, 0, &p.pows_off, &p.pows_loff,
                    "verify_mul_gamma_pows");
             note_gates(c, p.pows);
-            c->gamma_slots.emplace_back(c->layout_chk.size() - 1, p.pows.kext);
+            c->wit.gamma_slots.emplace_back(c->wit.layout_chk.size() - 1, p.pows.kext);
             // v_(i-1): the `one` cell, then the previous mul's output
-            c->layout_chk.back().esrc[0] = eqsrc_chain(phase, p.one_off, phase, p.pows_off + 3, 4);
+            c->wit.layout_chk.back().esrc[0] = eqsrc_chain(phase, p.one_off, phase, p.pows_off + 3, 4);
             stage_own(c, phase, p.pows, d - 1, 1, p.pows_off, p.pows_loff);
         }
         const RegionChecks::EqSrc gsrc = eqsrc_chain(phase, p.one_off, phase, p.pows_off + 3, 4);
@@ -1529,9 +1453,9 @@ static void verify_mul_many(svdw_ctx* c, uint32_t phase, const VMul* vm, int n, 
         append(c, phase, (uint64_t)a.rows * p.eq.a.C, (uint64_t)a.rows * p.eq.a.L, &p.eq_off,
                &p.eq_loff, "verify_mul_is_equal", a.rows);
         note_gates(c, p.eq);
-        p.eq_reg = c->layout_chk.size() - 1;
-        c->layout_chk.back().esrc[0] = eqsrc_mat(mat_of_vec(p.csv));
-        c->layout_chk.back().esrc[1] = eqsrc_mat(mat_of_vec(p.abv));
+        p.eq_reg = c->wit.layout_chk.size() - 1;
+        c->wit.layout_chk.back().esrc[0] = eqsrc_mat(mat_of_vec(p.csv));
+        c->wit.layout_chk.back().esrc[1] = eqsrc_mat(mat_of_vec(p.abv));
         stage_own(c, phase, p.eq, a.rows, 1, p.eq_off, p.eq_loff);
     }
     if (c->dry) return;
@@ -1595,7 +1519,7 @@ static void verify_mul_many(svdw_ctx* c, uint32_t phase, const VMul* vm, int n, 
         return j;
     };
     auto launch = [&](Scans& S, const char* name) {
-        S.sb.bitw = c->dbitw;
+        S.sb.bitw = c->wit.dbitw;
         S.sb.f = scale_tab();
         const int na = batch_na_host(c, S.ms, (int)S.sb.njobs);
         ProfScope ps(c, c->st, name, S.bytes, S.ops);
@@ -1637,7 +1561,7 @@ static void verify_mul_many(svdw_ctx* c, uint32_t phase, const VMul* vm, int n, 
         memset(&cb, 0, sizeof cb);
         cb.tab = gtab;
         cb.tl = c->gp_len;
-        cb.bitw = c->dbitw;
+        cb.bitw = c->wit.dbitw;
         int slot[kMaxVerifyBatch];
         size_t poff[kMaxVerifyBatch], ptot = 0;
         for (int i = 0; i < n; ++i) {
@@ -1701,7 +1625,7 @@ static void verify_mul_many(svdw_ctx* c, uint32_t phase, const VMul* vm, int n, 
             slot[i] = nv++;
         }
         vb.njobs = nv;
-        vb.bitw = c->dbitw;
+        vb.bitw = c->wit.dbitw;
         {
             ProfScope ps(c, c->st, "k_matvec_values", 0, 0);
             hipck(launch_matvec_values(vb, batch_na_host(c, vms, nv), c->st), "k_matvec_values");
@@ -1940,9 +1864,9 @@ static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const s
         // honest_prover_mat_mul registers them: the c_s scans then size their
         // operand on the device (NaSpec) instead of falling back to full
         // Montgomery products (8-way shard rank: 81 -> 25 us)
-        c->prods.push_back({pl.m_times_vt, m, t_v, clog2(M)});
-        c->prods.push_back({pl.u_times_ut, u, t_u, clog2(N)});
-        c->prods.push_back({pl.v_times_vt, v, t_v, clog2(M)});
+        c->wit.prods.push_back({pl.m_times_vt, m, t_v, clog2(M)});
+        c->wit.prods.push_back({pl.u_times_ut, u, t_u, clog2(N)});
+        c->wit.prods.push_back({pl.v_times_vt, v, t_v, clog2(M)});
         auto f = std::move(c->call.early_p1);
         c->call.early_p1 = nullptr;
         f(pl);
@@ -2201,12 +2125,12 @@ static svdw_counts svd_witness(svdw_ctx* c, const double* m, const double* u, co
     // compute_rlc_fixed_len(ctx_rlc, [one, zero]) with one = ctx_gate.load_constant(1),
     // zero = ctx_gate.load_zero(): two constant cells at the head of ctx_gate (the
     // stream here); [E(one), E(zero), W(gamma)] go to ctx_rlc, whose cell 2 is init_rand.
-    c->ext_off = 0;
+    c->wit.ext_off = 0;
     c->rlc.n = 0;
     if (c->opt.rlc_prefix) {
         const svdw_vec one = put_cell(c, 1, fr_from_u64(1), true);
         const svdw_vec zero = put_cell(c, 1, fr_zero(), true);
-        c->ext_off = 2;
+        c->wit.ext_off = 2;
         c->rlc.n = 3;
         c->rlc.cells[0] = fr_from_u64(1);
         c->rlc.cells[1] = fr_zero();
@@ -2285,8 +2209,8 @@ static svdw_counts svd_witness(svdw_ctx* c, const double* m, const double* u, co
         c->bits_pending = true;
         c->qmat[0] = zm; c->qmat[1] = zu; c->qmat[2] = zv;
         // the same words for the device-side choices (row-scan operand widths)
-        c->dbitw = dbits;
-        c->dwords = {{zm, 0}, {zu, 1}, {zv, 2}};
+        c->wit.dbitw = dbits;
+        c->wit.dwords = {{zm, 0}, {zu, 1}, {zv, 2}};
         host_mark(c, "quantize + bits queued");
     }
     // Phase 1 needs only the products (queued on st2 by check_svd_phase0), the
@@ -2393,7 +2317,7 @@ static svdw_counts verify_mul_witness(svdw_ctx* c, const double* a, const double
         plan_and_grow(c, {0x766d77ull, N, K, M}, [&](svdw_ctx* plan) {
             verify_mul_witness(plan, nullptr, nullptr, N, K, M, false, gamma);
         });
-    c->ext_off = 0;
+    c->wit.ext_off = 0;
     c->gp_ev = nullptr;
     if (!c->dry && c->opt.hold_us) {       // every stream of the step waits for st's hold
         hipck(launch_hold(c->opt.hold_us, c->st), "k_hold");
@@ -2444,8 +2368,8 @@ static svdw_counts verify_mul_witness(svdw_ctx* c, const double* a, const double
     }
     if (!c->dry) {
         if (!folded) hipck(launch_bits_reduce(dbits + 64, seg, 2, dbits, c->st), "k_bits_reduce");
-        c->dbitw = dbits;
-        c->dwords = {{za, 0}, {zb, 1}};
+        c->wit.dbitw = dbits;
+        c->wit.dwords = {{za, 0}, {zb, 1}};
     }
     host_mark(c, "quantize queued");
     if (on_device && !c->dry)
@@ -2455,7 +2379,7 @@ static svdw_counts verify_mul_witness(svdw_ctx* c, const double* a, const double
     append(c, 0, (uint64_t)N * M, 0, &off, nullptr, "product", N);
     const svdw_mat cs{0, N, M, off, (int64_t)M, 1};
     const uint32_t lk = clog2(K);
-    c->prods.push_back({cs, za, zb, lk});
+    c->wit.prods.push_back({cs, za, zb, lk});
     // device inputs: residue planes of a and b^T straight from the f64 inputs
     // (one launch), the GEMM and combine on st, and verify_mul on the third
     // stream from the loads on: its one / gamma-power cells and the b and a
@@ -2496,37 +2420,15 @@ static svdw_counts verify_mul_witness(svdw_ctx* c, const double* a, const double
 // is sized) and replayed with one hipGraphLaunch; the host state the call
 // leaves (layout, checks, counts) is restored from the capture, with gamma
 // patched into the constants that hold it.
-static void vmg_drop(svdw_ctx* c) {
-    if (c->vmg.exec) (void)hipGraphExecDestroy(c->vmg.exec);
-    c->vmg.exec = nullptr;
-    c->vmg.key.clear();
-}
 static void vmg_snapshot(svdw_ctx* c, const svdw_counts& k) {
-    auto& g = c->vmg;
-    g.layout = c->layout;
-    g.layout_chk = c->layout_chk;
-    g.consts = c->consts;
-    g.gamma_slots = c->gamma_slots;
-    g.mbits = c->mbits;
-    g.prods = c->prods;
-    g.dwords = c->dwords;
-    g.dbitw = c->dbitw;
-    g.ext_off = c->ext_off;
-    g.counts = k;
+    c->vmg.rec = c->wit;
+    c->vmg.counts = k;
 }
 static svdw_counts vmg_restore(svdw_ctx* c, const Fr& gamma) {
     const auto& g = c->vmg;
     clear_streams(c);
-    c->layout = g.layout;
-    c->layout_chk = g.layout_chk;
-    c->consts = g.consts;
-    c->gamma_slots = g.gamma_slots;
-    for (const auto& s : c->gamma_slots) c->layout_chk.at(s.first).eqk.at((size_t)s.second) = gamma;
-    c->mbits = g.mbits;
-    c->prods = g.prods;
-    c->dwords = g.dwords;
-    c->dbitw = g.dbitw;
-    c->ext_off = g.ext_off;
+    c->wit = g.rec;
+    c->wit.patch_gamma(gamma);
     c->ext_gamma = gamma;
     c->ph[0].n = g.counts.advice0;
     c->ph[1].n = g.counts.advice1;
@@ -2534,184 +2436,6 @@ static svdw_counts vmg_restore(svdw_ctx* c, const Fr& gamma) {
     c->ph[1].nl = g.counts.lookup1;
     return g.counts;
 }
-// Every scratch buffer of a state (release, footprint).
-static std::vector<DBuf*> dbufs(svdw_ctx* c) {
-    std::vector<DBuf*> v = {&c->f64in, &c->digA, &c->digB, &c->digC, &c->w1c, &c->w1t, &c->w2c, &c->w2t, &c->bits,
-                            &c->gpc, &c->gtab, &c->gpc_alt, &c->gtab_alt, &c->crtR, &c->gbits, &c->colpart, &c->qfold,
-                            &c->ing_x, &c->ing_e, &c->ing_c, &c->ing_p10, &c->ing_val, &c->ing_npos, &c->ing_nd,
-                            &c->ing_rpos, &c->ing_kpos, &c->ing_err, &c->ing_q, &c->exp_buf[0], &c->exp_buf[1],
-                            &c->staging.buf};
-    for (DBuf* d : c->circuit.dbufs()) v.push_back(d);
-    for (DBuf* d : c->prover.dbufs()) v.push_back(d);
-    for (int i = 0; i < kMaxScanJobs; ++i) {
-        v.push_back(&c->wbc[i]);
-        v.push_back(&c->wbt[i]);
-        v.push_back(&c->bvfull[i]);
-    }
-    return v;
-}
-// Device bytes a state holds (cell sets and scratch).
-static double state_bytes(svdw_ctx* c) {
-    double b = set_bytes(c->ph) + set_bytes(c->alt);
-    for (DBuf* d : dbufs(c)) b += (double)d->cap;
-    return b;
-}
-// Every device object is released on its own (a state whose creation failed
-// part-way holds some of them only).
-static void ctx_release(svdw_ctx* c) {
-    if (!c) return;
-    if (c->lane) ctx_release(c->lane);
-    if (!c->dry) {
-        for (hipStream_t t : {c->st_cell ? c->st_cell : c->st, c->st2, c->st3})
-            if (t) (void)hipStreamSynchronize(t);
-        vmg_drop(c);
-        for (auto& s : c->ph) { (void)hipFree(s.adv); (void)hipFree(s.lk); }
-        for (auto& s : c->alt) { (void)hipFree(s.adv); (void)hipFree(s.lk); }
-        for (auto& t : c->tail_ev)
-            for (auto e : t)
-                if (e) (void)hipEventDestroy(e);
-        for (DBuf* b : dbufs(c))
-            if (b->p) (void)hipFree(b->p);
-        if (c->hbits) (void)hipHostFree(c->hbits);
-        if (c->ev_bits) (void)hipEventDestroy(c->ev_bits);
-        for (auto e : c->xev)
-            if (e) (void)hipEventDestroy(e);
-        for (auto e : c->exp_ev)
-            if (e) (void)hipEventDestroy(e);
-        for (auto& m : c->mk.ev)
-            for (auto e : m)
-                if (e) (void)hipEventDestroy(e);
-        for (auto& r : c->recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
-        for (auto e : c->pool) (void)hipEventDestroy(e);
-        for (auto e : c->deps) (void)hipEventDestroy(e);
-        if (c->lin_ev) (void)hipEventDestroy(c->lin_ev);
-        for (hipStream_t t : {c->st3, c->st2, c->st_cell ? c->st_cell : c->st})
-            if (t) (void)hipStreamDestroy(t);
-    }
-    delete c;
-}
-// "lanes": may the next verify_mul_witness run on the other state? Yes when
-// that state already holds as much device memory as this one (the calls have
-// one shape), or when its growth to this one's footprint fits in free memory
-// with 10 % of the device to spare; else the call stays on this state.
-static bool lane_fits(svdw_ctx* c) {
-    const double need = state_bytes(c) - (c->lane ? state_bytes(c->lane) : 0.0);
-    if (need <= 0) return true;
-    size_t fr = 0, tot = 0;
-    if (hipMemGetInfo(&fr, &tot) != hipSuccess) return false;
-    return need + 0.1 * (double)tot <= (double)fr;
-}
-// Device state of a new context: its three streams, the pinned bit words, events.
-static void ctx_init_device(svdw_ctx* c) {
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking);
-    c->st_cell = c->st;
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->st2, hipStreamNonBlocking);
-    // the third stream exists from the start: one created lazily inside a
-    // call would not wait for what st already waits for (svdw_stream_wait)
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->st3, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&c->hbits, 64 * sizeof(uint32_t), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_bits, hipEventDisableTiming | hipEventReleaseToDevice);
-    for (int k = 0; k < 4 && e == hipSuccess; ++k)
-        e = hipEventCreateWithFlags(&c->tail_ev[k / 2][k % 2], hipEventDisableTiming | hipEventReleaseToDevice);
-    c->stream_id[0] = c->st;
-    c->stream_id[1] = c->st2;
-    c->stream_id[2] = c->st3;
-    size_t mfree = 0;
-    if (e == hipSuccess) e = hipMemGetInfo(&mfree, &c->mem_total);
-    if (e != hipSuccess) fail(SVDW_EDEVICE, std::string("HIP device init failed: ") + hipGetErrorString(e));
-}
-// The settings (options, shard, profiler) of `s` onto the lane `d`; a change
-// bumps the lane's epoch (its captured graph no longer applies).
-static void copy_settings(svdw_ctx* d, const svdw_ctx* s) {
-    if (d->opt == s->opt) return;
-    d->opt = s->opt;
-    ++d->epoch;
-}
-// svdw_set_option's names: a value in [lo, hi] (else SVDW_EINVAL with `msg`)
-// goes to `set` (a bool member takes value != 0).
-struct OptionDef {
-    const char* name;
-    int64_t lo, hi;
-    const char* msg;
-    void (*set)(svdw_ctx*, int64_t);
-};
-template <auto Member>
-static void set_opt(svdw_ctx* c, int64_t v) {
-    c->opt.*Member = static_cast<std::remove_reference_t<decltype(c->opt.*Member)>>(v);
-}
-static void set_lanes(svdw_ctx* c, int64_t v) { c->lanes = (int)v; }   // (the handle's, not the state's)
-static void set_pipeline(svdw_ctx* c, int64_t v) {
-    c->opt.pipeline = (int)v;
-    if (!v) {                                        // the other cell set is not needed any more
-        release_alt(c);
-        if (c->lane) release_alt(c->lane);
-    }
-}
-static void set_stage_rot(svdw_ctx* c, int64_t v) {
-    c->opt.stage_flags = v ? (c->opt.stage_flags | STAGE_ROT) : (c->opt.stage_flags & ~STAGE_ROT);
-}
-static const char kStageElemsMsg[] = "stage_elems: a multiple of 16 in [16, 256]";
-static void set_stage_elems(svdw_ctx* c, int64_t v) {
-    REQUIRE(v % 16 == 0, kStageElemsMsg);
-    c->opt.stage_elems = (uint32_t)v;
-}
-static void set_commit_window_bits(svdw_ctx* c, int64_t v) {
-    REQUIRE(v != 1, "commit_window_bits: 0 (the plan) or 2..16");
-    c->opt.commit_window_bits = (uint32_t)v;
-}
-using Opt = svdw_ctx::Options;
-static const OptionDef kOptions[] = {
-    {"lanes", 1, 2, "lanes: 1 or 2", set_lanes},   // verify_mul_witness on two alternating states
-    {"pipeline", 0, 1, "pipeline: 0 or 1", set_pipeline},   // pipelined svd_witness (svd_witness)
-    {"vm_linear", 0, 1, "vm_linear: 0 or 1", set_opt<&Opt::vm_linear>},   // captured verify_mul_witness on one stream
-    {"graph", 0, 1, "graph: 0 or 1", set_opt<&Opt::graph_vm>},   // captured verify_mul_witness (vm_graph)
-    {"gemm_impl", SVDW_GEMM_MFMA, SVDW_GEMM_VALU, "gemm_impl: 0 (mfma) or 1 (valu)", set_opt<&Opt::gemm_impl>},
-    {"stage_elems", 16, 256, kStageElemsMsg, set_stage_elems},
-    {"prod_cell", -1, 1, "prod_cell: -1, 0 or 1", set_opt<&Opt::prod_cell>},
-    {"phase1_overlap", 0, 2, "phase1_overlap: 0, 1 or 2", set_opt<&Opt::phase1_overlap>},
-    {"hold_us", 0, 100000, "hold_us: 0..100000", set_opt<&Opt::hold_us>},   // timing aid: GPU-only schedule of a witness
-    {"rlc_prefix", INT64_MIN, INT64_MAX, "", set_opt<&Opt::rlc_prefix>},
-    {"res_f64", INT64_MIN, INT64_MAX, "", set_opt<&Opt::res_f64>},
-    {"gemm_crt", 0, 1, "gemm_crt: 0 or 1", set_opt<&Opt::gemm_crt>},
-    {"res_wait", -1, 1, "res_wait: -1 (auto), 0 or 1", set_opt<&Opt::res_wait>},   // pipelined: st2 waits for the residue planes
-    {"place_trials", 0, 8, "place_trials: 0..8", set_opt<&Opt::place_trials>},   // cell streams >= 256 MiB: best of this many placements
-    {"stage_rot", 0, 1, "stage_rot: 0 or 1", set_stage_rot},   // phase B from a block-dependent window on
-    {"gemm_kern", -1, 2, "gemm_kern: -1 (auto), 0, 1 or 2", set_opt<&Opt::gemm_kern>},   // CRT GEMM kernel variant (bit-identical)
-    {"stage_batch", INT64_MIN, INT64_MAX, "", set_opt<&Opt::stage_batch>},   // small independent stages share k_stage_multi launches
-    {"f64_views", INT64_MIN, INT64_MAX, "", set_opt<&Opt::f64_views>},
-    {"p1_at", -1, 3, "p1_at: -1 (auto), 0, 1, 2 or 3", set_opt<&Opt::p1_at>},
-    {"commit_window_bits", 0, kCommitMaxBits, "commit_window_bits: 0 (the plan) or 2..16", set_commit_window_bits},
-    {"commit_scratch_mib", 1, 65536, "commit_scratch_mib: 1..65536", set_opt<&Opt::commit_scratch_mib>},
-    {"dchk_at", 0, 2, "dchk_at: 0 (cell stream), 1 (st2) or 2 (st3)", set_opt<&Opt::dchk_at>},   // pipelined: the d checks' stream
-    {"gamma_at", -1, 1, "gamma_at: -1 (auto), 0 (cell stream) or 1 (st3)", set_opt<&Opt::gamma_at>},   // pipelined: k_gamma_prep's stream
-    {"overlap", INT64_MIN, INT64_MAX, "", set_opt<&Opt::overlap>},
-};
-// "lanes": exchange this state with the lane's (created on first use).
-static_assert(std::is_nothrow_move_constructible<svdw_ctx>::value && std::is_nothrow_move_assignable<svdw_ctx>::value, "svdw_ctx moves");
-static void lane_switch(svdw_ctx* c) {
-    if (!c->lane) {
-        svdw_ctx* L = new svdw_ctx();
-        L->P = c->P;
-        L->LB = c->LB;
-        L->device = c->device;
-        L->dry = false;
-        try {
-            ctx_init_device(L);
-        } catch (...) {
-            ctx_release(L);
-            throw;
-        }
-        c->lane = L;
-    }
-    svdw_ctx* L = c->lane;
-    copy_settings(L, c);
-    std::swap(*c, *L);
-    std::swap(c->lane, L->lane);                  // (the handle keeps the lane and the option)
-    std::swap(c->lanes, L->lanes);
-    std::swap(c->mk, L->mk);
-}
-static hipEvent_t xevent(svdw_ctx* c, int i);
 // caller: the caller's stream (svdw_verify_mul_witness_on), waited for by the
 // state that runs the call (after the lane switch)
 static svdw_counts verify_mul_witness_api(svdw_ctx* c, const double* a, const double* b, uint32_t N,
@@ -2831,374 +2555,12 @@ static svdw_counts verify_mul_witness_api(svdw_ctx* c, const double* a, const do
 // ================================================================== C ABI
 extern "C" {
 
-const char* svdw_last_error(void) { return g_err.c_str(); }
-
-int svdw_ctx_create(const svdw_params* p, svdw_ctx** out) {
-    return guarded([&] {
-        REQUIRE(p && out, "null argument");
-        if (p->precision_bits < 1 || p->precision_bits > 63)
-            fail(SVDW_ERANGE, "precision_bits must be in [1, 63] (src/svd/mod.rs:74 uses u64)");
-        if (p->lookup_bits < 8 || p->lookup_bits > 63)
-            fail(SVDW_ERANGE, "lookup_bits must be in [8, 63]");
-        svdw_ctx* c = new svdw_ctx();
-        c->P = p->precision_bits;
-        c->LB = p->lookup_bits;
-        c->device = p->device;
-        c->dry = p->device < 0;
-        if (const char* h = getenv("SVDW_HOST_TRACE")) c->opt.host_trace = atoi(h) != 0;
-        if (const char* g = getenv("SVDW_GEMM"))
-            c->opt.gemm_impl = (!strcmp(g, "valu") || !strcmp(g, "dot4")) ? SVDW_GEMM_VALU : SVDW_GEMM_MFMA;
-        if (!c->dry) {
-            try {
-                ctx_init_device(c);
-            } catch (...) {
-                ctx_release(c);
-                throw;
-            }
-        }
-        *out = c;
-    });
-}
-int svdw_ctx_destroy(svdw_ctx* c) {
-    return guarded([&] { ctx_release(c); });
-}
-int svdw_ctx_reset(svdw_ctx* c) {
-    return guarded([&] {
-        REQUIRE(c, "null ctx");
-        sync(c);
-        clear_streams(c);
-        c->call.pre.clear();
-        c->call.pre_wait_st = nullptr;
-        c->call.pre_wait_ev = nullptr;
-    });
-}
 int svdw_reserve(svdw_ctx* c, uint32_t phase, uint64_t na, uint64_t nl) {
     return guarded([&] {
         REQUIRE(c && phase < 2, "bad argument");
         Stream& s = c->ph[phase];
         grow(c, s.adv, s.n, s.cap, na);
         grow(c, s.lk, s.nl, s.lcap, nl);
-    });
-}
-// Stream-ordered hand-off with a caller's stream (e.g. torch's current stream):
-// the context's streams wait for the work queued on `s` so far (inputs it is
-// still writing, buffers it still reads), and `s` waits for the context's
-// queued work (outputs it will read). No host wait either way.
-static hipEvent_t xevent(svdw_ctx* c, int i) {
-    if (!c->xev[i])
-        hipck(hipEventCreateWithFlags(&c->xev[i], hipEventDisableTiming), "hipEventCreate");
-    return c->xev[i];
-}
-// st waits at once; st2 / st3 inherit the wait from st where a call orders them
-// after it, else wait themselves (xwait_side). With lanes, the lane's state too
-// (the next verify_mul_witness runs there).
-int svdw_stream_wait(svdw_ctx* c, void* stream) {
-    return guarded([&] {
-        REQUIRE(c, "null ctx");
-        if (c->dry) return;
-        const hipStream_t s = (hipStream_t)stream;
-        const hipEvent_t e = xevent(c, 0);
-        hipck(hipEventRecord(e, s), "hipEventRecord");
-        for (svdw_ctx* x : {c, c->lane}) {
-            if (!x) continue;
-            hipck(hipStreamWaitEvent(x->st, e, 0), "hipStreamWaitEvent");
-            x->xwait_side = e;
-        }
-    });
-}
-int svdw_stream_signal(svdw_ctx* c, void* stream) {
-    return guarded([&] {
-        REQUIRE(c, "null ctx");
-        if (c->dry) return;
-        const hipStream_t s = (hipStream_t)stream;
-        for (svdw_ctx* x : {c, c->lane}) {
-            if (!x) continue;
-            int i = 1;
-            for (hipStream_t t : {x->st, x->st2, x->st3}) {
-                if (!t) continue;
-                flush_batch(x, t);
-                const hipEvent_t e = xevent(x, i++);
-                hipck(hipEventRecord(e, t), "hipEventRecord");
-                hipck(hipStreamWaitEvent(s, e, 0), "hipStreamWaitEvent");
-            }
-        }
-    });
-}
-int svdw_debug_trace(void* buf) {
-    return guarded([&] { hipck(set_debug_trace(buf), "set_debug_trace"); });
-}
-int svdw_sync(svdw_ctx* c) {
-    return guarded([&] { REQUIRE(c, "null ctx"); sync(c); });
-}
-// 1 when every launch queued on the context (both lanes) has completed, 0
-// while some still runs; no host wait (hipStreamQuery).
-int svdw_query(svdw_ctx* c) {
-    int done = 1;
-    const int rc = guarded([&] {
-        REQUIRE(c, "null ctx");
-        if (c->dry) return;
-        for (svdw_ctx* x : {c, c->lane}) {
-            if (!x) continue;
-            for (hipStream_t t : {x->st, x->st2, x->st3}) {
-                if (!t) continue;
-                const hipError_t e = hipStreamQuery(t);
-                if (e == hipErrorNotReady) {
-                    done = 0;
-                    return;
-                }
-                hipck(e, "hipStreamQuery");
-            }
-        }
-    });
-    return rc ? rc : done;
-}
-// Completion marks (svdw_mark / svdw_mark_done / svdw_mark_wait): an event on
-// each stream of both lanes, recorded behind what is queued there (pending
-// batched stages launched first), so no stream waits for anything. A slot is
-// reused 16 marks later; a ticket whose slot holds a later mark is answered
-// by that mark (later done implies earlier done; not done reads as 0).
-int svdw_mark(svdw_ctx* c, uint64_t* ticket) {
-    return guarded([&] {
-        REQUIRE(c && ticket, "null argument");
-        const uint64_t t = ++c->mk.seq;
-        *ticket = t;
-        if (c->dry) return;
-        const int k = (int)(t % svdw_ctx::kMarks);
-        int i = 0;
-        for (svdw_ctx* x : {c, c->lane}) {
-            if (!x) continue;
-            for (hipStream_t st : {x->st, x->st2, x->st3}) {
-                if (!st) continue;
-                flush_batch(x, st);
-                hipEvent_t& e = c->mk.ev[k][i++];
-                if (!e) hipck(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
-                hipck(hipEventRecord(e, st), "hipEventRecord");
-            }
-        }
-        c->mk.used[k] = (uint8_t)i;
-        c->mk.t[k] = t;
-    });
-}
-// the slot answering ticket t, or -1 (t not issued)
-static int mark_slot(const svdw_ctx* c, uint64_t t) {
-    if (!t || t > c->mk.seq) return -1;
-    return (int)(t % svdw_ctx::kMarks);
-}
-int svdw_mark_done(svdw_ctx* c, uint64_t ticket) {
-    int done = 1;
-    const int rc = guarded([&] {
-        REQUIRE(c, "null ctx");
-        const int k = mark_slot(c, ticket);
-        REQUIRE(k >= 0, "svdw_mark_done: ticket not issued");
-        if (c->dry) return;
-        for (int i = 0; i < c->mk.used[k]; ++i) {
-            const hipError_t e = hipEventQuery(c->mk.ev[k][i]);
-            if (e == hipErrorNotReady) {
-                done = 0;
-                return;
-            }
-            hipck(e, "hipEventQuery");
-        }
-    });
-    return rc ? rc : done;
-}
-int svdw_mark_wait(svdw_ctx* c, uint64_t ticket) {
-    return guarded([&] {
-        REQUIRE(c, "null ctx");
-        const int k = mark_slot(c, ticket);
-        REQUIRE(k >= 0, "svdw_mark_wait: ticket not issued");
-        if (c->dry) return;
-        for (int i = 0; i < c->mk.used[k]; ++i) hipck(hipEventSynchronize(c->mk.ev[k][i]), "hipEventSynchronize");
-    });
-}
-uint64_t svdw_advice_len(const svdw_ctx* c, uint32_t phase) { return c && phase < 2 ? c->ph[phase].n : 0; }
-uint64_t svdw_lookup_len(const svdw_ctx* c, uint32_t phase) { return c && phase < 2 ? c->ph[phase].nl : 0; }
-const void* svdw_advice_device_ptr(const svdw_ctx* c, uint32_t phase) { return c && phase < 2 ? c->ph[phase].adv : nullptr; }
-const void* svdw_lookup_device_ptr(const svdw_ctx* c, uint32_t phase) { return c && phase < 2 ? c->ph[phase].lk : nullptr; }
-
-static int copy_cells(svdw_ctx* c, uint32_t phase, uint64_t off, uint64_t n, uint64_t* out, bool lk) {
-    return guarded([&] {
-        REQUIRE(c && phase < 2 && out, "bad argument");
-        REQUIRE(!c->dry, "planning context has no cells");
-        const Stream& s = c->ph[phase];
-        REQUIRE(off + n <= (lk ? s.nl : s.n), "copy range outside the stream");
-        if (!n) return;
-        settle(c);
-        hipck(hipMemcpyAsync(out, (lk ? s.lk : s.adv) + off, n * sizeof(Fr), hipMemcpyDeviceToHost,
-                             c->st), "D2H");
-        sync(c);
-    });
-}
-int svdw_copy_advice(svdw_ctx* c, uint32_t phase, uint64_t off, uint64_t n, uint64_t* out) {
-    return copy_cells(c, phase, off, n, out, false);
-}
-int svdw_copy_lookup(svdw_ctx* c, uint32_t phase, uint64_t off, uint64_t n, uint64_t* out) {
-    return copy_cells(c, phase, off, n, out, true);
-}
-
-// ------------------------------------------------------------- read-out
-// Cells in the form the consumer holds them (export.hpp): a stream range or a
-// view, canonical or Montgomery, or dequantized to f64; into device memory
-// (queued, no host wait) or host memory (staged through bounded scratch).
-static constexpr size_t kExportChunk = 64ull << 20;       // bytes of cells per staging half
-static hipEvent_t export_event(svdw_ctx* c, int i) {
-    if (!c->exp_ev[i])
-        hipck(hipEventCreateWithFlags(&c->exp_ev[i], hipEventDisableTiming), "hipEventCreate");
-    return c->exp_ev[i];
-}
-// The cell stream behind everything queued on the context so far: a pipelined
-// witness's tail (settle) and whatever a call left on the side streams.
-static void export_join(svdw_ctx* c) {
-    settle(c);
-    flush_batch(c, c->st);
-    int i = 4;
-    for (hipStream_t t : {c->st2, c->st3}) {
-        const hipEvent_t e = export_event(c, i++);
-        if (!t || t == c->st) continue;
-        flush_batch(c, t);
-        hipck(hipEventRecord(e, t), "hipEventRecord");
-        hipck(hipStreamWaitEvent(c->st, e, 0), "hipStreamWaitEvent");
-    }
-}
-static ExportSrc range_src(svdw_ctx* c, uint32_t phase, int lookup, uint64_t off, uint64_t n) {
-    REQUIRE(phase < 2, "phase must be 0 or 1");
-    REQUIRE(!c->dry, "planning context has no cells");
-    const Stream& s = c->ph[phase];
-    const uint64_t len = lookup ? s.nl : s.n;
-    REQUIRE(off <= len && n <= len - off, "export range outside the stream");
-    return ExportSrc{lookup ? s.lk : s.adv, off, n, 0, 0, 0, 0};
-}
-static ExportSrc view_src(svdw_ctx* c, const svdw_mat& m) {
-    REQUIRE(!c->dry, "planning context has no cells");
-    check_mat(c, m);
-    return ExportSrc{c->ph[m.phase].adv, m.off, (uint64_t)m.rows * m.cols, 0, m.rs, m.cs, m.cols};
-}
-// cells [k0, k0 + cnt) of s
-static ExportSrc sub_src(const ExportSrc& s, uint64_t k0, uint64_t cnt) {
-    ExportSrc r = s;
-    r.n = cnt;
-    if (s.cols) r.k0 = s.k0 + k0;
-    else r.off = s.off + k0;
-    return r;
-}
-// conv(sub, dev): queue the conversion of `sub` into device memory dev on st;
-// esz: bytes per converted cell. Into device memory in one launch; into host
-// memory in chunks through the two staging halves, chunk k + 1's conversion (st)
-// beside chunk k's copy (st2), then waits.
-static void export_run(svdw_ctx* c, const ExportSrc& s, size_t esz, void* dst, bool on_device,
-                       const std::function<void(const ExportSrc&, void*)>& conv) {
-    if (!s.n) return;
-    if (on_device) {
-        export_join(c);
-        conv(s, dst);
-        return;
-    }
-    const uint64_t chunk = kExportChunk / sizeof(Fr);      // cells per half
-    for (int h = 0; h < (s.n > chunk ? 2 : 1); ++h)        // (allocating synchronises: first)
-        ensure_buf(c, c->exp_buf[h], (size_t)std::min(s.n, chunk) * esz);
-    export_join(c);
-    const hipStream_t cp = c->st2 && c->st2 != c->st ? c->st2 : c->st;
-    uint64_t k0 = 0;
-    for (uint64_t i = 0; k0 < s.n; ++i, k0 += chunk) {
-        const int h = (int)(i & 1);
-        const uint64_t cnt = std::min(chunk, s.n - k0);
-        if (i >= 2) hipck(hipStreamWaitEvent(c->st, export_event(c, 2 + h), 0), "hipStreamWaitEvent");
-        conv(sub_src(s, k0, cnt), c->exp_buf[h].p);
-        hipck(hipEventRecord(export_event(c, h), c->st), "hipEventRecord");
-        hipck(hipStreamWaitEvent(cp, export_event(c, h), 0), "hipStreamWaitEvent");
-        hipck(hipMemcpyAsync((char*)dst + k0 * esz, c->exp_buf[h].p, cnt * esz, hipMemcpyDeviceToHost, cp), "D2H");
-        hipck(hipEventRecord(export_event(c, 2 + h), cp), "hipEventRecord");
-    }
-    sync(c);
-}
-static void export_cells_to(svdw_ctx* c, const ExportSrc& s, int form, void* dst, bool on_device) {
-    if (!on_device && form == SVDW_FORM_CANONICAL && !s.cols) {   // straight from the stream
-        if (!s.n) return;
-        export_join(c);
-        hipck(hipMemcpyAsync(dst, s.src + s.off, s.n * sizeof(Fr), hipMemcpyDeviceToHost, c->st), "D2H");
-        sync(c);
-        return;
-    }
-    export_run(c, s, sizeof(Fr), dst, on_device, [&](const ExportSrc& sub, void* dev) {
-        ProfScope ps(c, c->st, form == SVDW_FORM_MONTGOMERY ? "k_export_mont" : "k_export", 64.0 * (double)sub.n, 0);
-        hipck(launch_export(sub, form, (Fr*)dev, 0, c->st), "k_export");
-    });
-}
-static void dequantize_to(svdw_ctx* c, const ExportSrc& s, double* dst, bool on_device) {
-    export_run(c, s, sizeof(double), dst, on_device, [&](const ExportSrc& sub, void* dev) {
-        ProfScope ps(c, c->st, "k_dequantize", 40.0 * (double)sub.n, 0);
-        hipck(launch_dequantize(sub, c->P, (double*)dev, c->st), "k_dequantize");
-    });
-}
-int svdw_export_cells(svdw_ctx* c, uint32_t phase, int lookup, uint64_t off, uint64_t n, int form, void* dst) {
-    return guarded([&] {
-        REQUIRE(c && dst, "null argument");
-        check_form(form);
-        export_cells_to(c, range_src(c, phase, lookup, off, n), form, dst, true);
-    });
-}
-int svdw_copy_cells(svdw_ctx* c, uint32_t phase, int lookup, uint64_t off, uint64_t n, int form, uint64_t* out) {
-    return guarded([&] {
-        REQUIRE(c && out, "null argument");
-        check_form(form);
-        export_cells_to(c, range_src(c, phase, lookup, off, n), form, out, false);
-    });
-}
-int svdw_export_mat(svdw_ctx* c, const svdw_mat* a, int form, void* dst, int on_device) {
-    return guarded([&] {
-        REQUIRE(c && a && dst, "null argument");
-        check_form(form);
-        export_cells_to(c, view_src(c, *a), form, dst, on_device != 0);
-    });
-}
-int svdw_export_vec(svdw_ctx* c, const svdw_vec* v, int form, void* dst, int on_device) {
-    return guarded([&] {
-        REQUIRE(c && v && dst, "null argument");
-        check_form(form);
-        export_cells_to(c, view_src(c, mat_of_vec(*v)), form, dst, on_device != 0);
-    });
-}
-int svdw_dequantize_mat(svdw_ctx* c, const svdw_mat* a, double* out, int on_device) {
-    return guarded([&] {
-        REQUIRE(c && a && out, "null argument");
-        dequantize_to(c, view_src(c, *a), out, on_device != 0);
-    });
-}
-int svdw_dequantize_vec(svdw_ctx* c, const svdw_vec* v, double* out, int on_device) {
-    return guarded([&] {
-        REQUIRE(c && v && out, "null argument");
-        dequantize_to(c, view_src(c, mat_of_vec(*v)), out, on_device != 0);
-    });
-}
-// Host helpers (fr.hpp / export.hpp on the host, no context, no GPU).
-int svdw_fr_convert(const uint64_t* in, uint64_t n, int from, int to, uint64_t* out) {
-    return guarded([&] {
-        REQUIRE(n == 0 || (in && out), "null argument");
-        check_form(from);
-        check_form(to);
-        for (uint64_t i = 0; i < n; ++i)
-            REQUIRE(fr_reduced(fr_raw_words(in + 4 * i)), "svdw_fr_convert: input value >= p");
-        for (uint64_t i = 0; i < n; ++i) {
-            Fr x = fr_raw_words(in + 4 * i);
-            if (from != to) x = to == SVDW_FORM_MONTGOMERY ? fr_to_mont(x) : fr_from_mont(x);
-            fr_store_words(x, out + 4 * i);
-        }
-    });
-}
-int svdw_quantization(double x, uint32_t precision_bits, uint64_t out[4]) {
-    return guarded([&] {
-        REQUIRE(out, "null argument");
-        if (precision_bits < 1 || precision_bits > 63) fail(SVDW_ERANGE, "precision_bits must be in [1, 63]");
-        fr_store_words(quantize_fr(x, ldexp(1.0, (int)precision_bits)), out);
-    });
-}
-int svdw_dequantization(const uint64_t value[4], uint32_t precision_bits, double* out) {
-    return guarded([&] {
-        REQUIRE(value && out, "null argument");
-        if (precision_bits < 1 || precision_bits > 63) fail(SVDW_ERANGE, "precision_bits must be in [1, 63]");
-        const Fr x = fr_raw_words(value);
-        REQUIRE(fr_reduced(x), "svdw_dequantization: value >= p");
-        *out = dequantize_fr(x, precision_bits);
     });
 }
 
@@ -3239,24 +2601,21 @@ int svdw_entries_less_than(svdw_ctx* c, const svdw_vec* d, uint32_t max_bits) {
     return guarded([&] {
         REQUIRE(c && d, "null argument");
         check_vec(c, *d);
-        pregrow(c, [&](svdw_ctx* x) { entries_less_than(x, *d, max_bits); });
-        entries_less_than(c, *d, max_bits);
+        run_sized(c, [&](svdw_ctx* x) { entries_less_than(x, *d, max_bits); });
     });
 }
 int svdw_entries_in_desc_order(svdw_ctx* c, const svdw_vec* d, uint32_t max_bits) {
     return guarded([&] {
         REQUIRE(c && d, "null argument");
         check_vec(c, *d);
-        pregrow(c, [&](svdw_ctx* x) { entries_in_desc_order(x, *d, max_bits); });
-        entries_in_desc_order(c, *d, max_bits);
+        run_sized(c, [&](svdw_ctx* x) { entries_in_desc_order(x, *d, max_bits); });
     });
 }
 int svdw_check_mat_entries_bounded(svdw_ctx* c, const svdw_mat* a, const uint64_t bnd[4]) {
     return guarded([&] {
         REQUIRE(c && a && bnd, "null argument");
         check_mat(c, *a);
-        pregrow(c, [&](svdw_ctx* x) { check_mat_entries_bounded(x, *a, big_from_words(bnd)); });
-        check_mat_entries_bounded(c, *a, big_from_words(bnd));
+        run_sized(c, [&](svdw_ctx* x) { check_mat_entries_bounded(x, *a, big_from_words(bnd)); });
     });
 }
 int svdw_check_mat_diff(svdw_ctx* c, const svdw_mat* a, const svdw_mat* b, const uint64_t tol[4]) {
@@ -3266,12 +2625,10 @@ int svdw_check_mat_diff(svdw_ctx* c, const svdw_mat* a, const svdw_mat* b, const
         check_mat(c, *b);
         REQUIRE(a->rows == b->rows && a->cols == b->cols, "check_mat_diff: shape mismatch");
         REQUIRE(a->phase == b->phase, "check_mat_diff: a and b in different phases");
-        pregrow(c, [&](svdw_ctx* x) {
+        run_sized(c, [&](svdw_ctx* x) {
             check_mat_diff_views(x, a->phase, view_of(x, *a), view_of(x, *b), a->rows, a->cols,
                                  big_from_words(tol));
         });
-        check_mat_diff_views(c, a->phase, view_of(c, *a), view_of(c, *b), a->rows, a->cols,
-                             big_from_words(tol));
     });
 }
 int svdw_check_mat_id(svdw_ctx* c, const svdw_mat* a, const svdw_vec* sid, const uint64_t tol[4]) {
@@ -3279,8 +2636,7 @@ int svdw_check_mat_id(svdw_ctx* c, const svdw_mat* a, const svdw_vec* sid, const
         REQUIRE(c && a && sid && tol, "null argument");
         check_mat(c, *a);
         check_vec(c, *sid);
-        pregrow(c, [&](svdw_ctx* x) { check_mat_id(x, *a, *sid, big_from_words(tol)); });
-        check_mat_id(c, *a, *sid, big_from_words(tol));
+        run_sized(c, [&](svdw_ctx* x) { check_mat_id(x, *a, *sid, big_from_words(tol)); });
     });
 }
 int svdw_mat_times_diag_mat(svdw_ctx* c, const svdw_mat* a, const svdw_vec* v, svdw_mat* out) {
@@ -3288,8 +2644,7 @@ int svdw_mat_times_diag_mat(svdw_ctx* c, const svdw_mat* a, const svdw_vec* v, s
         REQUIRE(c && a && v && out, "null argument");
         check_mat(c, *a);
         check_vec(c, *v);
-        pregrow(c, [&](svdw_ctx* x) { mat_times_diag_mat(x, *a, *v); });
-        *out = mat_times_diag_mat(c, *a, *v);
+        *out = run_sized(c, [&](svdw_ctx* x) { return mat_times_diag_mat(x, *a, *v); });
     });
 }
 int svdw_rescale_matrix(svdw_ctx* c, const svdw_mat* cs, const svdw_div_scale* cfg, svdw_mat* out) {
@@ -3297,8 +2652,7 @@ int svdw_rescale_matrix(svdw_ctx* c, const svdw_mat* cs, const svdw_div_scale* c
         REQUIRE(c && cs && out, "null argument");
         check_mat(c, *cs);
         const DivScale d = div_scale_of(c, cfg);
-        pregrow(c, [&](svdw_ctx* x) { rescale_matrix(x, *cs, d); });
-        *out = rescale_matrix(c, *cs, d);
+        *out = run_sized(c, [&](svdw_ctx* x) { return rescale_matrix(x, *cs, d); });
     });
 }
 int svdw_zkvector_inner_product(svdw_ctx* c, uint32_t phase, const svdw_vec* self, const svdw_vec* x,
@@ -3309,8 +2663,7 @@ int svdw_zkvector_inner_product(svdw_ctx* c, uint32_t phase, const svdw_vec* sel
         check_vec(c, *self);
         check_vec(c, *x);
         const DivScale d = div_scale_of(c, cfg);
-        pregrow(c, [&](svdw_ctx* y) { zkvector_inner_product(y, phase, *self, *x, d); });
-        *out = zkvector_inner_product(c, phase, *self, *x, d);
+        *out = run_sized(c, [&](svdw_ctx* y) { return zkvector_inner_product(y, phase, *self, *x, d); });
     });
 }
 int svdw_zkvector_norm_square(svdw_ctx* c, uint32_t phase, const svdw_vec* self,
@@ -3320,8 +2673,7 @@ int svdw_zkvector_norm_square(svdw_ctx* c, uint32_t phase, const svdw_vec* self,
         REQUIRE(phase < 2, "phase must be 0 or 1");
         check_vec(c, *self);
         const DivScale d = div_scale_of(c, cfg);
-        pregrow(c, [&](svdw_ctx* y) { zkvector_norm_square(y, phase, *self, d); });
-        *out = zkvector_norm_square(c, phase, *self, d);
+        *out = run_sized(c, [&](svdw_ctx* y) { return zkvector_norm_square(y, phase, *self, d); });
     });
 }
 int svdw_zkvector_norm(svdw_ctx* c, uint32_t phase, const svdw_vec* self, const svdw_div_scale* cfg,
@@ -3331,9 +2683,9 @@ int svdw_zkvector_norm(svdw_ctx* c, uint32_t phase, const svdw_vec* self, const 
         REQUIRE(phase < 2, "phase must be 0 or 1");
         check_vec(c, *self);
         const DivScale d = div_scale_of(c, cfg);
-        auto f = [&](svdw_ctx* x) { return qsqrt_vec(x, phase, zkvector_norm_square(x, phase, *self, d), sqrt_bits); };
-        pregrow(c, f);
-        *out = f(c);
+        *out = run_sized(c, [&](svdw_ctx* x) {
+            return qsqrt_vec(x, phase, zkvector_norm_square(x, phase, *self, d), sqrt_bits);
+        });
     });
 }
 int svdw_zkvector_dist(svdw_ctx* c, uint32_t phase, const svdw_vec* self, const svdw_vec* x,
@@ -3344,11 +2696,9 @@ int svdw_zkvector_dist(svdw_ctx* c, uint32_t phase, const svdw_vec* self, const 
         check_vec(c, *self);
         check_vec(c, *x);
         const DivScale d = div_scale_of(c, cfg);
-        auto f = [&](svdw_ctx* y) {
+        *out = run_sized(c, [&](svdw_ctx* y) {
             return qsqrt_vec(y, phase, zkvector_dist_square(y, phase, *self, *x, d), sqrt_bits);
-        };
-        pregrow(c, f);
-        *out = f(c);
+        });
     });
 }
 int svdw_zkvector_dist_square(svdw_ctx* c, uint32_t phase, const svdw_vec* self, const svdw_vec* x,
@@ -3359,8 +2709,7 @@ int svdw_zkvector_dist_square(svdw_ctx* c, uint32_t phase, const svdw_vec* self,
         check_vec(c, *self);
         check_vec(c, *x);
         const DivScale d = div_scale_of(c, cfg);
-        pregrow(c, [&](svdw_ctx* y) { zkvector_dist_square(y, phase, *self, *x, d); });
-        *out = zkvector_dist_square(c, phase, *self, *x, d);
+        *out = run_sized(c, [&](svdw_ctx* y) { return zkvector_dist_square(y, phase, *self, *x, d); });
     });
 }
 int svdw_zkvector_mul(svdw_ctx* c, uint32_t phase, const svdw_vec* self, const svdw_mat* a,
@@ -3371,8 +2720,7 @@ int svdw_zkvector_mul(svdw_ctx* c, uint32_t phase, const svdw_vec* self, const s
         check_vec(c, *self);
         check_mat(c, *a);
         const DivScale d = div_scale_of(c, cfg);
-        pregrow(c, [&](svdw_ctx* y) { zkvector_mul(y, phase, *self, *a, d); });
-        *out = zkvector_mul(c, phase, *self, *a, d);
+        *out = run_sized(c, [&](svdw_ctx* y) { return zkvector_mul(y, phase, *self, *a, d); });
     });
 }
 int svdw_honest_prover_mat_mul(svdw_ctx* c, uint32_t phase, const svdw_mat* a, const svdw_mat* b,
@@ -3395,8 +2743,7 @@ int svdw_field_mat_vec_mul(svdw_ctx* c, uint32_t phase, const svdw_mat* a, const
         REQUIRE(c && a && v && out, "null argument");
         check_mat(c, *a);
         check_vec(c, *v);
-        pregrow(c, [&](svdw_ctx* x) { field_mat_vec_mul(x, phase, *a, *v); });
-        *out = field_mat_vec_mul(c, phase, *a, *v);
+        *out = run_sized(c, [&](svdw_ctx* x) { return field_mat_vec_mul(x, phase, *a, *v); });
     });
 }
 int svdw_verify_mul(svdw_ctx* c, uint32_t phase, const svdw_mat* a, const svdw_mat* b,
@@ -3406,8 +2753,7 @@ int svdw_verify_mul(svdw_ctx* c, uint32_t phase, const svdw_mat* a, const svdw_m
         check_mat(c, *a);
         check_mat(c, *b);
         check_mat(c, *cs);
-        pregrow(c, [&](svdw_ctx* x) { verify_mul(x, phase, *a, *b, *cs, fr_from_words(gamma)); });
-        verify_mul(c, phase, *a, *b, *cs, fr_from_words(gamma));
+        run_sized(c, [&](svdw_ctx* x) { verify_mul(x, phase, *a, *b, *cs, fr_from_words(gamma)); });
     });
 }
 int svdw_err_calc(uint32_t p, uint64_t size, double max_norm, double eps_svd, double eps_u,
@@ -3425,18 +2771,16 @@ int svdw_check_svd_phase0(svdw_ctx* c, const svdw_mat* m, const svdw_mat* u, con
         check_mat(c, *m); check_mat(c, *u); check_mat(c, *v); check_vec(c, *d);
         REQUIRE(m->phase == 0 && u->phase == 0 && v->phase == 0 && d->phase == 0,
                 "check_svd_phase0 inputs must live in phase 0");
-        pregrow(c, [&](svdw_ctx* x) {
-            check_svd_phase0(x, *m, *u, *v, *d, err_svd, err_u, max_bits_d);
+        *out = run_sized(c, [&](svdw_ctx* x) {
+            return check_svd_phase0(x, *m, *u, *v, *d, err_svd, err_u, max_bits_d);
         });
-        *out = check_svd_phase0(c, *m, *u, *v, *d, err_svd, err_u, max_bits_d);
     });
 }
 int svdw_check_svd_phase1(svdw_ctx* c, const svdw_mat* m, const svdw_mat* u, const svdw_mat* v,
                           const svdw_svd_payload* pl, const uint64_t gamma[4]) {
     return guarded([&] {
         REQUIRE(c && m && u && v && pl && gamma, "null argument");
-        pregrow(c, [&](svdw_ctx* x) { check_svd_phase1(x, *m, *u, *v, *pl, fr_from_words(gamma)); });
-        check_svd_phase1(c, *m, *u, *v, *pl, fr_from_words(gamma));
+        run_sized(c, [&](svdw_ctx* x) { check_svd_phase1(x, *m, *u, *v, *pl, fr_from_words(gamma)); });
     });
 }
 int svdw_svd_witness(svdw_ctx* c, const double* m, const double* u, const double* v,
@@ -3466,304 +2810,6 @@ int svdw_verify_mul_witness_on(svdw_ctx* c, void* stream, const double* a, const
         svdw_counts k = verify_mul_witness_api(c, a, b, N, K, M, true, fr_from_words(gamma), (hipStream_t)stream,
                                                true);
         if (counts) *counts = k;
-    });
-}
-int svdw_parse_svd_input(const char* text, uint64_t len, int mode, svdw_input_dims* dims,
-                         double* m, double* u, double* d, double* v) {
-    return guarded([&] {
-        REQUIRE(text && dims, "null argument");
-        REQUIRE(mode == SVDW_PARSE_SERDE || mode == SVDW_PARSE_CORRECT, "parse mode: 0 or 1");
-        svdw_ingest::SvdInput in;
-        std::string err;
-        svdw_ingest::Parser ps(text, len, mode);
-        if (!ps.parse(in, err)) fail(SVDW_EINVAL, "svd input: " + err);
-        REQUIRE(in.d.rows == 0 && in.m.rows && in.u.rows && in.v.rows,
-                "svd input: m, u, v must be matrices and d a vector");
-        *dims = svdw_input_dims{in.m.rows, in.m.cols, in.u.rows, in.u.cols, in.v.rows, in.v.cols,
-                                in.d.cols};
-        const std::pair<double*, const svdw_ingest::Array*> outs[4] = {
-            {m, &in.m}, {u, &in.u}, {d, &in.d}, {v, &in.v}};
-        for (const auto& o : outs)
-            if (o.first) memcpy(o.first, o.second->v.data(), o.second->v.size() * sizeof(double));
-    });
-}
-// Device ingest of data/matrix.in (ingest_dev.hip): three passes over the text
-// on the device, then the few top-level keys and the arrays' number ranges on
-// the host (small reads), then a device check of depths, separators and row
-// lengths of m, u, v, d and device-to-device copies of their values.
-namespace {
-struct DevText {                  // small host reads of the device text
-    svdw_ctx* c;
-    const uint8_t* t;
-    uint64_t n;
-    std::vector<uint8_t> get(uint64_t at, uint64_t len) {
-        len = std::min(len, at < n ? n - at : 0);
-        std::vector<uint8_t> b(len);
-        if (len) hipck(hipMemcpy(b.data(), t + at, len, hipMemcpyDeviceToHost), "D2H");
-        return b;
-    }
-    // the string starting with the quote at `at`: its content (escapes as the
-    // host parser reads them) and the position just past the closing quote
-    bool str(uint64_t at, std::string* s, uint64_t* end) {
-        uint64_t p = at + 1;
-        bool esc = false;
-        for (;;) {
-            std::vector<uint8_t> b = get(p, 256);
-            if (b.empty()) return false;
-            for (size_t k = 0; k < b.size(); ++k, ++p) {
-                if (esc) { s->push_back((char)b[k]); esc = false; continue; }
-                if (b[k] == '\\') { esc = true; continue; }
-                if (b[k] == '"') { *end = p + 1; return true; }
-                s->push_back((char)b[k]);
-            }
-        }
-    }
-    int next_nonws(uint64_t at) {
-        for (;;) {
-            std::vector<uint8_t> b = get(at, 256);
-            if (b.empty()) return -1;
-            for (uint8_t x : b)
-                if (!(x == ' ' || x == '\n' || x == '\r' || x == '\t')) return x;
-            at += b.size();
-        }
-    }
-};
-}  // namespace
-int svdw_parse_svd_input_device(svdw_ctx* c, const void* text, uint64_t len, int mode,
-                                svdw_input_dims* dims, double* m, double* u, double* d, double* v) {
-    namespace ig = svdw_ingest_dev;
-    return guarded([&] {
-        REQUIRE(c && text && dims, "null argument");
-        need_device(c, "device ingest");
-        REQUIRE(mode == SVDW_PARSE_SERDE,
-                "device ingest: serde mode only (correct rounding: svdw_parse_svd_input)");
-        REQUIRE(len > 0, "svd input: empty text");
-        const uint8_t* t = (const uint8_t*)text;
-        const uint64_t nc64 = (len + ig::kChunk - 1) / ig::kChunk;
-        REQUIRE(nc64 < (1ull << 31), "svd input: text too large");
-        const uint32_t nc = (uint32_t)nc64;
-        hipStream_t s = c->st;
-        sync(c);
-        if (!c->ing_p10.p) {                       // serde's POW10 table (correctly rounded 10^k)
-            std::vector<double> p10(309);
-            char buf[16];
-            for (int i = 0; i <= 308; ++i) { snprintf(buf, sizeof buf, "1e%d", i); p10[i] = strtod(buf, nullptr); }
-            ensure_buf(c, c->ing_p10, sizeof(double) * 309);
-            // on st, complete before p10 goes out of scope (a null-stream copy
-            // is not ordered against the parse launches on st)
-            hipck(hipMemcpyAsync(c->ing_p10.p, p10.data(), sizeof(double) * 309, hipMemcpyHostToDevice, s), "H2D");
-            hipck(hipStreamSynchronize(s), "hipStreamSynchronize");
-        }
-        ensure_buf(c, c->ing_x, sizeof(ig::Xfer) * nc);
-        ensure_buf(c, c->ing_e, sizeof(ig::Entry) * (nc + 1));
-        ensure_buf(c, c->ing_c, sizeof(ig::Counts) * (nc + 1));
-        ig::Xfer* X = (ig::Xfer*)c->ing_x.p;
-        ig::Entry* E = (ig::Entry*)c->ing_e.p;
-        ig::Counts* C = (ig::Counts*)c->ing_c.p;
-        hipck(ig::launch_pass1(t, len, X, s), "ingest pass 1");
-        hipck(ig::launch_scan1(X, nc, E, s), "ingest scan 1");
-        hipck(ig::launch_pass2(t, len, E, C, s), "ingest pass 2");
-        hipck(ig::launch_scan2(C, nc, s), "ingest scan 2");
-        ig::Entry fin;
-        ig::Counts tot;
-        hipck(hipMemcpyAsync(&fin, E + nc, sizeof fin, hipMemcpyDeviceToHost, s), "D2H");
-        hipck(hipMemcpyAsync(&tot, C + nc, sizeof tot, hipMemcpyDeviceToHost, s), "D2H");
-        hipck(hipStreamSynchronize(s), "hipStreamSynchronize");
-        REQUIRE(fin.state == 0, "svd input: unterminated string");
-        REQUIRE(fin.depth == 0, "svd input: unbalanced brackets");
-        const uint32_t nn = tot.num, nr = tot.row, nk = tot.key;
-        ensure_buf(c, c->ing_val, sizeof(double) * std::max(nn, 1u));
-        ensure_buf(c, c->ing_npos, sizeof(uint64_t) * std::max(nn, 1u));
-        ensure_buf(c, c->ing_nd, std::max(nn, 1u));
-        ensure_buf(c, c->ing_rpos, sizeof(uint64_t) * std::max(nr, 1u));
-        ensure_buf(c, c->ing_kpos, sizeof(uint64_t) * std::max(nk, 1u));
-        ensure_buf(c, c->ing_err, sizeof(uint64_t) * 264);
-        unsigned long long* slist = (unsigned long long*)c->ing_err.p;          // [0] count, [1..255]
-        unsigned long long* verr = slist + 256;
-        hipck(hipMemsetAsync(slist, 0, sizeof(uint64_t), s), "memset");
-        hipck(hipMemsetAsync(verr, 0xff, sizeof(uint64_t), s), "memset");
-        hipck(ig::launch_pass3(t, len, E, C, (const double*)c->ing_p10.p, (double*)c->ing_val.p,
-                               (uint64_t*)c->ing_npos.p, (uint8_t*)c->ing_nd.p, (uint64_t*)c->ing_rpos.p,
-                               (uint64_t*)c->ing_kpos.p, slist, s), "ingest pass 3");
-        std::vector<uint64_t> kpos(nk), sl(256);
-        if (nk) hipck(hipMemcpyAsync(kpos.data(), c->ing_kpos.p, sizeof(uint64_t) * nk, hipMemcpyDeviceToHost, s), "D2H");
-        hipck(hipMemcpyAsync(sl.data(), slist, sizeof(uint64_t) * 256, hipMemcpyDeviceToHost, s), "D2H");
-        hipck(hipStreamSynchronize(s), "hipStreamSynchronize");
-        auto at = [](uint64_t p) { return " (at byte " + std::to_string(p) + ")"; };
-        // members: depth-1 strings followed by ':' are keys (host parser: str, ws, ':')
-        DevText dt{c, t, len};
-        struct Member { uint64_t pos; std::string key; };
-        std::vector<Member> mem;
-        for (uint32_t j = 0; j < nk; ++j) {
-            std::string k;
-            uint64_t end = 0;
-            REQUIRE(dt.str(kpos[j], &k, &end), "svd input: unterminated string" + at(kpos[j]));
-            const int nx = dt.next_nonws(end);
-            // a key follows '{' or ','; a string value follows ':' and is not followed by ':'
-            std::vector<uint8_t> back = dt.get(kpos[j] >= 256 ? kpos[j] - 256 : 0, kpos[j] >= 256 ? 256 : kpos[j]);
-            int pv = 0;
-            for (size_t q = back.size(); q-- > 0;)
-                if (!(back[q] == ' ' || back[q] == '\n' || back[q] == '\r' || back[q] == '\t')) { pv = back[q]; break; }
-            if (pv == ':') {
-                REQUIRE(nx != ':', "svd input: expected ',' or '}'" + at(end));
-                continue;
-            }
-            REQUIRE(nx == ':', "svd input: expected ':'" + at(end));
-            mem.push_back({kpos[j], k});
-        }
-        const uint64_t nsl = sl[0];
-        REQUIRE(nsl <= 255, "svd input: too many structural irregularities for the device parser");
-        for (const char* want : {"m", "u", "v", "d"}) {
-            int cnt = 0;
-            for (const auto& x : mem) cnt += x.key == want;
-            REQUIRE(cnt <= 1, std::string("svd input: duplicate key \"") + want + "\"");
-            REQUIRE(cnt == 1, "svd input: missing one of the keys m, u, v, d");
-        }
-        // number / row-open ranges of every member
-        std::vector<uint64_t> q;
-        for (const auto& x : mem) q.push_back(x.pos);
-        q.push_back(len);
-        ensure_buf(c, c->ing_q, (sizeof(uint64_t) + 2 * sizeof(uint32_t)) * q.size());
-        uint32_t* rg = (uint32_t*)((uint64_t*)c->ing_q.p + q.size());
-        hipck(hipMemcpyAsync(c->ing_q.p, q.data(), sizeof(uint64_t) * q.size(), hipMemcpyHostToDevice, s), "H2D");
-        hipck(ig::launch_ranges((const uint64_t*)c->ing_npos.p, nn, (const uint64_t*)c->ing_rpos.p, nr,
-                                (const uint64_t*)c->ing_q.p, (uint32_t)q.size(), rg, s), "ingest ranges");
-        std::vector<uint32_t> r(2 * q.size());
-        hipck(hipMemcpyAsync(r.data(), rg, sizeof(uint32_t) * r.size(), hipMemcpyDeviceToHost, s), "D2H");
-        hipck(hipStreamSynchronize(s), "hipStreamSynchronize");
-        for (uint64_t k = 0; k < nsl; ++k) {       // structural errors: object level, or inside m/u/v/d
-            const uint64_t p = sl[1 + k] & ~(1ull << 63);
-            REQUIRE(!(sl[1 + k] >> 63), "svd input: malformed JSON object" + at(p));
-            for (size_t j = 0; j < mem.size(); ++j) {
-                const bool known = mem[j].key == "m" || mem[j].key == "u" || mem[j].key == "v" || mem[j].key == "d";
-                REQUIRE(!(known && p >= q[j] && p < q[j + 1]), "svd input: malformed array" + at(p));
-            }
-        }
-        struct Arr { uint32_t lo, hi, r0, rows, cols; };
-        auto arr = [&](const char* key, bool matrix) {
-            size_t j = 0;
-            while (mem[j].key != key) ++j;
-            Arr a{r[2 * j], r[2 * j + 2], r[2 * j + 1], r[2 * j + 3] - r[2 * j + 1], 0};
-            const uint32_t total = a.hi - a.lo;
-            if (matrix) {
-                REQUIRE(a.rows >= 1, "svd input: m, u, v must be matrices and d a vector");
-                REQUIRE(total % a.rows == 0, std::string("svd input: ragged matrix rows (") + key + ")");
-                a.cols = total / a.rows;
-            } else {
-                REQUIRE(a.rows == 0, "svd input: m, u, v must be matrices and d a vector");
-                a.cols = total;
-            }
-            hipck(ig::launch_validate((const uint8_t*)c->ing_nd.p, a.lo, a.hi, matrix ? 3 : 2,
-                                      (const uint64_t*)c->ing_npos.p, nn, (const uint64_t*)c->ing_rpos.p,
-                                      a.r0, a.rows, a.cols, verr, s), "ingest validate");
-            return a;
-        };
-        const Arr am = arr("m", true), au = arr("u", true), av = arr("v", true), ad = arr("d", false);
-        unsigned long long ve = 0;
-        hipck(hipMemcpyAsync(&ve, verr, sizeof ve, hipMemcpyDeviceToHost, s), "D2H");
-        hipck(hipStreamSynchronize(s), "hipStreamSynchronize");
-        if (ve != ~0ull) {
-            static const char* what[] = {"", "expected a number", "significand beyond u64 (serde's overflow path is not emulated)",
-                                         "number out of range", "expected ',' or ']'", "unexpected nesting",
-                                         "ragged matrix rows"};
-            const uint32_t code = (uint32_t)(ve >> 48);
-            fail(SVDW_EINVAL, std::string("svd input: ") + (code < 7 ? what[code] : "malformed") +
-                              at(ve & ((1ull << 48) - 1)));
-        }
-        *dims = svdw_input_dims{am.rows, am.cols, au.rows, au.cols, av.rows, av.cols, ad.cols};
-        const std::pair<double*, const Arr*> outs[4] = {{m, &am}, {u, &au}, {d, &ad}, {v, &av}};
-        for (const auto& o : outs)
-            if (o.first && o.second->hi > o.second->lo)
-                hipck(hipMemcpyAsync(o.first, (const double*)c->ing_val.p + o.second->lo,
-                                     sizeof(double) * (o.second->hi - o.second->lo), hipMemcpyDeviceToDevice, s),
-                      "D2D");
-        hipck(hipStreamSynchronize(s), "hipStreamSynchronize");
-    });
-}
-int svdw_set_shard(svdw_ctx* c, uint32_t rank, uint32_t world) {
-    return guarded([&] {
-        REQUIRE(c, "null ctx");
-        REQUIRE(world >= 1 && rank < world, "svdw_set_shard: need rank < world");
-        ++c->epoch;
-        c->opt.shard_rank = rank;
-        c->opt.shard_world = world;
-        c->owned.clear();
-    });
-}
-int svdw_abi_version(void) { return SVDW_ABI_VERSION; }
-int svdw_set_option(svdw_ctx* c, const char* name, int64_t value) {
-    return guarded([&] {
-        REQUIRE(c && name, "null argument");
-        sync(c);
-        ++c->epoch;                                  // a captured launch sequence may change
-        for (const OptionDef& o : kOptions)
-            if (!strcmp(o.name, name)) {
-                REQUIRE(value >= o.lo && value <= o.hi, o.msg);
-                return o.set(c, value);
-            }
-        fail(SVDW_EINVAL, std::string("unknown option ") + name);
-    });
-}
-int svdw_graph_stats(svdw_ctx* c, uint64_t* captures, uint64_t* replays) {
-    return guarded([&] {
-        REQUIRE(c && captures && replays, "null argument");
-        *captures = c->vmg.captures + (c->lane ? c->lane->vmg.captures : 0);
-        *replays = c->vmg.replays + (c->lane ? c->lane->vmg.replays : 0);
-    });
-}
-int svdw_set_gemm_impl(svdw_ctx* c, int impl) {
-    return guarded([&] {
-        REQUIRE(c, "null ctx");
-        REQUIRE(impl == SVDW_GEMM_MFMA || impl == SVDW_GEMM_VALU, "unknown GEMM implementation");
-        sync(c);
-        ++c->epoch;
-        c->opt.gemm_impl = impl;
-    });
-}
-int svdw_profile_enable(svdw_ctx* c, int on) {
-    return guarded([&] {
-        REQUIRE(c, "null ctx");
-        sync(c);
-        for (auto& r : c->recs) { c->pool.push_back(r.e0); c->pool.push_back(r.e1); }
-        c->recs.clear();
-        c->opt.prof = on != 0;
-    });
-}
-int svdw_profile_filter(svdw_ctx* c, const char* prefix) {
-    return guarded([&] {
-        REQUIRE(c, "null ctx");
-        c->opt.prof_filter = prefix ? prefix : "";
-    });
-}
-int svdw_profile_collect(svdw_ctx* c, svdw_kstat* out, uint32_t cap, uint32_t* n) {
-    return guarded([&] {
-        REQUIRE(c && n, "null argument");
-        sync(c);
-        std::vector<svdw_kstat> agg;
-        for (auto& r : c->recs) {
-            float ms = 0;
-            hipck(hipEventElapsedTime(&ms, r.e0, r.e1), "hipEventElapsedTime");
-            svdw_kstat* s = nullptr;
-            for (auto& x : agg)
-                if (r.name == x.name) s = &x;
-            if (!s) {
-                agg.emplace_back();
-                s = &agg.back();
-                memset(s, 0, sizeof(*s));
-                snprintf(s->name, sizeof(s->name), "%s", r.name.c_str());
-            }
-            s->launches += 1;
-            s->total_ms += ms;
-            s->bytes += r.bytes;
-            s->ops += r.ops;
-            if (ms > s->max_ms) s->max_ms = ms;
-            c->pool.push_back(r.e0);
-            c->pool.push_back(r.e1);
-        }
-        c->recs.clear();
-        *n = (uint32_t)agg.size();
-        if (out)
-            for (uint32_t i = 0; i < agg.size() && i < cap; ++i) out[i] = agg[i];
     });
 }
 int svdw_plan_svd(uint32_t N, uint32_t M, uint32_t p, uint32_t lb, const svdw_svd_config* cfg,

@@ -1,13 +1,16 @@
-// What engine.cpp (the witness engine), gemm.cpp (the exact field product),
-// circuit.cpp (the assigned-witness calls) and prover.cpp (the prover calls)
-// share: the C ABI's error plumbing, device buffers, the entries' host Fr
-// helpers, the two families' state, the context (svdw_ctx), the functions that
-// cross a file boundary, the staged call.
+// What the host files share: engine.cpp (the witness engine), context.cpp (the
+// context's lifetime, lanes, options, stream hand-off, marks, profiling),
+// export.cpp (read-out), ingest.cpp (text ingest), gemm.cpp (the exact field
+// product), circuit.cpp (the assigned-witness calls) and prover.cpp (the prover
+// calls). In order: the C ABI's error plumbing, device buffers, the entries'
+// host Fr helpers, each family's state, the host record of a witness, the
+// context (svdw_ctx), the functions that cross a file boundary, the staged call.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
 #include <array>
 #include <chrono>
 #include <functional>
@@ -118,6 +121,78 @@ struct ProverState {
         return v;
     }
 };
+#pragma GCC visibility push(hidden)
+// Read-out (export.cpp: svdw_copy_cells, the host variants of svdw_export_* /
+// svdw_dequantize_*): two staging halves of at most kExportChunk bytes each, and
+// the events that order them ([0..1] half converted, [2..3] half copied out,
+// [4..5] the join of st2 / st3 into st ahead of every read-out).
+struct ExportState {
+    DBuf half[2];
+    hipEvent_t ev[6] = {};
+    std::vector<DBuf*> dbufs() { return {&half[0], &half[1]}; }
+};
+// The scratch of the device ingest (ingest.cpp, svdw_parse_svd_input_device).
+struct IngestState {
+    DBuf xfer, entry, counts;               // per chunk of text: its transfer, entry state and counts (passes 1, 2)
+    DBuf pow10;                             // serde's table of 10^k, written once
+    DBuf values, num_pos, num_depth;        // per number: its f64 value, byte position and bracket depth (pass 3)
+    DBuf row_pos, key_pos;                  // the byte positions of the row opens and of the depth-1 strings
+    DBuf errors;                            // the structural-error list ([0] count, [1..255]) and the validation word
+    DBuf queries;                           // the members' positions and the number / row ranges found for them
+    std::vector<DBuf*> dbufs() {
+        return {&xfer, &entry, &counts, &pow10, &values, &num_pos, &num_depth, &row_pos, &key_pos, &errors, &queries};
+    }
+};
+
+// ------------------------------------------- the host record of a witness
+// What a witness call leaves on the host about the cells it appended: the calls
+// on a finished witness (circuit.cpp) and the row scans read it, and a replay of
+// the captured verify_mul_witness puts it back as a whole (VmGraph::rec). The
+// members are listed here and in clear() only.
+struct WitnessRecord {
+    std::vector<svdw_region> layout;        // every appended region of the current witness
+    // per region: gate offsets within one element's cells and cells per element
+    // (program regions; empty otherwise; svdw_check_gates)
+    std::vector<RegionChecks> layout_chk;
+    // distinct constant cell values (halo2-base Constant / load_constant):
+    // the fixed-column count of svdw_physical_layout
+    std::set<std::array<uint32_t, 8>> consts;
+    // (layout_chk index, eqk slot) of the constants that hold gamma (the
+    // verify_mul gamma powers' init_rand), patched on replay
+    std::vector<std::pair<size_t, int>> gamma_slots;
+    // Known magnitude bounds of matrices written in this witness: cell (i, j) of
+    // `m` satisfies |signed value| < 2^bits.
+    struct MatBits { svdw_mat m; uint32_t bits; };
+    std::vector<MatBits> mbits;
+    // products c_s = a * b (K = 2^lk-bounded inner dimension): |c_s| < 2^(bits_a + bits_b + lk)
+    struct Prod { svdw_mat cs, a, b; uint32_t lk; };
+    std::vector<Prod> prods;
+    // Device bit-length words of matrices written in this witness (svd_witness:
+    // quantized m, u, v at dbitw[0..2]): the row scans decide their operand
+    // width on the device from these (NaSpec), so the host never waits for them.
+    struct DevBits { svdw_mat m; int16_t word; };
+    std::vector<DevBits> dwords;
+    const unsigned* dbitw = nullptr;
+    uint64_t ext_off = 0;                   // the cell of the last verify_mul's init_rand in the RLC context
+    // Empties the members in place, as copy-assignment refills them in place: a
+    // witness call allocates nothing here once the containers have grown (begin_call).
+    void clear() {
+        layout.clear();
+        layout_chk.clear();
+        consts.clear();
+        gamma_slots.clear();
+        mbits.clear();
+        prods.clear();
+        dwords.clear();
+        dbitw = nullptr;
+        ext_off = 0;
+    }
+    // The constants that hold gamma take the gamma of a replayed call.
+    void patch_gamma(const Fr& gamma) {
+        for (const auto& s : gamma_slots) layout_chk.at(s.first).eqk.at((size_t)s.second) = gamma;
+    }
+};
+#pragma GCC visibility pop
 
 // -------------------------------------------------------------- context
 struct Stream {
@@ -292,19 +367,7 @@ struct svdw_ctx {
     uint32_t gp_len = 0;
     hipEvent_t gp_ev = nullptr;
     hipStream_t gp_st = nullptr;            // the stream gp_ev was recorded on
-    // Device bit-length words of matrices written in this witness (svd_witness:
-    // quantized m, u, v at dbitw[0..2]): the row scans decide their operand
-    // width on the device from these (NaSpec), so the host never waits for them.
-    struct DevBits { svdw_mat m; int16_t word; };
-    std::vector<DevBits> dwords;
-    const unsigned* dbitw = nullptr;
-    // Known magnitude bounds of matrices written in this witness: cell (i, j) of
-    // `m` satisfies |signed value| < 2^bits. Cleared with the streams.
-    struct MatBits { svdw_mat m; uint32_t bits; };
-    std::vector<MatBits> mbits;
-    // products c_s = a * b (K = 2^lk-bounded inner dimension): |c_s| < 2^(bits_a + bits_b + lk)
-    struct Prod { svdw_mat cs, a, b; uint32_t lk; };
-    std::vector<Prod> prods;
+    WitnessRecord wit;                      // the host record of the current witness: cleared with the streams
     // svd_witness: bit lengths of quantized m, u, v travel to pinned host memory
     // behind ev_bits; the host waits for them only where the GEMM launches need
     // them (fetch_bits), with check stages already queued on the device.
@@ -323,8 +386,7 @@ struct svdw_ctx {
     std::vector<hipEvent_t> pool;
     hipStream_t stream_id[3] = {};          // st, st2, st3 as created (st / st2 / st3 are swapped at times)
     bool gemm_solo = false;                 // svdw_honest_prover_mat_mul: a product queued on its own (gemm_kern)
-    Fr ext_gamma{};                          // init_rand of the last verify_mul (equality source 2)
-    uint64_t ext_off = 0;                    // its cell in the RLC context
+    Fr ext_gamma{};                          // init_rand of the last verify_mul (equality source 2; its cell: wit.ext_off)
     // ctx_rlc of the last svd_witness with rlc_prefix: [E(one), E(zero), W(gamma)]
     // and the phase-1 offsets of the two ctx_gate constants its first cells copy
     struct RlcTrace {
@@ -356,13 +418,6 @@ struct svdw_ctx {
         uint8_t used[kMarks] = {};
         uint64_t seq = 0;
     } mk;
-    std::vector<svdw_region> layout;        // every appended region of the current witness
-    // per region: gate offsets within one element's cells and cells per element
-    // (program regions; empty otherwise; svdw_check_gates)
-    std::vector<RegionChecks> layout_chk;
-    // distinct constant cell values (halo2-base Constant / load_constant):
-    // the fixed-column count of svdw_physical_layout
-    std::set<std::array<uint32_t, 8>> consts;
     // svdw_physical_layout's plan: per phase, the virtual index of each advice
     // column's row 0 and each full column's break point
     struct Phys {
@@ -396,17 +451,11 @@ struct svdw_ctx {
         size_t last = 0;                   // group of the latest stage
     };
     std::vector<Batch> batches;
-    // device ingest (svdw_parse_svd_input_device) scratch
-    DBuf ing_x, ing_e, ing_c, ing_p10, ing_val, ing_npos, ing_nd, ing_rpos, ing_kpos, ing_err, ing_q;
-    // read-out (svdw_copy_cells, the host variants of svdw_export_* / svdw_dequantize_*):
-    // two staging halves of at most kExportChunk bytes each, and the events that
-    // order them ([0..1] half converted, [2..3] half copied out, [4..5] the join
-    // of st2 / st3 into st ahead of every read-out)
-    DBuf exp_buf[2];
     StagedScratch staging;                  // every staged call's scratch (circuit.cpp, prover.cpp)
     CircuitState circuit;                   // the assigned-witness calls (circuit.cpp)
     ProverState prover;                     // the prover calls (prover.cpp)
-    hipEvent_t exp_ev[6] = {};
+    ExportState exp;                        // read-out (export.cpp)
+    IngestState ingest;                     // the device ingest (ingest.cpp)
     // ---- captured verify_mul_witness ("graph", vm_graph): the launch sequence of
     // a device-input call is captured once into a HIP graph (the second call of
     // a shape, when every buffer is sized) and replayed by later calls of the
@@ -414,33 +463,27 @@ struct svdw_ctx {
     // ahead of the graph (gp_external), so the graph itself is gamma-free.
     hipEvent_t lin_ev = nullptr;            // "vm_linear": stream_dep's placeholder (call.linear)
     uint64_t epoch = 0;                     // bumped by every allocation / option change
-    // (layout_chk index, eqk slot) of the constants that hold gamma (the
-    // verify_mul gamma powers' init_rand), patched on replay
-    std::vector<std::pair<size_t, int>> gamma_slots;
     struct VmGraph {
         std::vector<uint64_t> key, seen;    // replay key; the last eager call's key
         hipGraphExec_t exec = nullptr;
-        // host state the captured call left behind (restored on replay)
-        std::vector<svdw_region> layout;
-        std::vector<RegionChecks> layout_chk;
-        std::set<std::array<uint32_t, 8>> consts;
-        std::vector<std::pair<size_t, int>> gamma_slots;
-        std::vector<MatBits> mbits;
-        std::vector<Prod> prods;
-        std::vector<DevBits> dwords;
-        const unsigned* dbitw = nullptr;
-        uint64_t ext_off = 0;
+        WitnessRecord rec;                  // the record the captured call left behind (restored on replay)
         svdw_counts counts{};
         uint64_t replays = 0, captures = 0;
     } vmg;
 };
 
-// engine.cpp's functions that the other files call too, and gemm.cpp's that
-// engine.cpp calls (the library exports only the C ABI).
+// The functions that cross a file boundary (the library exports only the C ABI).
 #pragma GCC visibility push(hidden)
+// ---- context.cpp
 void sync(svdw_ctx* c);                                    // every stream of the context has run dry
 void settle(svdw_ctx* c);                                  // st waits for the tail of a pipelined svd_witness
 void ensure_buf(svdw_ctx* c, DBuf& b, size_t bytes);
+void release_alt(svdw_ctx* c);                             // frees the pipeline's other cell set
+void clear_streams(svdw_ctx* c);                           // empty streams, an empty witness record
+bool lane_fits(svdw_ctx* c);                               // "lanes": the next call may run on the other state
+void lane_switch(svdw_ctx* c);                             // "lanes": exchanges this state with the lane's
+hipEvent_t xevent(svdw_ctx* c, int i);                     // the i-th hand-off event of a state, made on first use
+// ---- engine.cpp
 void flush_batch(svdw_ctx* c, hipStream_t s, hipStream_t waiter = nullptr, hipEvent_t then_wait = nullptr);
 DView view_of(svdw_ctx* c, const svdw_mat& m);             // the cells of m as a kernel's operand
 // ---- gemm.cpp: the exact field product c_s = a * b
@@ -466,6 +509,31 @@ void svd_products_f64(svdw_ctx* c, const svdw_mat (&A)[3], const svdw_mat (&B)[3
 // verify_mul_witness's product from its f64 inputs
 void product_f64(svdw_ctx* c, hipStream_t s, const double* a, const double* b, uint32_t N, uint32_t K, uint32_t M,
                  Fr* out, const unsigned* dbits);
+// ---- small helpers that more than one file needs
+// Device bytes held by a set of cell streams (both phases, advice + lookups).
+inline double set_bytes(const Stream (&s)[2]) {
+    return 32.0 * (double)(s[0].cap + s[0].lcap + s[1].cap + s[1].lcap);
+}
+// The captured verify_mul_witness (engine.cpp) no longer applies.
+inline void vmg_drop(svdw_ctx* c) {
+    if (c->vmg.exec) (void)hipGraphExecDestroy(c->vmg.exec);
+    c->vmg.exec = nullptr;
+    c->vmg.key.clear();
+}
+inline svdw_mat mat_of_vec(const svdw_vec& v) {   // len x 1 column
+    return svdw_mat{v.phase, v.len, 1, v.off, v.stride, 0};
+}
+inline void check_mat(const svdw_ctx* c, const svdw_mat& m) {
+    REQUIRE(m.phase < 2, "matrix phase must be 0 or 1");
+    REQUIRE(m.rows >= 1 && m.cols >= 1, "empty matrix");
+    // every referenced cell must already exist
+    int64_t lo = (int64_t)m.off, hi = (int64_t)m.off;
+    int64_t er = (int64_t)(m.rows - 1) * m.rs, ec = (int64_t)(m.cols - 1) * m.cs;
+    lo += std::min<int64_t>(er, 0) + std::min<int64_t>(ec, 0);
+    hi += std::max<int64_t>(er, 0) + std::max<int64_t>(ec, 0);
+    REQUIRE(lo >= 0 && (uint64_t)hi < c->ph[m.phase].n, "matrix view outside its phase stream");
+}
+inline void check_vec(const svdw_ctx* c, const svdw_vec& v) { check_mat(c, mat_of_vec(v)); }
 #pragma GCC visibility pop
 inline bool sharded(const svdw_ctx* c) { return c->opt.shard_world > 1; }
 // rows of a row-parallel stage (R rows) that this rank computes / owns
@@ -485,7 +553,6 @@ inline uint32_t clog2(uint32_t k) {                        // least l with 2^l >
 inline uint32_t ceil_to(uint32_t x, uint32_t a) { return (x + a - 1) / a * a; }
 // The check every device entry makes, under the entry's name f.
 inline void need_device(const svdw_ctx* c, const std::string& f) { REQUIRE(!c->dry, f + " needs a device context"); }
-
 // RAII: brackets one kernel launch with HIP events on the context stream.
 struct ProfScope {
     svdw_ctx* c;

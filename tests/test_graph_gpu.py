@@ -107,6 +107,60 @@ def test_graph_off_and_invalidation(gpu_ctx_factory):
     assert on.graph_stats() == (3, 4)
 
 
+def _smallest_k(ctx):
+    """The smallest k at which physical_layout and the permutation argument's
+    layout both accept the context's witness."""
+    import halo2_svd041_amd as hs
+    for k in range(3, 29):
+        try:
+            ctx.physical_layout(k)
+            ctx.permutation_layout()
+        except hs.SvdwError:
+            continue
+        return k
+    raise AssertionError("no k accepts the witness")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape,other", [((64, 40, 50), (3, 2, 1)), ((3, 2, 1), (64, 40, 50))])
+def test_graph_replay_restores_witness_record(gpu_ctx_factory, shape, other):
+    """After a replay, every call on the finished witness sees the record an eager
+    call leaves (test_graph_off_and_invalidation's set-up; the checker calls are
+    here because their scratch bumps the epoch, which would shift its counts):
+    layout, the equality records of both phases, the physical layout at the
+    smallest k that accepts the witness, and the permutation argument's edges
+    equal those of a graph-off context. A call of another shape and one back
+    still match the C oracle."""
+    import torch
+    import halo2_svd041_amd as hs
+    P = 32
+    a, b = _mats(*shape, seed=9)
+    ta, tb = (torch.tensor(x, dtype=torch.float64, device="cuda:0") for x in (a, b))
+    on, off = gpu_ctx_factory(P), gpu_ctx_factory(P)
+    for x in (on, off):
+        x.set_option("lanes", 1)
+    off.set_option("graph", 0)
+    for it in range(4):
+        g = gamma_for(40 + it)
+        hs.verify_mul_witness(on, ta, tb, g)
+        hs.verify_mul_witness(off, ta, tb, g)
+    assert on.graph_stats() == (1, 2) and off.graph_stats() == (0, 0)   # (the last call of `on` was a replay)
+    assert on.layout() == off.layout()
+    for ph in (0, 1):
+        eq = on.check_equalities(ph)
+        assert eq == off.check_equalities(ph) and eq["copy_failures"] == 0 and eq["const_failures"] == 0
+    k = _smallest_k(off)
+    assert on.physical_layout(k) == off.physical_layout(k)
+    (e_on, lay_on), (e_off, lay_off) = on.permutation_edges(), off.permutation_edges()
+    assert lay_on == lay_off and lay_on["edges"] > 0 and torch.equal(e_on, e_off)
+    a2, b2 = _mats(*other, seed=3)                        # another shape, then back
+    t2a, t2b = (torch.tensor(x, dtype=torch.float64, device="cuda:0") for x in (a2, b2))
+    hs.verify_mul_witness(on, t2a, t2b, gamma_for(60))
+    _check_all(on, a2, b2, P, gamma_for(60))
+    hs.verify_mul_witness(on, ta, tb, gamma_for(61))
+    _check_all(on, a, b, P, gamma_for(61))
+
+
 @pytest.mark.gpu
 def test_graph_replay_after_svd_witness(gpu_ctx_factory):
     """A replay after another call on the same context: the captured graph's
