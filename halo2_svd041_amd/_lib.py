@@ -147,6 +147,23 @@ class CommitCheck(ct.Structure):
                 ("bases_checked", ct.c_uint64), ("bases_off_curve", ct.c_uint64)]
 
 
+class FixedBaseResult(ct.Structure):
+    _fields_ = [("window_bits", ct.c_uint32), ("windows", ct.c_uint32), ("points", ct.c_uint64),
+                ("zero_scalars", ct.c_uint64), ("identity_outputs", ct.c_uint64)]
+
+
+class SrsResult(ct.Structure):
+    _fields_ = [("k", ct.c_uint32), ("window_bits", ct.c_uint32), ("windows", ct.c_uint32), ("chunks", ct.c_uint32),
+                ("rows", ct.c_uint64), ("chunk_rows", ct.c_uint64), ("g_zero_scalars", ct.c_uint64),
+                ("g_identity_outputs", ct.c_uint64), ("lagrange_zero_scalars", ct.c_uint64),
+                ("lagrange_identity_outputs", ct.c_uint64), ("secret_in_domain", ct.c_uint32), ("_pad", ct.c_uint32)]
+
+
+class SrsCheck(ct.Structure):
+    _fields_ = [("points_checked", ct.c_uint64), ("points_off_curve", ct.c_uint64), ("g_failed", ct.c_uint32),
+                ("lagrange_failed", ct.c_uint32)]
+
+
 class QuotientArgs(ct.Structure):
     _fields_ = [("k", ct.c_uint32), ("extended_k", ct.c_uint32), ("unusable_rows", ct.c_uint32), ("form", ct.c_int),
                 ("shift", ct.c_uint64 * 4), ("beta", ct.c_uint64 * 4), ("gamma", ct.c_uint64 * 4),
@@ -333,6 +350,9 @@ SIGNATURES = {
     "svdw_commit": (_i32, [_P, _u32, _i32, _i32, _P, _P, _u32, _P, ct.POINTER(CommitResult)]),
     "svdw_check_commit": (_i32, [_P, _u32, _i32, _i32, _P, _P, _u32, _P, ct.POINTER(CommitCheck)]),
     "svdw_commit_add_probe": (_i32, [_P, _P, _u32, _u64, _u32, ct.POINTER(ct.c_double)]),
+    "svdw_fixed_base_mul": (_i32, [_P, _i32, _i32, _P, _P, _u64, _u32, _P, ct.POINTER(FixedBaseResult)]),
+    "svdw_srs_setup": (_i32, [_P, _u32, _P, _i32, _P, _P, ct.POINTER(SrsResult)]),
+    "svdw_check_srs": (_i32, [_P, _u32, _i32, _P, _P, _P, _P, ct.POINTER(SrsCheck)]),
     "svdw_open_quotient": (_i32, [_P, _u32, _i32, _P, _u32, _P, _P, _P, _u32, _P, _P, _P, ct.POINTER(OpenResult)]),
     "svdw_open_linearise": (_i32, [_P, _u32, _i32, _P, _u32, _P, _P, _P, _u32, _P, _P, _P, _P, _P,
                                    ct.POINTER(OpenResult)]),

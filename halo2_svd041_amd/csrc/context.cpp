@@ -63,6 +63,7 @@ static std::vector<DBuf*> dbufs(svdw_ctx* c) {
                             &c->staging.buf};
     for (DBuf* d : c->circuit.dbufs()) v.push_back(d);
     for (DBuf* d : c->prover.dbufs()) v.push_back(d);
+    for (DBuf* d : c->srs.dbufs()) v.push_back(d);
     for (DBuf* d : c->exp.dbufs()) v.push_back(d);
     for (DBuf* d : c->ingest.dbufs()) v.push_back(d);
     for (int i = 0; i < kMaxScanJobs; ++i) {
@@ -205,6 +206,7 @@ static const OptionDef kOptions[] = {
     {"p1_at", -1, 3, "p1_at: -1 (auto), 0, 1, 2 or 3", set_opt<&Opt::p1_at>},
     {"commit_window_bits", 0, kCommitMaxBits, "commit_window_bits: 0 (the plan) or 2..16", set_commit_window_bits},
     {"commit_scratch_mib", 1, 65536, "commit_scratch_mib: 1..65536", set_opt<&Opt::commit_scratch_mib>},
+    {"srs_chunk_rows", 0, 1 << 28, "srs_chunk_rows: 0 (what fits commit_scratch_mib) or 1..2^28", set_opt<&Opt::srs_chunk_rows>},
     {"dchk_at", 0, 2, "dchk_at: 0 (cell stream), 1 (st2) or 2 (st3)", set_opt<&Opt::dchk_at>},   // pipelined: the d checks' stream
     {"gamma_at", -1, 1, "gamma_at: -1 (auto), 0 (cell stream) or 1 (st3)", set_opt<&Opt::gamma_at>},   // pipelined: k_gamma_prep's stream
     {"overlap", INT64_MIN, INT64_MAX, "", set_opt<&Opt::overlap>},

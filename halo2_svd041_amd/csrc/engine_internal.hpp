@@ -1,8 +1,8 @@
 // What the host files share: engine.cpp (the witness engine), context.cpp (the
 // context's lifetime, lanes, options, stream hand-off, marks, profiling),
 // export.cpp (read-out), ingest.cpp (text ingest), gemm.cpp (the exact field
-// product), circuit.cpp (the assigned-witness calls) and prover.cpp (the prover
-// calls). In order: the C ABI's error plumbing, device buffers, the entries'
+// product), circuit.cpp (the assigned-witness calls), prover.cpp (the prover
+// calls) and srs.cpp (the SRS calls). In order: the C ABI's error plumbing, device buffers, the entries'
 // host Fr helpers, each family's state, the host record of a witness, the
 // context (svdw_ctx), the functions that cross a file boundary, the staged call.
 #pragma once
@@ -121,6 +121,23 @@ struct ProverState {
         return v;
     }
 };
+// What the SRS calls (srs.cpp) keep on a context between calls.
+struct SrsState {
+    // the fixed-base tables (srs.hpp) by (base, window bits): built on first use, replaced in turn
+    struct Table {
+        DBuf buf;
+        uint32_t base[16] = {};             // the base's 64 bytes as given
+        int base_form = 0;
+        uint32_t c = 0;                     // 0: empty
+    } table[4];
+    uint32_t next = 0;                      // the slot the next new table takes
+    DBuf ws;                                // a call's scratch: a scalar column, accumulators, prefix products
+    std::vector<DBuf*> dbufs() {
+        std::vector<DBuf*> v = {&ws};
+        for (Table& t : table) v.push_back(&t.buf);
+        return v;
+    }
+};
 #pragma GCC visibility push(hidden)
 // Read-out (export.cpp: svdw_copy_cells, the host variants of svdw_export_* /
 // svdw_dequantize_*): two staging halves of at most kExportChunk bytes each, and
@@ -233,6 +250,8 @@ struct svdw_ctx {
         uint32_t commit_window_bits = 0;        // "commit_window_bits": svdw_commit's window, 0: svdw_commit_plan's
                                                 // (a tuning aid, tools/commit_bench.py; the result reports it)
         uint32_t commit_scratch_mib = 1024;     // "commit_scratch_mib": svdw_commit's workspace cap per batch of tasks
+        uint32_t srs_chunk_rows = 0;            // "srs_chunk_rows": rows per chunk of svdw_srs_setup, 0: what fits
+                                                // commit_scratch_mib (a testing aid; the result reports it)
         bool rlc_prefix = false;                // "rlc_prefix": svd_witness's phase 1 starts with the
                                                 // ctx_gate cells of load_rlc_cache(.., 1)
         int p1_at = -1;                         // "p1_at": phase 1 on st3 (mode 2) enqueued after
@@ -454,6 +473,7 @@ struct svdw_ctx {
     StagedScratch staging;                  // every staged call's scratch (circuit.cpp, prover.cpp)
     CircuitState circuit;                   // the assigned-witness calls (circuit.cpp)
     ProverState prover;                     // the prover calls (prover.cpp)
+    SrsState srs;                           // the SRS calls (srs.cpp)
     ExportState exp;                        // read-out (export.cpp)
     IngestState ingest;                     // the device ingest (ingest.cpp)
     // ---- captured verify_mul_witness ("graph", vm_graph): the launch sequence of
@@ -509,6 +529,8 @@ void svd_products_f64(svdw_ctx* c, const svdw_mat (&A)[3], const svdw_mat (&B)[3
 // verify_mul_witness's product from its f64 inputs
 void product_f64(svdw_ctx* c, hipStream_t s, const double* a, const double* b, uint32_t N, uint32_t K, uint32_t M,
                  Fr* out, const unsigned* dbits);
+// ---- prover.cpp: the context's table of omega_k's powers, uploaded on first use (ProverState::DomainSlot)
+const ProverState::DomainSlot& domain_table(svdw_ctx* c, uint32_t k);
 // ---- small helpers that more than one file needs
 // Device bytes held by a set of cell streams (both phases, advice + lookups).
 inline double set_bytes(const Stream (&s)[2]) {

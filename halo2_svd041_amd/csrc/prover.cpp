@@ -298,7 +298,7 @@ static Fr domain_omega_mont(uint32_t k) {
 }
 // The context's slot of omega_k's table (pow_table.hpp), host and device views: filled and uploaded on the first
 // use of k, never again. The upload is ordered on the stream before the caller's kernels; the slot keeps its source.
-static const ProverState::DomainSlot& domain_table(svdw_ctx* c, uint32_t k) {
+const ProverState::DomainSlot& domain_table(svdw_ctx* c, uint32_t k) {   // (srs.cpp reads it too)
     ProverState::DomainSlot& s = c->prover.domain[k];
     if (!s.buf.p) {
         s.cells.resize(pow_table_cells(k));

@@ -20,7 +20,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import (CheckResult, CommitCheck, CommitResult, EqCheck, OpenCheck, OpenResult, LookupCheck, LookupProductCheck, LookupProductResult, LookupResult, NttCheck, NttResult, PermutationCyclesResult, PermutationLayout, PermutationMappingCheck, PermutationProductCheck, PermutationProductResult, PhysParams, QuotientArgs, QuotientCheck, QuotientResult, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SvdwError,
+from ._lib import (CheckResult, CommitCheck, CommitResult, EqCheck, FixedBaseResult, OpenCheck, OpenResult, LookupCheck, LookupProductCheck, LookupProductResult, LookupResult, NttCheck, NttResult, PermutationCyclesResult, PermutationLayout, PermutationMappingCheck, PermutationProductCheck, PermutationProductResult, PhysParams, QuotientArgs, QuotientCheck, QuotientResult, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SrsCheck, SrsResult, SvdwError,
                    Vec, check, lib)
 
 P_MOD = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -1000,6 +1000,85 @@ class Context:
         check(lib().svdw_check_commit(self._h, k, _form(form), _form(bases_form), bases.data_ptr(), cp, n,
                                       commitments.data_ptr() if n else None, ct.byref(r)))
         return {k_: getattr(r, k_) for k_, _ in CommitCheck._fields_}
+
+    # ---- the SRS (include/svdw.h, "SRS"; parity pinned by the reference's file)
+    @staticmethod
+    def _points_tensor(what: str, t, rows: int, at_least: bool = False):
+        import torch
+        if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous()
+                or t.dim() != 2 or t.shape[1] != 64 or (t.shape[0] < rows if at_least else t.shape[0] != rows)):
+            raise SvdwError(-1, f"{what} must be a contiguous uint8 device tensor [{'>= ' if at_least else ''}{rows}, 64]")
+        return t
+
+    def fixed_base_mul(self, base, scalars, form: str = "canonical", base_form: str = "montgomery",
+                       window_bits: int = 0, out=None):
+        """(points, result): [scalars[i]] base for every cell of `scalars`, a
+        [n, 32] u8 device tensor in `form` (svdw_fixed_base_mul). base: the 64
+        bytes of one affine point in base_form (bytes or a u8 array), (0, 0) the
+        identity. points: [n, 64] u8 on the device in base_form; an `out` with
+        more than n rows keeps its rows from n on. window_bits: 0 for the
+        planned window, or 2..16. result: window_bits, windows, points,
+        zero_scalars, identity_outputs."""
+        import torch
+        f, bf = _form(form), _form(base_form)
+        raw = bytes(base) if isinstance(base, (bytes, bytearray)) else np.ascontiguousarray(base, dtype=np.uint8).tobytes()
+        if len(raw) != 64:
+            raise SvdwError(-1, "base must be the 64 bytes of one affine point")
+        if (not isinstance(scalars, torch.Tensor) or not scalars.is_cuda or scalars.dtype != torch.uint8
+                or not scalars.is_contiguous() or scalars.dim() != 2 or scalars.shape[1] != 32):
+            raise SvdwError(-1, "scalars must be a contiguous uint8 device tensor [n, 32]")
+        n = scalars.shape[0]
+        if out is None:
+            out = torch.empty((n, 64), dtype=torch.uint8, device=scalars.device)
+        self._points_tensor("out", out, n, at_least=True)
+        r = FixedBaseResult()
+        _after_torch(self)
+        check(lib().svdw_fixed_base_mul(self._h, f, bf, raw, scalars.data_ptr() if n else None,
+                                        n, window_bits, out.data_ptr() if n else None, ct.byref(r)))
+        _before_torch(self)
+        return out, {k_: getattr(r, k_) for k_, _ in FixedBaseResult._fields_}
+
+    def srs_setup(self, k: int, s: int, bases_form: str = "montgomery", g=True, g_lagrange=True):
+        """(g, g_lagrange, result): ParamsKZG::setup(k, .) for the secret s (an
+        int in [0, p)): g[i] = [s^i] G and g_lagrange[i] = [l_i(s)] G, [2^k, 64] u8
+        device tensors in bases_form (svdw_srs_setup). g, g_lagrange: True for a
+        new tensor, a tensor to write into, or None to leave that array out (it
+        is returned as None). result: k, window_bits, windows, chunks, rows,
+        chunk_rows, the zero scalars and identity outputs of either array,
+        secret_in_domain."""
+        import torch
+        sw, bf = _challenge_arg(s), _form(bases_form)
+        rows = 1 << k if 0 <= k < 32 else 0
+        outs = []
+        for what, t in (("g", g), ("g_lagrange", g_lagrange)):
+            if t is True:
+                t = torch.empty((rows, 64), dtype=torch.uint8, device=torch.device("cuda", self.device))
+            elif t is None or t is False:
+                t = None
+            else:
+                self._points_tensor(what, t, rows)
+            outs.append(t)
+        r = SrsResult()
+        _after_torch(self)
+        check(lib().svdw_srs_setup(self._h, k, sw, bf, *[t.data_ptr() if t is not None else None
+                                                                        for t in outs], ct.byref(r)))
+        _before_torch(self)
+        return outs[0], outs[1], {k_: getattr(r, k_) for k_, _ in SrsResult._fields_ if k_ != "_pad"}
+
+    def check_srs(self, g, g_lagrange, k: int, s: int, rho: int, bases_form: str = "montgomery") -> dict:
+        """Device check of an SRS's two arrays against its secret s with the
+        challenge rho (ints in [0, p)), sharing nothing with srs_setup
+        (svdw_check_srs): points_checked, points_off_curve, g_failed,
+        lagrange_failed."""
+        sw, rw, bf = _challenge_arg(s), _challenge_arg(rho), _form(bases_form)
+        rows = 1 << k if 0 <= k < 32 else 0
+        self._points_tensor("g", g, rows)
+        self._points_tensor("g_lagrange", g_lagrange, rows)
+        r = SrsCheck()
+        _after_torch(self)
+        check(lib().svdw_check_srs(self._h, k, bf, g.data_ptr(), g_lagrange.data_ptr(), sw, rw,
+                                   ct.byref(r)))
+        return {k_: getattr(r, k_) for k_, _ in SrsCheck._fields_}
 
     # ---- quotient polynomial (include/svdw.h, "quotient"; parity unpinned)
     _QUOTIENT_FAMILIES = ("advice", "selectors", "perm_columns", "sigma", "perm_z", "lookup_input", "lookup_table",

@@ -338,7 +338,11 @@ int svdw_set_gemm_impl(svdw_ctx* ctx, int impl);
  *   "commit_window_bits" 0 | 2..16 (svdw_commit's window instead of
  *   svdw_commit_plan's, a tuning aid; the result reports what was used);
  *   "commit_scratch_mib" 1024 | 1..65536 (svdw_commit's workspace cap per batch
- *   of (column, window) tasks, MiB; one task always runs);
+ *   of (column, window) tasks, MiB; one task always runs; svdw_fixed_base_mul
+ *   and svdw_srs_setup size their pieces by it too);
+ *   "srs_chunk_rows" 0 | 1..2^28 (svdw_srs_setup works through that many rows
+ *   at a time instead of what fits "commit_scratch_mib", a testing aid; the
+ *   result reports what was used);
  *   "place_trials" 6 | 0..8 (a cell stream of >= 256 MiB allocated from now on
  *   is chosen among that many placements in HBM by timing the stage kernels'
  *   store pattern on each; 0 or 1: the first one);
@@ -1100,6 +1104,100 @@ int svdw_check_commit(svdw_ctx* ctx, uint32_t k, int form, int bases_form, const
  * register-resident accumulator; *seconds is the launch's device time. */
 int svdw_commit_add_probe(svdw_ctx* ctx, const void* points, uint32_t npoints, uint64_t threads, uint32_t reps,
                           double* seconds);
+/* --------------------------------------------------------------------- SRS
+ * The bases of the commitments above, made on the device: what halo2-base's
+ * gen_srs(k) obtains from ParamsKZG::setup(k, rng), which draws one secret s
+ * and writes g[i] = [s^i] G and g_lagrange[i] = [l_i(s)] G for i < n = 2^k,
+ * G = (1, 2) and l_i the Lagrange basis of the domain of omega_k:
+ * l_i(s) = (s^n - 1) omega^i / (n (s - omega^i)). PARITY PINNED BY THE
+ * REFERENCE'S FILE: with the secret gen_srs draws (ChaCha20Rng from the zero
+ * seed, Fr::random; halo2_svd041_amd.srs.default_secret) the two arrays are,
+ * byte for byte, those of the reference's params/kzg_bn254_8.srs
+ * (tests/golden). The G2 half of a file ([1] G2 and [s] G2) is one scalar
+ * multiplication on the host (halo2_svd041_amd/srs.py) and not part of this
+ * interface. These calls need no witness and no physical layout.
+ *
+ * All of it is multiplication of ONE base by many unrelated scalars, which is
+ * not Pippenger's problem: svdw_fixed_base_mul looks every signed digit of a
+ * scalar up in a table of the base's multiples. Points, forms and the digits
+ * (c bits, W = ceil(255 / c) windows, digits in (-2^(c-1), 2^(c-1)] with
+ * carry) are those of the commitments section. */
+typedef struct {
+    uint32_t window_bits, windows;   /* c and W = ceil(255 / c) as used */
+    uint64_t points;                 /* n */
+    uint64_t zero_scalars;           /* scalars equal to 0 */
+    uint64_t identity_outputs;       /* outputs that are the identity, written as (0, 0) */
+} svdw_fixed_base_result;
+/* out[i] = [scalars[i]] base for i < n. base: HOST, one point (64 bytes) in
+ * base_form, (0, 0) allowed. scalars: DEVICE, n cells in `form`, taken as
+ * integers below p. out: DEVICE, n points in base_form; exactly n points are
+ * written. window_bits: 0 for the planned window (the c <= 12 with the fewest
+ * field products for n outputs; at c = 12 the table of W 2^(c-1) = 45056
+ * points, 2.75 MiB, stays in one XCD's L2), or 2..16. The table is built on
+ * the device on the first use of (base, base_form, window_bits) and kept on
+ * the context, four tables at the most, the oldest replaced. The checks of the
+ * arguments come first, before anything touches the device, in this order:
+ * null ctx, base or result (SVDW_EINVAL), an unknown form or base_form
+ * (SVDW_EINVAL), a base coordinate >= q or a base that is neither (0, 0) nor
+ * on the curve (SVDW_EINVAL), window_bits outside {0, 2..16} (SVDW_ERANGE), a
+ * planning context (SVDW_EINVAL), n > 0 with a null scalars or out, or an out
+ * that overlaps the scalars (SVDW_EINVAL). n == 0: SVDW_OK, nothing is touched
+ * (window_bits and windows are still reported). Queued on the context's
+ * stream with no host wait between the kernels; the call returns once its two
+ * counters have been read back. Scratch is the engine's, 160 B per output,
+ * in pieces kept under the option "commit_scratch_mib". */
+int svdw_fixed_base_mul(svdw_ctx* ctx, int form, int base_form, const void* base, const void* scalars, uint64_t n,
+                        uint32_t window_bits, void* out, svdw_fixed_base_result* result);
+typedef struct {
+    uint32_t k;
+    uint32_t window_bits, windows;   /* of the fixed-base multiplications */
+    uint32_t chunks;                 /* pieces of chunk_rows rows (the last may be shorter) */
+    uint64_t rows, chunk_rows;       /* 2^k; rows of a full piece */
+    uint64_t g_zero_scalars, g_identity_outputs;                 /* over g: s^i == 0; [s^i] G == identity */
+    uint64_t lagrange_zero_scalars, lagrange_identity_outputs;   /* over g_lagrange */
+    uint32_t secret_in_domain;       /* s^n == 1: g_lagrange is G at the i with omega^i == s, the identity elsewhere */
+    uint32_t _pad;
+} svdw_srs_result;
+/* ParamsKZG::setup(k, .) for the secret s (4 little-endian words, canonical):
+ * g (DEVICE, 2^k points in bases_form, or NULL) and g_lagrange (likewise) as
+ * defined above; either may be NULL and the other is still written. The two
+ * scalar columns are made on the device, s^i from a two-level power table of s,
+ * omega^i from the context's domain table, the inverses of s - omega^i by
+ * Montgomery's trick over Fr, and both go through svdw_fixed_base_mul's kernel
+ * with the planned window. A secret in the domain (s^n = 1, where the formula
+ * is 0 / 0) and s = 0 (g = G, identity, ...; g_lagrange = [1 / n] G throughout)
+ * are ordinary inputs. Rows are worked through in pieces of what fits the
+ * option "commit_scratch_mib" at 192 B per row and array (option
+ * "srs_chunk_rows": that many rows instead, a testing aid); the two columns
+ * of a piece share one launch of the multiplication. Checks in this order: null ctx, s or
+ * result (SVDW_EINVAL), an unknown bases_form (SVDW_EINVAL), s >= p
+ * (SVDW_EINVAL), k outside 1..28 (SVDW_ERANGE), a planning context
+ * (SVDW_EINVAL), g and g_lagrange overlapping (SVDW_EINVAL). Both NULL:
+ * SVDW_OK, nothing is touched. Queued and finished like svdw_fixed_base_mul. */
+int svdw_srs_setup(svdw_ctx* ctx, uint32_t k, const uint64_t s[4], int bases_form, void* g, void* g_lagrange,
+                   svdw_srs_result* result);
+typedef struct {
+    uint64_t points_checked, points_off_curve;   /* over both arrays; off the curve as svdw_commit_check counts it */
+    uint32_t g_failed;                /* sum_i rho^i g[i] != [((rho s)^n - 1) / (rho s - 1)] G */
+    uint32_t lagrange_failed;         /* sum_i rho^i g_lagrange[i] != [sum_i rho^i l_i(s)] G */
+} svdw_srs_check;
+/* g and g_lagrange (DEVICE, 2^k points in bases_form each, both required)
+ * against the secret s, independently of svdw_fixed_base_mul and of the
+ * setup's scalar columns: no table, no digits of s^i, no l_i. Every point is
+ * tested for the curve; then, with the column rho^i for a caller-chosen rho
+ * (canonical, like every challenge of this interface), svdw_commit's Pippenger
+ * path gives the two sums above, and each must be one multiple of G, which the
+ * host computes bit by bit with the laws of g1.hpp. The first scalar is the
+ * geometric sum (n when rho s = 1). The second is the value at s of the
+ * polynomial that takes rho^i at omega^i: svdw_ntt (inverse) of the column,
+ * then svdw_eval_polynomial at s. A single wrong point passes for at most n of
+ * the p choices of rho. Checks in this order: null ctx, s, rho or result
+ * (SVDW_EINVAL), an unknown bases_form (SVDW_EINVAL), s or rho >= p
+ * (SVDW_EINVAL), k outside 1..28 (SVDW_ERANGE), a planning context
+ * (SVDW_EINVAL), a null g or g_lagrange (SVDW_EINVAL). It writes to none of its
+ * inputs and returns after the device has finished. Scratch: two columns. */
+int svdw_check_srs(svdw_ctx* ctx, uint32_t k, int bases_form, const void* g, const void* g_lagrange,
+                   const uint64_t s[4], const uint64_t rho[4], svdw_srs_check* result);
 /* ---------------------------------------------------------------- openings
  * The quotient polynomials of halo2_proofs' poly::kzg::multiopen::shplonk
  * prover (ProverSHPLONK::create_proof) for polynomials held as coefficient
