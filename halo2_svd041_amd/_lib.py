@@ -164,6 +164,22 @@ class SrsCheck(ct.Structure):
                 ("lagrange_failed", ct.c_uint32)]
 
 
+class G1MulResult(ct.Structure):
+    _fields_ = [("window_bits", ct.c_uint32), ("windows", ct.c_uint32), ("points", ct.c_uint64),
+                ("zero_scalars", ct.c_uint64), ("identity_inputs", ct.c_uint64), ("identity_outputs", ct.c_uint64)]
+
+
+class G1FftResult(ct.Structure):
+    _fields_ = [("k", ct.c_uint32), ("stages", ct.c_uint32), ("window_bits", ct.c_uint32), ("windows", ct.c_uint32),
+                ("rows", ct.c_uint64), ("multiplications", ct.c_uint64), ("identity_inputs", ct.c_uint64),
+                ("identity_outputs", ct.c_uint64)]
+
+
+class LagrangeCheck(ct.Structure):
+    _fields_ = [("points_checked", ct.c_uint64), ("points_off_curve", ct.c_uint64), ("failed", ct.c_uint32),
+                ("_pad", ct.c_uint32)]
+
+
 class QuotientArgs(ct.Structure):
     _fields_ = [("k", ct.c_uint32), ("extended_k", ct.c_uint32), ("unusable_rows", ct.c_uint32), ("form", ct.c_int),
                 ("shift", ct.c_uint64 * 4), ("beta", ct.c_uint64 * 4), ("gamma", ct.c_uint64 * 4),
@@ -353,6 +369,9 @@ SIGNATURES = {
     "svdw_fixed_base_mul": (_i32, [_P, _i32, _i32, _P, _P, _u64, _u32, _P, ct.POINTER(FixedBaseResult)]),
     "svdw_srs_setup": (_i32, [_P, _u32, _P, _i32, _P, _P, ct.POINTER(SrsResult)]),
     "svdw_check_srs": (_i32, [_P, _u32, _i32, _P, _P, _P, _P, ct.POINTER(SrsCheck)]),
+    "svdw_g1_mul": (_i32, [_P, _i32, _i32, _P, _P, _u64, _u32, _P, ct.POINTER(G1MulResult)]),
+    "svdw_g1_fft": (_i32, [_P, _u32, _i32, _i32, _P, _P, ct.POINTER(G1FftResult)]),
+    "svdw_check_lagrange": (_i32, [_P, _u32, _i32, _P, _P, _P, ct.POINTER(LagrangeCheck)]),
     "svdw_open_quotient": (_i32, [_P, _u32, _i32, _P, _u32, _P, _P, _P, _u32, _P, _P, _P, ct.POINTER(OpenResult)]),
     "svdw_open_linearise": (_i32, [_P, _u32, _i32, _P, _u32, _P, _P, _P, _u32, _P, _P, _P, _P, _P,
                                    ct.POINTER(OpenResult)]),

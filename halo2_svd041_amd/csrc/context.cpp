@@ -64,6 +64,7 @@ static std::vector<DBuf*> dbufs(svdw_ctx* c) {
     for (DBuf* d : c->circuit.dbufs()) v.push_back(d);
     for (DBuf* d : c->prover.dbufs()) v.push_back(d);
     for (DBuf* d : c->srs.dbufs()) v.push_back(d);
+    for (DBuf* d : c->g1fft.dbufs()) v.push_back(d);
     for (DBuf* d : c->exp.dbufs()) v.push_back(d);
     for (DBuf* d : c->ingest.dbufs()) v.push_back(d);
     for (int i = 0; i < kMaxScanJobs; ++i) {
@@ -183,6 +184,10 @@ static void set_commit_window_bits(svdw_ctx* c, int64_t v) {
     REQUIRE(v != 1, "commit_window_bits: 0 (the plan) or 2..16");
     c->opt.commit_window_bits = (uint32_t)v;
 }
+static void set_g1_window_bits(svdw_ctx* c, int64_t v) {
+    REQUIRE(v != 1, "g1_window_bits: 0 (the plan) or 2..6");
+    c->opt.g1_window_bits = (uint32_t)v;
+}
 using Opt = svdw_ctx::Options;
 static const OptionDef kOptions[] = {
     {"lanes", 1, 2, "lanes: 1 or 2", set_lanes},   // verify_mul_witness on two alternating states
@@ -205,6 +210,7 @@ static const OptionDef kOptions[] = {
     {"f64_views", INT64_MIN, INT64_MAX, "", set_opt<&Opt::f64_views>},
     {"p1_at", -1, 3, "p1_at: -1 (auto), 0, 1, 2 or 3", set_opt<&Opt::p1_at>},
     {"commit_window_bits", 0, kCommitMaxBits, "commit_window_bits: 0 (the plan) or 2..16", set_commit_window_bits},
+    {"g1_window_bits", 0, 6, "g1_window_bits: 0 (the plan) or 2..6", set_g1_window_bits},
     {"commit_scratch_mib", 1, 65536, "commit_scratch_mib: 1..65536", set_opt<&Opt::commit_scratch_mib>},
     {"srs_chunk_rows", 0, 1 << 28, "srs_chunk_rows: 0 (what fits commit_scratch_mib) or 1..2^28", set_opt<&Opt::srs_chunk_rows>},
     {"dchk_at", 0, 2, "dchk_at: 0 (cell stream), 1 (st2) or 2 (st3)", set_opt<&Opt::dchk_at>},   // pipelined: the d checks' stream

@@ -2,7 +2,7 @@
 // context's lifetime, lanes, options, stream hand-off, marks, profiling),
 // export.cpp (read-out), ingest.cpp (text ingest), gemm.cpp (the exact field
 // product), circuit.cpp (the assigned-witness calls), prover.cpp (the prover
-// calls) and srs.cpp (the SRS calls). In order: the C ABI's error plumbing, device buffers, the entries'
+// calls), srs.cpp (the SRS calls) and g1_fft.cpp (the G1 transform calls). In order: the C ABI's error plumbing, device buffers, the entries'
 // host Fr helpers, each family's state, the host record of a witness, the
 // context (svdw_ctx), the functions that cross a file boundary, the staged call.
 #pragma once
@@ -138,6 +138,12 @@ struct SrsState {
         return v;
     }
 };
+// What the G1 transform calls (g1_fft.cpp) keep on a context between calls.
+struct G1FftState {
+    DBuf work;                              // svdw_g1_fft: the working array, 2^k XYZZ points
+    DBuf ws;                                // a piece's accumulators and tables; svdw_check_lagrange's two columns
+    std::vector<DBuf*> dbufs() { return {&work, &ws}; }
+};
 #pragma GCC visibility push(hidden)
 // Read-out (export.cpp: svdw_copy_cells, the host variants of svdw_export_* /
 // svdw_dequantize_*): two staging halves of at most kExportChunk bytes each, and
@@ -249,6 +255,8 @@ struct svdw_ctx {
         uint32_t hold_us = 0;                   // "hold_us": timing aid, st spins this long first
         uint32_t commit_window_bits = 0;        // "commit_window_bits": svdw_commit's window, 0: svdw_commit_plan's
                                                 // (a tuning aid, tools/commit_bench.py; the result reports it)
+        uint32_t g1_window_bits = 0;            // "g1_window_bits": svdw_g1_fft's window, 0: g1_plan's (a tuning aid,
+                                                // tools/g1_fft_bench.py; the result reports it)
         uint32_t commit_scratch_mib = 1024;     // "commit_scratch_mib": svdw_commit's workspace cap per batch of tasks
         uint32_t srs_chunk_rows = 0;            // "srs_chunk_rows": rows per chunk of svdw_srs_setup, 0: what fits
                                                 // commit_scratch_mib (a testing aid; the result reports it)
@@ -474,6 +482,7 @@ struct svdw_ctx {
     CircuitState circuit;                   // the assigned-witness calls (circuit.cpp)
     ProverState prover;                     // the prover calls (prover.cpp)
     SrsState srs;                           // the SRS calls (srs.cpp)
+    G1FftState g1fft;                       // the G1 transform calls (g1_fft.cpp)
     ExportState exp;                        // read-out (export.cpp)
     IngestState ingest;                     // the device ingest (ingest.cpp)
     // ---- captured verify_mul_witness ("graph", vm_graph): the launch sequence of

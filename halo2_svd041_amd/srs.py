@@ -16,6 +16,13 @@ derives that s; gen_srs() here runs the 2 * 2^k fixed-base multiplications on
 the device (Context.srs_setup); write_srs() adds the G2 half on the host, one
 scalar multiplication over Python integers. The golden file is reproduced byte
 for byte (tests/test_srs_cpu.py, tests/test_srs_gpu.py).
+
+A ceremony's file has no known secret and fixes k at the ceremony's size:
+downsize() is ParamsKZG::downsize, the first 2^k points of g and their Lagrange
+form by g_to_lagrange(), an inverse FFT over G1 on the device (Context.g1_fft).
+read_srs() keeps the file's G2 bytes and write_srs() writes them back when it
+has no secret, so a downsized ceremony file can be written
+(tests/test_g1_fft_cpu.py, tests/test_g1_fft_gpu.py).
 """
 from __future__ import annotations
 
@@ -23,7 +30,7 @@ import numpy as np
 
 from ._lib import SvdwError
 
-__all__ = ["read_srs", "default_secret", "gen_srs", "write_srs"]
+__all__ = ["read_srs", "default_secret", "gen_srs", "write_srs", "g_to_lagrange", "downsize"]
 
 _G2_BYTES = 2 * 128
 _Q = 21888242871839275222246405745257275088696311157297823662689037894645226208583
@@ -37,9 +44,9 @@ _G2 = ((108570469990230571359445707622328294813707563595785180869905199932856558
 
 
 def read_srs(path) -> dict:
-    """{"k", "g", "g_lagrange"}: the two arrays as [2^k, 64] u8 views of the
-    file's bytes. Raises SvdwError on a truncated file or a k that does not fit
-    the file's length."""
+    """{"k", "g", "g_lagrange", "g2"}: the two arrays as [2^k, 64] u8 views of the
+    file's bytes and its 256 G2 bytes as they are. Raises SvdwError on a
+    truncated file or a k that does not fit the file's length."""
     with open(path, "rb") as f:
         raw = f.read()
     if len(raw) < 4:
@@ -48,7 +55,7 @@ def read_srs(path) -> dict:
     if not 1 <= k <= 28 or len(raw) != 4 + 2 * (64 << k) + _G2_BYTES:
         raise SvdwError(-1, f"{path}: k = {k} does not fit a file of {len(raw)} bytes (truncated or not an SRS)")
     a = np.frombuffer(raw, dtype=np.uint8, count=2 * (64 << k), offset=4).reshape(2, 1 << k, 64)
-    return {"k": k, "g": a[0], "g_lagrange": a[1]}
+    return {"k": k, "g": a[0], "g_lagrange": a[1], "g2": raw[-_G2_BYTES:]}
 
 
 def _chacha20_block0() -> bytes:
@@ -141,15 +148,65 @@ def gen_srs(ctx, k: int, s=None) -> dict:
     return {"k": k, "g": g, "g_lagrange": gl, "s": s}
 
 
-def write_srs(path, srs: dict) -> None:
-    """Write {"k", "g", "g_lagrange", "s"} (gen_srs's result; the arrays device
-    tensors or numpy arrays in Montgomery form) as ParamsKZG::write does: u32 k,
-    g, g_lagrange, the G2 generator and [s] G2."""
-    k, s = int(srs["k"]), int(srs["s"])
+def g_to_lagrange(ctx, g, k=None):
+    """ParamsKZG's g_to_lagrange on the device: the Lagrange form of the first
+    2^k points of g, a [2^k, 64] u8 device tensor in Montgomery form
+    (Context.g1_fft, inverse). g: a [>= 2^k, 64] u8 device tensor or numpy array
+    in Montgomery form; k None: all of g, whose length must be a power of two."""
+    import torch
+    if not isinstance(g, (np.ndarray, torch.Tensor)) or len(g.shape) != 2:
+        raise SvdwError(-1, "g must be a [rows, 64] uint8 device tensor or numpy array")
+    if k is None:
+        k = max(int(g.shape[0]).bit_length() - 1, 0)
+        if g.shape[0] != 1 << k:
+            raise SvdwError(-1, f"g has {g.shape[0]} points, not a power of two: give k")
+    k = int(k)
     if not 1 <= k <= 28:
         raise SvdwError(-2, f"k = {k} is outside 1..28")
-    if not 0 <= s < _R:
-        raise SvdwError(-1, "s must be in [0, r)")
+    if g.shape[0] < 1 << k:
+        raise SvdwError(-2, f"k = {k} needs {1 << k} points, g has {g.shape[0]}")
+    g = g[:1 << k]
+    if isinstance(g, np.ndarray):                          # (a copy: read_srs's views are read-only)
+        g = torch.from_numpy(np.array(g)).to(torch.device("cuda", ctx.device))
+    out, _ = ctx.g1_fft(g.contiguous(), k, inverse=True)
+    return out
+
+
+def downsize(ctx, srs: dict, k: int) -> dict:
+    """ParamsKZG::downsize(k) of read_srs's or gen_srs's dict: g[:2^k], the
+    recomputed g_lagrange (a device tensor) and the new k; "s" and "g2" are
+    carried through. Raises SvdwError when k exceeds the dict's k."""
+    k = int(k)
+    if not 1 <= k <= int(srs["k"]):
+        raise SvdwError(-2, f"k = {k} is outside 1..{int(srs['k'])}, the SRS's size")
+    out = {key: srs[key] for key in ("s", "g2") if key in srs}
+    out.update(k=k, g=srs["g"][:1 << k], g_lagrange=g_to_lagrange(ctx, srs["g"], k))
+    return out
+
+
+def write_srs(path, srs: dict) -> None:
+    """Write {"k", "g", "g_lagrange"} and "s" or "g2" (gen_srs's, read_srs's or
+    downsize's result; the arrays device tensors or numpy arrays in Montgomery
+    form) as ParamsKZG::write does: u32 k, g, g_lagrange, the G2 generator and
+    [s] G2. With "s" the G2 half is computed from it; without, the 256 bytes of
+    "g2" are written back unchanged (a ceremony's file, whose secret nobody
+    has); with neither it raises."""
+    k = int(srs["k"])
+    if not 1 <= k <= 28:
+        raise SvdwError(-2, f"k = {k} is outside 1..28")
+    if srs.get("s") is not None:
+        s = int(srs["s"])
+        if not 0 <= s < _R:
+            raise SvdwError(-1, "s must be in [0, r)")
+        g2 = None
+    elif srs.get("g2") is not None:
+        g2 = bytes(srs["g2"])
+        if len(g2) != _G2_BYTES:
+            raise SvdwError(-1, f"g2 must be the {_G2_BYTES} bytes of two G2 points")
+    else:
+        raise SvdwError(-1, 'write_srs needs the secret "s" or the G2 bytes "g2"')
     body = _point_array("g", srs["g"], 1 << k) + _point_array("g_lagrange", srs["g_lagrange"], 1 << k)
+    if g2 is None:
+        g2 = _g2_bytes(_G2) + _g2_bytes(_g2_mul(_G2, s))
     with open(path, "wb") as f:
-        f.write(k.to_bytes(4, "little") + body + _g2_bytes(_G2) + _g2_bytes(_g2_mul(_G2, s)))
+        f.write(k.to_bytes(4, "little") + body + g2)

@@ -20,7 +20,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import (CheckResult, CommitCheck, CommitResult, EqCheck, FixedBaseResult, OpenCheck, OpenResult, LookupCheck, LookupProductCheck, LookupProductResult, LookupResult, NttCheck, NttResult, PermutationCyclesResult, PermutationLayout, PermutationMappingCheck, PermutationProductCheck, PermutationProductResult, PhysParams, QuotientArgs, QuotientCheck, QuotientResult, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SrsCheck, SrsResult, SvdwError,
+from ._lib import (CheckResult, CommitCheck, CommitResult, EqCheck, FixedBaseResult, G1FftResult, G1MulResult, LagrangeCheck, OpenCheck, OpenResult, LookupCheck, LookupProductCheck, LookupProductResult, LookupResult, NttCheck, NttResult, PermutationCyclesResult, PermutationLayout, PermutationMappingCheck, PermutationProductCheck, PermutationProductResult, PhysParams, QuotientArgs, QuotientCheck, QuotientResult, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SrsCheck, SrsResult, SvdwError,
                    Vec, check, lib)
 
 P_MOD = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -1079,6 +1079,68 @@ class Context:
         check(lib().svdw_check_srs(self._h, k, bf, g.data_ptr(), g_lagrange.data_ptr(), sw, rw,
                                    ct.byref(r)))
         return {k_: getattr(r, k_) for k_, _ in SrsCheck._fields_}
+
+    # ---- G1 transforms (include/svdw.h, "G1 transforms"; parity pinned by the reference's file)
+    def g1_mul(self, points, scalars, form: str = "canonical", bases_form: str = "montgomery", window_bits: int = 0,
+               out=None):
+        """(out, result): [scalars[i]] points[i], an unrelated scalar times an
+        unrelated point per row (svdw_g1_mul). points: a [n, 64] u8 device
+        tensor of affine points in bases_form, (0, 0) the identity; scalars: a
+        [n, 32] u8 device tensor in `form`. out: [n, 64] u8 on the device in
+        bases_form; an `out` with more than n rows keeps its rows from n on.
+        window_bits: 0 for the planned window, or 2..6. result: window_bits,
+        windows, points, zero_scalars, identity_inputs, identity_outputs."""
+        import torch
+        f, bf = _form(form), _form(bases_form)
+        if (not isinstance(scalars, torch.Tensor) or not scalars.is_cuda or scalars.dtype != torch.uint8
+                or not scalars.is_contiguous() or scalars.dim() != 2 or scalars.shape[1] != 32):
+            raise SvdwError(-1, "scalars must be a contiguous uint8 device tensor [n, 32]")
+        n = scalars.shape[0]
+        self._points_tensor("points", points, n)
+        if out is None:
+            out = torch.empty((n, 64), dtype=torch.uint8, device=scalars.device)
+        self._points_tensor("out", out, n, at_least=True)
+        r = G1MulResult()
+        _after_torch(self)
+        check(lib().svdw_g1_mul(self._h, f, bf, points.data_ptr() if n else None, scalars.data_ptr() if n else None,
+                                n, window_bits, out.data_ptr() if n else None, ct.byref(r)))
+        _before_torch(self)
+        return out, {k_: getattr(r, k_) for k_, _ in G1MulResult._fields_}
+
+    def g1_fft(self, points, k: int, inverse: bool = False, bases_form: str = "montgomery", out=None):
+        """(out, result): the FFT over G1 of the 2^k affine points, natural
+        order on both sides (svdw_g1_fft): out[i] = sum_j [omega^(i j)] points[j],
+        or with inverse=True [2^-k] sum_j [omega^(-i j)] points[j], which is
+        ParamsKZG's g_to_lagrange. points, out: [2^k, 64] u8 device tensors in
+        bases_form that do not overlap. result: k, stages, window_bits,
+        windows, rows, multiplications, identity_inputs, identity_outputs."""
+        import torch
+        bf = _form(bases_form)
+        rows = 1 << k if 0 <= k < 32 else 0
+        self._points_tensor("points", points, rows)
+        if out is None:
+            out = torch.empty((rows, 64), dtype=torch.uint8, device=points.device)
+        self._points_tensor("out", out, rows)
+        r = G1FftResult()
+        _after_torch(self)
+        check(lib().svdw_g1_fft(self._h, k, bf, 1 if inverse else 0, points.data_ptr(), out.data_ptr(), ct.byref(r)))
+        _before_torch(self)
+        return out, {k_: getattr(r, k_) for k_, _ in G1FftResult._fields_}
+
+    def check_lagrange(self, g, g_lagrange, k: int, rho: int, bases_form: str = "montgomery") -> dict:
+        """Device check that g_lagrange is the Lagrange form of g, with the
+        challenge rho (an int in [0, p)) and no secret, sharing nothing with
+        g1_fft (svdw_check_lagrange): points_checked, points_off_curve, failed.
+        It does not show that g is a sequence of powers (that needs G2 and a
+        pairing)."""
+        rw, bf = _challenge_arg(rho), _form(bases_form)
+        rows = 1 << k if 0 <= k < 32 else 0
+        self._points_tensor("g", g, rows)
+        self._points_tensor("g_lagrange", g_lagrange, rows)
+        r = LagrangeCheck()
+        _after_torch(self)
+        check(lib().svdw_check_lagrange(self._h, k, bf, g.data_ptr(), g_lagrange.data_ptr(), rw, ct.byref(r)))
+        return {k_: getattr(r, k_) for k_, _ in LagrangeCheck._fields_ if k_ != "_pad"}
 
     # ---- quotient polynomial (include/svdw.h, "quotient"; parity unpinned)
     _QUOTIENT_FAMILIES = ("advice", "selectors", "perm_columns", "sigma", "perm_z", "lookup_input", "lookup_table",

@@ -339,7 +339,10 @@ int svdw_set_gemm_impl(svdw_ctx* ctx, int impl);
  *   svdw_commit_plan's, a tuning aid; the result reports what was used);
  *   "commit_scratch_mib" 1024 | 1..65536 (svdw_commit's workspace cap per batch
  *   of (column, window) tasks, MiB; one task always runs; svdw_fixed_base_mul
- *   and svdw_srs_setup size their pieces by it too);
+ *   and svdw_srs_setup size their pieces by it too, and so do svdw_g1_mul
+ *   and the stages of svdw_g1_fft, whose planned window also depends on it);
+ *   "g1_window_bits" 0 | 2..6 (svdw_g1_fft's window instead of the planned one,
+ *   a tuning aid; the result reports what was used);
  *   "srs_chunk_rows" 0 | 1..2^28 (svdw_srs_setup works through that many rows
  *   at a time instead of what fits "commit_scratch_mib", a testing aid; the
  *   result reports what was used);
@@ -1198,6 +1201,100 @@ typedef struct {
  * inputs and returns after the device has finished. Scratch: two columns. */
 int svdw_check_srs(svdw_ctx* ctx, uint32_t k, int bases_form, const void* g, const void* g_lagrange,
                    const uint64_t s[4], const uint64_t rho[4], svdw_srs_check* result);
+/* ----------------------------------------------------------- G1 transforms
+ * What a ceremony's SRS needs, whose secret nobody knows and whose file fixes
+ * k at the ceremony's size: halo2_proofs' ParamsKZG::downsize(k) keeps the
+ * first 2^k points of g and recomputes the Lagrange half with g_to_lagrange,
+ * an inverse FFT over G1: g_lagrange[i] = [1 / n] sum_j [omega^(-i j)] g[j].
+ * PARITY PINNED BY THE REFERENCE'S FILE: params/kzg_bn254_8.srs holds both
+ * halves, and svdw_g1_fft (inverse) of its g is its g_lagrange byte for byte
+ * (tests/golden), no secret involved. halo2_svd041_amd.srs has g_to_lagrange
+ * and downsize on top of it. These calls need no witness and no physical
+ * layout. Points, forms and the digits are those of the commitments section.
+ *
+ * An FFT over a group is, per butterfly and stage, one multiplication of an
+ * unrelated point by an unrelated scalar, which neither Pippenger's buckets
+ * nor svdw_fixed_base_mul's table of one base provide: svdw_g1_mul builds a
+ * table of every point's own small multiples and keeps the doublings. */
+typedef struct {
+    uint32_t window_bits, windows;        /* c and W = ceil(255 / c) as used */
+    uint64_t points;                      /* n */
+    uint64_t zero_scalars;                /* scalars equal to 0 */
+    uint64_t identity_inputs;             /* points equal to (0, 0) */
+    uint64_t identity_outputs;            /* outputs that are the identity, written as (0, 0) */
+} svdw_g1_mul_result;
+/* out[i] = [scalars[i]] points[i] for i < n. points, out: DEVICE, n affine
+ * points in bases_form each, (0, 0) the identity; coordinates are taken as
+ * svdw_commit takes its bases. scalars: DEVICE, n cells in `form`, taken as
+ * integers below p as svdw_fixed_base_mul takes them (a canonical cell may hold
+ * r itself: the digits are the integer's). Exactly n points are written.
+ * window_bits: 0 for the planned window, or 2..6. Per point a table [d] P,
+ * 1 <= d <= 2^(c-1), is built in scratch; the digits are walked top first, c
+ * doublings and at most one complete add per window. The planned window is
+ * the c <= 4 with the fewest field products (4: 3298 a multiplication) whose
+ * scratch for 2^17 points fits the option "commit_scratch_mib"; 5 has 2 % fewer
+ * products and twice the table, and measured slower at 2^20. The checks of the arguments come
+ * first, before anything touches the device, in this order: null ctx or result
+ * (SVDW_EINVAL), an unknown form or bases_form (SVDW_EINVAL), window_bits
+ * outside {0, 2..6} (SVDW_ERANGE), a planning context (SVDW_EINVAL), n > 0 with
+ * a null points, scalars or out, or an out that overlaps the points or the
+ * scalars (SVDW_EINVAL). n == 0: SVDW_OK, nothing is touched (window_bits and
+ * windows are still reported). Queued on the context's stream with no host
+ * wait between the kernels; the call returns once its counters have been read
+ * back. Scratch is the engine's, (2^(c-1) + 1) 128 B per point, worked through
+ * in pieces kept under the option "commit_scratch_mib". */
+int svdw_g1_mul(svdw_ctx* ctx, int form, int bases_form, const void* points, const void* scalars, uint64_t n,
+                uint32_t window_bits, void* out, svdw_g1_mul_result* result);
+typedef struct {
+    uint32_t k, stages;                   /* stages == k */
+    uint32_t window_bits, windows;        /* of the twiddle multiplications (the planned window) */
+    uint64_t rows;                        /* 2^k */
+    uint64_t multiplications;             /* twiddle multiplications done; a twiddle of 1 is not multiplied */
+    uint64_t identity_inputs, identity_outputs;
+} svdw_g1_fft_result;
+/* The FFT over G1 of size n = 2^k, natural order on both sides:
+ *   forward  out[i] = sum_j [omega_k^(i j)] points[j]
+ *   inverse  out[i] = [2^-k] sum_j [omega_k^(-i j)] points[j]   (g_to_lagrange)
+ * points, out: DEVICE, 2^k affine points in bases_form each; they must not
+ * overlap. Radix 2, decimation in time: the bit reversal and the first stage
+ * (twiddle 1) in one kernel, then one stage at a time over a working array of
+ * 2^k XYZZ points, a butterfly (a + [w] b, a - [w] b) with w from the
+ * context's domain table and [w] b by svdw_g1_mul's kernels; a butterfly whose
+ * twiddle is 1 multiplies nothing. The inverse folds 2^-k into its last stage,
+ * [c] a +- [c w] b, which costs n / 2 multiplications more where a scaling
+ * pass would cost n: multiplications = k n / 2 - n + 1 forward and
+ * k n / 2 - n / 2 + 2 inverse, counted on the device. Checks in this order: null
+ * ctx or result (SVDW_EINVAL), an unknown bases_form (SVDW_EINVAL), k outside
+ * 1..28 (SVDW_ERANGE), a planning context (SVDW_EINVAL), a null points or out,
+ * or an out that overlaps the points (SVDW_EINVAL). Queued and finished like
+ * svdw_g1_mul. Scratch: the working array, 128 B 2^k, outside the option
+ * "commit_scratch_mib" (a transform has no pieces; SVDW_ENOMEM when it cannot
+ * be had), and the tables of a stage, in pieces under that option. */
+int svdw_g1_fft(svdw_ctx* ctx, uint32_t k, int bases_form, int inverse, const void* points, void* out,
+                svdw_g1_fft_result* result);
+typedef struct {
+    uint64_t points_checked, points_off_curve;   /* over both arrays; off the curve as svdw_commit_check counts it */
+    uint32_t failed;                  /* sum_i rho^i g_lagrange[i] != sum_j c_j g[j] */
+    uint32_t _pad;
+} svdw_lagrange_check;
+/* g_lagrange against g (DEVICE, 2^k points in bases_form each, both required)
+ * without a secret and independently of svdw_g1_fft: no butterfly, no
+ * variable-base multiplication. Every point is tested for the curve; then,
+ * with the column v_i = rho^i for a caller-chosen rho (canonical) and its
+ * coefficients c = svdw_ntt (inverse) of v, svdw_commit's Pippenger path gives
+ * sum_i v_i g_lagrange[i] and sum_j c_j g[j], which the host compares. When
+ * g_lagrange is the inverse transform of g the two are equal for every rho; a
+ * single wrong point passes for at most n of the p choices of rho. rho = 0
+ * sees row 0 of g_lagrange alone. It proves that the two halves agree. It does
+ * NOT prove that g is a sequence of powers [s^j] G of one secret: that needs
+ * the G2 half and a pairing, which stay with the caller. It is also what to
+ * run on a file one was handed. Checks in this order: null ctx, rho or result
+ * (SVDW_EINVAL), an unknown bases_form (SVDW_EINVAL), rho >= p (SVDW_EINVAL), k
+ * outside 1..28 (SVDW_ERANGE), a planning context (SVDW_EINVAL), a null g or
+ * g_lagrange (SVDW_EINVAL). It writes to none of its inputs and returns after
+ * the device has finished. Scratch: two columns. */
+int svdw_check_lagrange(svdw_ctx* ctx, uint32_t k, int bases_form, const void* g, const void* g_lagrange,
+                        const uint64_t rho[4], svdw_lagrange_check* result);
 /* ---------------------------------------------------------------- openings
  * The quotient polynomials of halo2_proofs' poly::kzg::multiopen::shplonk
  * prover (ProverSHPLONK::create_proof) for polynomials held as coefficient
