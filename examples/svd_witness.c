@@ -6,6 +6,9 @@
  *       -Wl,-rpath,$PWD/halo2_svd041_amd -o svd_witness
  *   ./svd_witness [N] [P]            (device 0; N x N input with known SVD)
  *   ./svd_witness data/matrix.in [P] (input-creator.py file, serde_json-default parse)
+ *   ./svd_witness --decompose ...    (u, d, v computed from m on the device by
+ *                                     svdw_svd_decompose; the file's or the synthetic
+ *                                     u, d, v are ignored: no LAPACK anywhere)
  *
  * Input: m = u diag(d) v with u, v signed permutations scaled by cos/sin
  * (Givens rotations), so u, v are exactly orthogonal up to f64 rounding.
@@ -14,6 +17,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "svdw.h"
 
@@ -50,6 +54,14 @@ static char* read_file(const char* path, long* len) {
 }
 
 int main(int argc, char** argv) {
+    int decompose = 0;
+    for (int i = 1; i < argc; ++i)
+        if (!strcmp(argv[i], "--decompose")) {
+            decompose = 1;
+            for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
+            --argc;
+            --i;
+        }
     uint32_t N = 64, M = 64;
     uint32_t P = argc > 2 ? (uint32_t)atoi(argv[2]) : 42;
     double *u, *v, *m, *d;
@@ -82,6 +94,12 @@ int main(int argc, char** argv) {
     svdw_params p = {0, P, 19};
     svdw_ctx* ctx = NULL;
     CHECK(svdw_ctx_create(&p, &ctx));
+    if (decompose) {                     /* input-creator.py:30 on the device: u, d, v from m alone */
+        svdw_svd_info info;
+        CHECK(svdw_svd_decompose(ctx, m, N, M, 0, NULL, u, d, v, &info));
+        printf("decomposed: %u sweeps, %llu rotations, converged=%u, completed=%u, off=%.3g\n", info.sweeps,
+               (unsigned long long)info.rotations, info.converged, info.completed, info.off);
+    }
     svdw_svd_config cfg = {100.0, 1e-10, 1e-10, 30};
     uint64_t gamma[4] = {0x1234567890abcdefull, 0x0fedcba987654321ull, 0x1111ull, 0x0ull};
     svdw_counts cnt;

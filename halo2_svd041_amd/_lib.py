@@ -180,6 +180,16 @@ class LagrangeCheck(ct.Structure):
                 ("_pad", ct.c_uint32)]
 
 
+class SvdOpts(ct.Structure):
+    _fields_ = [("panel", ct.c_uint32), ("inner", ct.c_uint32), ("max_sweeps", ct.c_uint32)]
+
+
+class SvdInfo(ct.Structure):
+    _fields_ = [("sweeps", ct.c_uint32), ("converged", ct.c_uint32), ("completed", ct.c_uint32),
+                ("rotations", ct.c_uint64), ("off", ct.c_double), ("pairs", ct.c_uint64),
+                ("skipped_pairs", ct.c_uint64)]
+
+
 class QuotientArgs(ct.Structure):
     _fields_ = [("k", ct.c_uint32), ("extended_k", ct.c_uint32), ("unusable_rows", ct.c_uint32), ("form", ct.c_int),
                 ("shift", ct.c_uint64 * 4), ("beta", ct.c_uint64 * 4), ("gamma", ct.c_uint64 * 4),
@@ -378,6 +388,7 @@ SIGNATURES = {
     "svdw_check_open": (_i32, [_P, _u32, _i32, _P, _u32, _P, _P, _P, _u32, _P, _P, _P, _P, _P, _P, _P,
                                ct.POINTER(OpenCheck)]),
     "svdw_linear_combination": (_i32, [_P, _u32, _i32, _P, _u32, _P, _P]),
+    "svdw_svd_decompose": (_i32, [_P, _P, _u32, _u32, _i32, ct.POINTER(SvdOpts), _P, _P, _P, ct.POINTER(SvdInfo)]),
 }
 
 _lib = None

@@ -65,6 +65,7 @@ static std::vector<DBuf*> dbufs(svdw_ctx* c) {
     for (DBuf* d : c->prover.dbufs()) v.push_back(d);
     for (DBuf* d : c->srs.dbufs()) v.push_back(d);
     for (DBuf* d : c->g1fft.dbufs()) v.push_back(d);
+    for (DBuf* d : c->svd.dbufs()) v.push_back(d);
     for (DBuf* d : c->exp.dbufs()) v.push_back(d);
     for (DBuf* d : c->ingest.dbufs()) v.push_back(d);
     for (int i = 0; i < kMaxScanJobs; ++i) {
@@ -97,6 +98,7 @@ static void ctx_release(svdw_ctx* c) {
         for (DBuf* b : dbufs(c))
             if (b->p) (void)hipFree(b->p);
         if (c->hbits) (void)hipHostFree(c->hbits);
+        if (c->svd.pinned) (void)hipHostFree(c->svd.pinned);
         if (c->ev_bits) (void)hipEventDestroy(c->ev_bits);
         for (auto e : c->xev)
             if (e) (void)hipEventDestroy(e);

@@ -2,7 +2,8 @@
 // context's lifetime, lanes, options, stream hand-off, marks, profiling),
 // export.cpp (read-out), ingest.cpp (text ingest), gemm.cpp (the exact field
 // product), circuit.cpp (the assigned-witness calls), prover.cpp (the prover
-// calls), srs.cpp (the SRS calls) and g1_fft.cpp (the G1 transform calls). In order: the C ABI's error plumbing, device buffers, the entries'
+// calls), srs.cpp (the SRS calls), g1_fft.cpp (the G1 transform calls) and svd.cpp (the
+// decomposition). In order: the C ABI's error plumbing, device buffers, the entries'
 // host Fr helpers, each family's state, the host record of a witness, the
 // context (svdw_ctx), the functions that cross a file boundary, the staged call.
 #pragma once
@@ -143,6 +144,13 @@ struct G1FftState {
     DBuf work;                              // svdw_g1_fft: the working array, 2^k XYZZ points
     DBuf ws;                                // a piece's accumulators and tables; svdw_check_lagrange's two columns
     std::vector<DBuf*> dbufs() { return {&work, &ws}; }
+};
+// What the decomposition (svd.cpp) keeps on a context between calls.
+struct SvdState {
+    DBuf ws;                                // the working array, the partial Gram matrices, norms, order, words
+    DBuf io;                                // host inputs and outputs staged on the device: m, u, d, v
+    unsigned long long* pinned = nullptr;   // the host's view of a sweep's counter and of the load's words
+    std::vector<DBuf*> dbufs() { return {&ws, &io}; }
 };
 #pragma GCC visibility push(hidden)
 // Read-out (export.cpp: svdw_copy_cells, the host variants of svdw_export_* /
@@ -483,6 +491,7 @@ struct svdw_ctx {
     ProverState prover;                     // the prover calls (prover.cpp)
     SrsState srs;                           // the SRS calls (srs.cpp)
     G1FftState g1fft;                       // the G1 transform calls (g1_fft.cpp)
+    SvdState svd;                           // the decomposition (svd.cpp)
     ExportState exp;                        // read-out (export.cpp)
     IngestState ingest;                     // the device ingest (ingest.cpp)
     // ---- captured verify_mul_witness ("graph", vm_graph): the launch sequence of

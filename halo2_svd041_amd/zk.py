@@ -20,14 +20,14 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import (CheckResult, CommitCheck, CommitResult, EqCheck, FixedBaseResult, G1FftResult, G1MulResult, LagrangeCheck, OpenCheck, OpenResult, LookupCheck, LookupProductCheck, LookupProductResult, LookupResult, NttCheck, NttResult, PermutationCyclesResult, PermutationLayout, PermutationMappingCheck, PermutationProductCheck, PermutationProductResult, PhysParams, QuotientArgs, QuotientCheck, QuotientResult, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SrsCheck, SrsResult, SvdwError,
+from ._lib import (CheckResult, CommitCheck, CommitResult, EqCheck, FixedBaseResult, G1FftResult, G1MulResult, LagrangeCheck, OpenCheck, OpenResult, LookupCheck, LookupProductCheck, LookupProductResult, LookupResult, NttCheck, NttResult, PermutationCyclesResult, PermutationLayout, PermutationMappingCheck, PermutationProductCheck, PermutationProductResult, PhysParams, QuotientArgs, QuotientCheck, QuotientResult, Counts, DivScale, InputDims, KStat, Mat, Params, Payload, Region, Segment, SvdConfig, SvdInfo, SvdOpts, SrsCheck, SrsResult, SvdwError,
                    Vec, check, lib)
 
 P_MOD = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
 __all__ = ["Context", "ZkMatrix", "ZkVector", "honest_prover_mat_mul", "field_mat_vec_mul",
            "mat_times_diag_mat", "check_mat_diff", "check_mat_id", "check_mat_entries_bounded",
-           "check_svd_phase0", "check_svd_phase1", "err_calc", "svd_witness", "plan_svd",
+           "check_svd_phase0", "check_svd_phase1", "err_calc", "svd_witness", "svd_decompose", "plan_svd",
            "SvdwError", "SvdPayload", "SvdConfigPy", "P_MOD", "int_to_words", "words_to_int",
            "fr_convert", "quantization", "dequantization", "format_f64_debug", "permutation_constants",
            "commit_plan", "shplonk_queries"]
@@ -1685,6 +1685,44 @@ def svd_witness(ctx: Context, m, u, v, d, gamma: int, cfg: SvdConfigPy = SvdConf
                                      ct.byref(cfgc), g, ct.byref(cnt)))
     ctx.last_svd = (int(N), int(M), cfg)        # for collect.plan (shard segment replay)
     return cnt.as_dict()
+
+
+def svd_decompose(ctx: Context, m, device: bool = False, panel: int = 0, inner: int = 0, max_sweeps: int = 0):
+    """(u, d, v, info) with m = u diag(d) v, computed on the device by blocked
+    one-sided Jacobi (svdw_svd_decompose; input-creator.py:30 without LAPACK):
+    u N x N, d min(N, M), v M x M holding the rows of V^T as numpy's third
+    output does. device=False: m is a host array and the outputs are numpy
+    arrays. device=True: m is a contiguous float64 torch tensor on the
+    context's device (a host array is uploaded first) and the outputs are torch
+    tensors there, ready for svd_witness. info: sweeps, converged, completed
+    (columns made by completion), rotations, off, pairs and skipped_pairs (panel
+    pairs visited, and those whose solve made no rotation)."""
+    opts = SvdOpts(panel, inner, max_sweeps)
+    info = SvdInfo()
+    if device:
+        torch = _torch_mod()
+        dev = torch.device("cuda", ctx.device)
+        if _device_ptr(m) is None:
+            m = torch.from_numpy(np.ascontiguousarray(m, dtype=np.float64)).to(dev)
+        if m.dim() != 2:
+            raise SvdwError(-1, "svd_decompose: m must be a matrix")
+        N, M = m.shape
+        u = torch.empty((N, N), dtype=torch.float64, device=dev)
+        d = torch.empty(min(N, M), dtype=torch.float64, device=dev)
+        v = torch.empty((M, M), dtype=torch.float64, device=dev)
+        _after_torch(ctx)               # m may still be in flight, the outputs' memory still read, on torch's stream
+        check(lib().svdw_svd_decompose(ctx.handle, m.data_ptr(), N, M, 1, ct.byref(opts), u.data_ptr(),
+                                       d.data_ptr(), v.data_ptr(), ct.byref(info)))
+        _before_torch(ctx)
+    else:
+        m = np.ascontiguousarray(m, dtype=np.float64)
+        if m.ndim != 2:
+            raise SvdwError(-1, "svd_decompose: m must be a matrix")
+        N, M = m.shape
+        u, d, v = np.empty((N, N)), np.empty(min(N, M)), np.empty((M, M))
+        check(lib().svdw_svd_decompose(ctx.handle, m.ctypes.data, N, M, 0, ct.byref(opts), u.ctypes.data,
+                                       d.ctypes.data, v.ctypes.data, ct.byref(info)))
+    return u, d, v, {k: getattr(info, k) for k, _ in info._fields_}
 
 
 def verify_mul_witness(ctx: Context, a, b, gamma: int) -> dict:

@@ -1428,6 +1428,65 @@ int svdw_parse_svd_input(const char* text, uint64_t len, int mode, svdw_input_di
 int svdw_parse_svd_input_device(svdw_ctx* ctx, const void* text, uint64_t len, int mode,
                                 svdw_input_dims* dims, double* m, double* u, double* d, double* v);
 
+/* ----------------------------------------------------------- decomposition
+ * The singular value decomposition itself, m = u diag(d) v, on the device in
+ * f64: what input-creator.py:30 (`u, d, v = lin.svd(m)`) asks of LAPACK, so that
+ * a witness needs no host linear algebra. The circuit is the specification of
+ * a good factorisation (check_svd_phase0: d non-negative and descending, the
+ * entries of u and v inside (-1, 1), |u d - m v^T| < err_svd, |u u^T - I| and
+ * |v v^T - I| < err_u after quantization), and svdw_check_gates on the witness
+ * made from the factors is its acceptance test. NO PARITY WITH LAPACK: singular
+ * vectors are unique up to sign (and up to a rotation among equal singular
+ * values), and the method differs; d agrees to rounding.
+ *
+ * Blocked one-sided (Hestenes) Jacobi. With R = min(N, M), C = max(N, M) it works
+ * on G = m (N <= M) or m^T (N > M), R x C, and W = I (C x C): columns of G and W
+ * are rotated together until G's columns are mutually orthogonal. Columns go in
+ * panels of b; a sweep is the round-robin tournament over panel pairs; per pair
+ * the 2b x 2b Gram matrix (b = 8: one v_mfma_f64_16x16x4_f64 tile), `inner`
+ * cyclic Jacobi sweeps on it, and the product of the rotations applied to the
+ * pair's columns (matrix cores at b = 8). A rotation of columns i, j is skipped
+ * when h_ij^2 <= eps^2 h_ii h_jj or min(h_ii, h_jj) <= (eps |m|_F)^2, eps = 2^-52;
+ * a sweep without a rotation ends the iteration. No floating-point atomics: the
+ * result is the same bytes from run to run. Then d = the column norms sorted
+ * descending (stable), the R x R factor the normalised columns, the C x C factor
+ * W. A column j < R whose norm is <= C eps d_0 (rank deficiency; d_0 = 0 is the
+ * zero matrix) keeps its norm as d_j and gets its vector by completion on the
+ * host: unit vectors orthogonalised twice against all other columns. The zero
+ * matrix gives d = 0, u = I, v = I. */
+typedef struct {
+    uint32_t panel;        /* columns per panel b: 1, 4 or 8; 0 = default (8) */
+    uint32_t inner;        /* sweeps of the in-block eigen solve; 0 = default (2) */
+    uint32_t max_sweeps;   /* 0 = default (40) */
+} svdw_svd_opts;
+typedef struct {
+    uint32_t sweeps, converged, completed;   /* completed: u / v columns made by completion */
+    uint64_t rotations;
+    double off;            /* largest |h_ij| / sqrt(h_ii h_jj) seen in the last sweep */
+    uint64_t pairs;        /* panel pairs visited: sweeps (P - 1) P / 2 for P panels (padded to even) */
+    uint64_t skipped_pairs; /* of those, pairs whose solve made no rotation: their apply is skipped */
+} svdw_svd_info;
+/* u (N x N), d (min(N, M)) and v (M x M, the rows of V^T as numpy's third output
+ * and the reference's v) from m (N x M); all row-major f64, all four in host
+ * memory (on_device = 0) or all four in DEVICE memory (on_device = 1, then
+ * svdw_svd_witness(on_device = 1) reads u, d, v where they lie). opts and info
+ * may be null. Checks in this order, the first six before anything touches the
+ * device: null ctx (SVDW_EINVAL), N or M == 0 (SVDW_EINVAL), a null m, u, d or v
+ * (SVDW_EINVAL), an output that overlaps m or another output (SVDW_EINVAL), a
+ * panel other than 0, 1, 4, 8 or a dimension above 2^20 (SVDW_ERANGE), a planning
+ * context (SVDW_EINVAL, as svdw_ntt refuses it); workspace that cannot be had
+ * (SVDW_ENOMEM); an entry of m that is NaN or infinite (SVDW_EINVAL: found by the
+ * kernel that loads m, and u, d, v are not written). Not converged within
+ * max_sweeps is SVDW_OK with converged = 0 and the factors of the last sweep:
+ * the caller decides. Synchronous, like svdw_parse_svd_input_device: it waits
+ * for the context's queued work (and what svdw_stream_wait ordered it after),
+ * reads one counter back per sweep and returns when u, d, v are written, so a
+ * witness call that follows on the same context needs nothing in between.
+ * Workspace is the engine's, kept on the context: 8 (R + C) C bytes for G
+ * stacked on W, plus m, u, d, v staged when they are the host's. */
+int svdw_svd_decompose(svdw_ctx* ctx, const double* m, uint32_t N, uint32_t M, int on_device,
+                       const svdw_svd_opts* opts, double* u, double* d, double* v, svdw_svd_info* info);
+
 /* Closed-form cell counts of svdw_svd_witness without touching a device. */
 int svdw_plan_svd(uint32_t N, uint32_t M, uint32_t precision_bits, uint32_t lookup_bits,
                   const svdw_svd_config* cfg, svdw_counts* counts);
