@@ -18,7 +18,7 @@ SOURCES = ["kernels.hip", "gemm.hip", "ingest_dev.hip", "export.hip", "lookup.hi
 HEADERS = ["fr.hpp", "pow_table.hpp", "prog.hpp", "kernels.hpp", "kernel_common.hpp", "gemm.hpp", "crt_tables.hpp",
            "ingest.hpp", "ingest_dev.hpp", "export.hpp", "lookup.hpp", "grand_product.hpp", "lookup_product.hpp",
            "permutation_product.hpp", "permutation_cycles.hpp", "ntt.hpp", "quotient.hpp", "fq.hpp", "g1.hpp",
-           "commit.hpp", "open.hpp", "srs.hpp", "g1_fft.hpp", "svd.hpp", "engine_internal.hpp"]
+           "g1_mul.hpp", "commit.hpp", "open.hpp", "srs.hpp", "g1_fft.hpp", "svd.hpp", "engine_internal.hpp"]
 ARCH = os.environ.get("SVDW_OFFLOAD_ARCH", "gfx950")
 
 

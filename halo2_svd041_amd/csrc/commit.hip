@@ -6,35 +6,9 @@
 namespace svdw {
 namespace {
 
-__device__ __forceinline__ G1Affine load_base(const G1Affine* bases, uint64_t row, int bases_form) {
-    G1Affine p = bases[row];
-    if (bases_form == 0) {                                 // canonical coordinates: to Montgomery
-        p.x = fq_to_mont(p.x);
-        p.y = fq_to_mont(p.y);
-    }
-    return p;
-}
 __device__ __forceinline__ Fr load_scalar(const Fr* col, uint64_t row, int form) {
     const Fr s = col[row];
     return form == 0 ? s : fr_from_mont(s);
-}
-
-// The signed digits of s: emit(window, |d| - 1, negative) for every d != 0. The
-// scalar is shifted down c bits per window, so no word is indexed at run time.
-template <class Emit>
-__device__ __forceinline__ void commit_digits(Fr s, uint32_t c, uint32_t W, Emit&& emit) {
-    const uint32_t full = 1u << c, half = full >> 1;
-    uint32_t carry = 0;
-#pragma unroll 1
-    for (uint32_t w = 0; w < W; ++w) {
-        const uint32_t d = (s.w[0] & (full - 1)) + carry;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) s.w[i] = (s.w[i] >> c) | (s.w[i + 1] << (32 - c));
-        s.w[7] >>= c;
-        carry = d > half;
-        const uint32_t mag = carry ? full - d : d;
-        if (mag) emit(w, mag - 1, carry);
-    }
 }
 
 // SCATTER false: the histogram and the call's counters; true: the scatter.
@@ -53,10 +27,11 @@ __global__ __launch_bounds__(kCommitThreads) void k_commit_digits(CommitBatch a,
         if (idb && col == 0) atomicAdd(&a.cnt[1], 1ull);
     }
     if (idb) return;
-    commit_digits(s, a.c, a.W, [&](uint32_t w, uint32_t b, uint32_t neg) {
+    g1_signed_digits(s, a.c, a.W, [&](uint32_t w, uint32_t mag, uint32_t neg) {
         const uint64_t g = gcol + w;
-        if (g < a.g0 || g >= (uint64_t)a.g0 + a.T) return;
+        if (!mag || g < a.g0 || g >= (uint64_t)a.g0 + a.T) return;   // a zero digit adds nothing
         const uint64_t t = g - a.g0;
+        const uint32_t b = mag - 1;                        // bucket b holds |d| = b + 1
         if (SCATTER) {
             const uint32_t pos = atomicAdd(&a.cursor[t * B + b], 1u);
             a.sorted[(t << a.k) + pos] = (uint32_t)row | (neg << 31);
@@ -138,7 +113,7 @@ __global__ __launch_bounds__(kCommitThreads) void k_commit_runs(CommitBatch a) {
             bend = st[b + 1];
         }
         const uint32_t e = sorted[pos];
-        G1Affine p = load_base(a.bases, e & 0x7fffffffu, a.bases_form);
+        G1Affine p = g1_affine_to_mont(a.bases[e & 0x7fffffffu], a.bases_form);
         if (e >> 31) p.y = fq_neg(p.y);
         acc = g1_add_mixed(acc, p);
     }
@@ -249,14 +224,6 @@ __global__ __launch_bounds__(kCommitTreeThreads) void k_commit_window(CommitBatc
     if (threadIdx.x == 0) a.windows[(uint64_t)a.g0 + t] = acc;
 }
 
-__device__ __forceinline__ G1Affine store_form(G1Affine p, int bases_form) {
-    if (bases_form == 0) {
-        p.x = fq_from_mont(p.x);
-        p.y = fq_from_mont(p.y);
-    }
-    return p;
-}
-
 __global__ __launch_bounds__(64) void k_commit_horner(const G1Xyzz* windows, uint32_t ncols, uint32_t c, uint32_t W,
                                                       int bases_form, G1Affine* out, unsigned long long* cnt) {
     const uint32_t col = blockIdx.x * 64 + threadIdx.x;
@@ -270,7 +237,7 @@ __global__ __launch_bounds__(64) void k_commit_horner(const G1Xyzz* windows, uin
         acc = g1_add(acc, win[w]);
     }
     if (g1_is_identity(acc)) atomicAdd(&cnt[2], 1ull);
-    out[col] = store_form(g1_to_affine(acc), bases_form);
+    out[col] = g1_affine_to_form(g1_to_affine(acc), bases_form);
 }
 
 // ---- the checker
@@ -289,7 +256,7 @@ __global__ __launch_bounds__(kCommitTreeThreads) void k_commit_check_bits(const 
         uint32_t word = s.w[0];                            // select chain: no run-time index into s
 #pragma unroll
         for (int j = 1; j < 8; ++j) word = (wi == (uint32_t)j) ? s.w[j] : word;
-        if ((word >> sh_bit) & 1) acc = g1_add_mixed(acc, load_base(bases, row, bases_form));
+        if ((word >> sh_bit) & 1) acc = g1_add_mixed(acc, g1_affine_to_mont(bases[row], bases_form));
     }
     acc = block_sum(acc, sh);
     if (threadIdx.x == 0) part[((uint64_t)lc * kCommitScalarBits + bit) * gridDim.x + blockIdx.x] = acc;
@@ -315,14 +282,10 @@ __global__ __launch_bounds__(kCommitThreads) void k_commit_check_fold(const G1Xy
         acc = g1_double(acc);
         acc = g1_add(acc, sh[b]);
     }
-    G1Affine given = commitments[col0 + lc];
+    const G1Affine given = commitments[col0 + lc];
     const bool reduced = fq_reduced(given.x) && fq_reduced(given.y);
-    if (bases_form == 0) {
-        given.x = fq_to_mont(given.x);
-        given.y = fq_to_mont(given.y);
-    }
     atomicAdd(&cnt[0], 1ull);
-    if (!reduced || !g1_eq_affine(acc, given)) atomicAdd(&cnt[1], 1ull);
+    if (!reduced || !g1_eq_affine(acc, g1_affine_to_mont(given, bases_form))) atomicAdd(&cnt[1], 1ull);
 }
 
 __global__ __launch_bounds__(kCommitThreads) void k_commit_check_bases(const G1Affine* bases, uint64_t n, int bases_form,
@@ -331,7 +294,7 @@ __global__ __launch_bounds__(kCommitThreads) void k_commit_check_bases(const G1A
     if (row >= n) return;
     const G1Affine raw = bases[row];
     const bool reduced = fq_reduced(raw.x) && fq_reduced(raw.y);
-    const G1Affine p = load_base(bases, row, bases_form);
+    const G1Affine p = g1_affine_to_mont(raw, bases_form);
     atomicAdd(&cnt[2], 1ull);
     if (!g1_affine_is_identity(raw) && !(reduced && g1_on_curve(p))) atomicAdd(&cnt[3], 1ull);
 }
@@ -346,8 +309,6 @@ __global__ __launch_bounds__(kCommitThreads) void k_commit_add_probe(const G1Aff
     for (uint32_t r = 0; r < reps; ++r) acc = g1_add_mixed(acc, p);
     dst[i] = acc;
 }
-
-inline unsigned blocks_of(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace
 

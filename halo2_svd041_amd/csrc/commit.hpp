@@ -4,8 +4,9 @@
 //
 // Pippenger with signed c-bit digits. A cell, as a canonical integer below
 // r < 2^254, is cut into W = ceil(255 / c) digits d_w in (-2^(c-1), 2^(c-1)]
-// with carry (W c >= 255 leaves no carry out of the top window); a negative
-// digit adds the base with y -> q - y. A task is one (column, window); task
+// with carry (g1_signed_digits, g1_mul.hpp: the one recoder of this family, the
+// SRS's and the G1 transforms'); a negative digit adds the base with
+// y -> q - y. A task is one (column, window); task
 // g = column W + window. Tasks run in batches of T under the workspace cap
 // (commit_task_bytes; the option "commit_scratch_mib"); per batch:
 //
@@ -52,13 +53,15 @@
 // As grand_product.hpp and ntt.hpp ask: loops over points stay rolled (#pragma
 // unroll 1 around the inlined laws), no register arrays under a runtime index
 // (the digits shift the scalar down instead of indexing its words), 64-bit row
-// indices.
+// indices. Points are read and written in bases_form through g1.hpp's
+// g1_affine_to_mont and g1_affine_to_form alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "fr.hpp"
 #include "g1.hpp"
+#include "g1_mul.hpp"
 
 namespace svdw {
 

@@ -84,8 +84,22 @@ inline bool fr_reduced(const Fr& x) {
     return sub_p(t, x) != 0;                               // x - p borrows: x < p
 }
 
-inline void need_columns(const std::string& f, uint32_t n, const char* where = "") {   // under the entry's name f
+// The checks several entries repeat, each under the entry's name f (scratch_cap, which reads the context: below).
+inline void need_columns(const std::string& f, uint32_t n, const char* where = "") {
     if (n > 65535) fail(SVDW_ERANGE, f + ": more than 65535 columns" + where);
+}
+inline void need_k(const std::string& f, uint32_t k) {
+    if (k < 1 || k > 28) fail(SVDW_ERANGE, f + ": k must be in [1, 28]");
+}
+inline void need_pointer(const std::string& f, const void* p) { REQUIRE(p, f + ": null column pointer"); }
+// [o0, o1) (the output `out`) and [i0, i1) (`in`) do not meet.
+inline void need_apart(const std::string& f, const char* out, uintptr_t o0, uintptr_t o1, const char* in, uintptr_t i0,
+                       uintptr_t i1) {
+    REQUIRE(i1 <= o0 || o1 <= i0, f + ": " + out + " overlaps " + in);
+}
+// A nested call of the interface: its error becomes this call's.
+inline void nested(int rc) {
+    if (rc != SVDW_OK) fail(rc, g_err);
 }
 // ------------------------------------------------- the families' state
 // The device scratch of every staged call of either family (stage, below), in the
@@ -593,6 +607,8 @@ inline uint32_t clog2(uint32_t k) {                        // least l with 2^l >
 inline uint32_t ceil_to(uint32_t x, uint32_t a) { return (x + a - 1) / a * a; }
 // The check every device entry makes, under the entry's name f.
 inline void need_device(const svdw_ctx* c, const std::string& f) { REQUIRE(!c->dry, f + " needs a device context"); }
+// The scratch cap of a G1 call in bytes (the option "commit_scratch_mib").
+inline uint64_t scratch_cap(const svdw_ctx* c) { return (uint64_t)c->opt.commit_scratch_mib << 20; }
 // RAII: brackets one kernel launch with HIP events on the context stream.
 struct ProfScope {
     svdw_ctx* c;

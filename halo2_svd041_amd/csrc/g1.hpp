@@ -44,6 +44,24 @@ SVDW_HD G1Xyzz g1_from_affine(const G1Affine& p) {
     r.zz = r.zzz = id ? fq_zero() : fq_one();
     return r;
 }
+// The form of an affine point's coordinates as the entries pass it (bases_form,
+// base_form): 0 canonical Fq, anything else Montgomery. These two state the
+// rule for every reader and writer of points. (0, 0) stays (0, 0) either way,
+// so the identity is the same bytes in both forms.
+SVDW_HD G1Affine g1_affine_to_mont(G1Affine p, int form) {
+    if (form == 0) {
+        p.x = fq_to_mont(p.x);
+        p.y = fq_to_mont(p.y);
+    }
+    return p;
+}
+SVDW_HD G1Affine g1_affine_to_form(G1Affine p, int form) {
+    if (form == 0) {
+        p.x = fq_from_mont(p.x);
+        p.y = fq_from_mont(p.y);
+    }
+    return p;
+}
 SVDW_HD G1Affine g1_affine_neg(const G1Affine& p) {
     G1Affine r;
     r.x = p.x;

@@ -12,24 +12,9 @@
 #include "engine_internal.hpp"
 #include "g1_fft.hpp"
 
-namespace {
-struct G1Window {
-    uint32_t c, W;
-};
-}  // namespace
-
-static void g1_need_k(const std::string& f, uint32_t k) {
-    if (k < 1 || k > 28) fail(SVDW_ERANGE, f + ": k must be in [1, 28]");
-}
-// The scratch cap of a call in bytes (the option "commit_scratch_mib").
-static uint64_t g1_cap(const svdw_ctx* c) { return (uint64_t)c->opt.commit_scratch_mib << 20; }
 static G1Window g1_window(const svdw_ctx* c, uint32_t window_bits) {
-    const uint32_t cb = window_bits ? window_bits : g1_plan(g1_cap(c));
+    const uint32_t cb = window_bits ? window_bits : g1_plan(scratch_cap(c));
     return G1Window{cb, fb_windows(cb)};
-}
-static bool g1_overlap(const void* a, uint64_t abytes, const void* b, uint64_t bbytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return !(a0 + abytes <= b0 || b0 + bbytes <= a0);
 }
 // The `items` multiplications a describes, in pieces whose tables and
 // accumulators stay under the cap: the table, the multiplication, then
@@ -37,7 +22,7 @@ static bool g1_overlap(const void* a, uint64_t abytes, const void* b, uint64_t b
 template <class After>
 static void g1_pieces(svdw_ctx* c, G1Mul a, uint64_t items, After&& after) {
     const uint64_t per = g1_point_bytes(a.c);
-    const uint64_t rows = std::min<uint64_t>(std::max<uint64_t>(g1_cap(c) / per, 1), items);
+    const uint64_t rows = std::min<uint64_t>(std::max<uint64_t>(scratch_cap(c) / per, 1), items);
     ensure_buf(c, c->g1fft.ws, rows * per);
     G1Xyzz* acc = (G1Xyzz*)c->g1fft.ws.p;
     a.table = acc + rows;
@@ -72,8 +57,10 @@ int svdw_g1_mul(svdw_ctx* c, int form, int bases_form, const void* points, const
         result->points = n;
         if (!n) return;
         REQUIRE(points && scalars && out, "null argument");
-        REQUIRE(!g1_overlap(out, n * sizeof(G1Affine), points, n * sizeof(G1Affine)), f + ": out overlaps the points");
-        REQUIRE(!g1_overlap(out, n * sizeof(G1Affine), scalars, n * sizeof(Fr)), f + ": out overlaps the scalars");
+        const uintptr_t o0 = (uintptr_t)out, o1 = o0 + n * sizeof(G1Affine), p0 = (uintptr_t)points,
+                        s0 = (uintptr_t)scalars;
+        need_apart(f, "out", o0, o1, "the points", p0, p0 + n * sizeof(G1Affine));
+        need_apart(f, "out", o0, o1, "the scalars", s0, s0 + n * sizeof(Fr));
         sync(c);
         G1Mul a{};
         a.points = (const G1Affine*)points;
@@ -84,7 +71,7 @@ int svdw_g1_mul(svdw_ctx* c, int form, int bases_form, const void* points, const
         a.dst_linear = 1;
         a.c = w.c;
         a.W = w.W;
-        ensure_buf(c, c->g1fft.ws, std::min<uint64_t>(g1_cap(c), n * g1_point_bytes(w.c)));   // ahead of the counters
+        ensure_buf(c, c->g1fft.ws, std::min<uint64_t>(scratch_cap(c), n * g1_point_bytes(w.c)));   // ahead of the counters
         const Staged d = stage_counters(c);
         a.cnt = d.cnt;
         g1_pieces(c, a, n, [&](const G1Mul& p) { g1_affine(c, p.dst, p.m, bases_form, (G1Affine*)out + p.t0, d.cnt); });
@@ -102,11 +89,12 @@ int svdw_g1_fft(svdw_ctx* c, uint32_t k, int bases_form, int inverse, const void
         const std::string f = "svdw_g1_fft";
         REQUIRE(c && result, "null argument");
         check_form(bases_form);
-        g1_need_k(f, k);
+        need_k(f, k);
         need_device(c, f);
         REQUIRE(points && out, "null argument");
         const uint64_t n = 1ull << k, half = n >> 1;
-        REQUIRE(!g1_overlap(out, n * sizeof(G1Affine), points, n * sizeof(G1Affine)), f + ": out overlaps the points");
+        const uintptr_t o0 = (uintptr_t)out, p0 = (uintptr_t)points, len = n * sizeof(G1Affine);
+        need_apart(f, "out", o0, o0 + len, "the points", p0, p0 + len);
         memset(result, 0, sizeof *result);
         const G1Window w = g1_window(c, c->opt.g1_window_bits);
         result->k = result->stages = k;
@@ -116,7 +104,7 @@ int svdw_g1_fft(svdw_ctx* c, uint32_t k, int bases_form, int inverse, const void
         sync(c);
         // everything that may allocate comes ahead of the first launch
         ensure_buf(c, c->g1fft.work, n * sizeof(G1Xyzz));
-        ensure_buf(c, c->g1fft.ws, std::min<uint64_t>(g1_cap(c), half * g1_point_bytes(w.c)));
+        ensure_buf(c, c->g1fft.ws, std::min<uint64_t>(scratch_cap(c), half * g1_point_bytes(w.c)));
         const PowTable dom = domain_table(c, k).dev;
         G1Xyzz* work = (G1Xyzz*)c->g1fft.work.p;
         const Staged d = stage_counters(c);
@@ -165,11 +153,6 @@ int svdw_g1_fft(svdw_ctx* c, uint32_t k, int bases_form, int inverse, const void
     });
 }
 
-// A nested call of the interface: its error becomes this call's.
-static void g1_nested(int rc) {
-    if (rc != SVDW_OK) fail(rc, g_err);
-}
-
 int svdw_check_lagrange(svdw_ctx* c, uint32_t k, int bases_form, const void* g, const void* g_lagrange,
                         const uint64_t rho[4], svdw_lagrange_check* result) {
     return guarded([&] {
@@ -178,7 +161,7 @@ int svdw_check_lagrange(svdw_ctx* c, uint32_t k, int bases_form, const void* g, 
         check_form(bases_form);
         const Fr rc = fr_raw_words(rho);
         REQUIRE(fr_reduced(rc), f + ": rho must be below p");
-        g1_need_k(f, k);
+        need_k(f, k);
         need_device(c, f);
         REQUIRE(g && g_lagrange, "null argument");
         memset(result, 0, sizeof *result);
@@ -210,10 +193,10 @@ int svdw_check_lagrange(svdw_ctx* c, uint32_t k, int bases_form, const void* g, 
         const void* colp = col;
         const void* coefp = coeffs;
         svdw_ntt_result nr;
-        g1_nested(svdw_ntt(c, k, k, SVDW_FORM_MONTGOMERY, 1, nullptr, &colp, 1, coeffs, &nr));
+        nested(svdw_ntt(c, k, k, SVDW_FORM_MONTGOMERY, 1, nullptr, &colp, 1, coeffs, &nr));
         svdw_commit_result cr;
-        g1_nested(svdw_commit(c, k, SVDW_FORM_MONTGOMERY, bases_form, g, &coefp, 1, sums, &cr));
-        g1_nested(svdw_commit(c, k, SVDW_FORM_MONTGOMERY, bases_form, g_lagrange, &colp, 1, sums + 1, &cr));
+        nested(svdw_commit(c, k, SVDW_FORM_MONTGOMERY, bases_form, g, &coefp, 1, sums, &cr));
+        nested(svdw_commit(c, k, SVDW_FORM_MONTGOMERY, bases_form, g_lagrange, &colp, 1, sums + 1, &cr));
         G1Affine hs[2];
         hipck(hipMemcpyAsync(hs, sums, sizeof hs, hipMemcpyDeviceToHost, c->st), "D2H");
         sync(c);

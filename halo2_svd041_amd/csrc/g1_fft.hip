@@ -12,12 +12,7 @@ __device__ __forceinline__ uint64_t g1_item_index(const G1Mul& a, uint64_t t) {
 }
 __device__ __forceinline__ G1Xyzz g1_item_point(const G1Mul& a, uint64_t idx) {
     if (!a.points) return a.work[idx];
-    G1Affine p = a.points[idx];
-    if (a.bases_form == 0) {                               // (0, 0) stays (0, 0)
-        p.x = fq_to_mont(p.x);
-        p.y = fq_to_mont(p.y);
-    }
-    return g1_from_affine(p);
+    return g1_from_affine(g1_affine_to_mont(a.points[idx], a.bases_form));
 }
 // The exponent of item t's twiddle, before the inverse's sign.
 __device__ __forceinline__ uint64_t g1_item_exponent(const G1Mul& a, uint64_t t) { return (t & a.tw_mask) << a.tw_shift; }
@@ -55,27 +50,14 @@ __global__ __launch_bounds__(kG1Threads) void k_g1_table(G1Mul a) {
     }
 }
 
-// The signed digits of s (commit.hpp; srs.hip's fb_digits restated) into the
-// lane's column of dig, every window written: |d| in the low bits, 0x80 the sign.
-__device__ __forceinline__ void g1_digits(Fr s, uint32_t c, uint32_t W, uint8_t (*dig)[kG1Threads], uint32_t lane) {
-    const uint32_t full = 1u << c, half = full >> 1;
-    uint32_t carry = 0;
-#pragma unroll 1
-    for (uint32_t w = 0; w < W; ++w) {
-        const uint32_t d = (s.w[0] & (full - 1)) + carry;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) s.w[i] = (s.w[i] >> c) | (s.w[i + 1] << (32 - c));
-        s.w[7] >>= c;
-        carry = d > half;
-        dig[w][lane] = (uint8_t)(carry ? (full - d) | 0x80u : d);
-    }
-}
-
-// [s] P for the point whose table column starts at T (stride m): top window
-// first, c doublings and one complete add per window.
+// [s] P for the point whose table column starts at T (stride m): the signed
+// digits go to the lane's column of dig, every window written (|d| in the low
+// bits, 0x80 the sign), then top window first, c doublings and one complete add
+// per window.
 __device__ __forceinline__ G1Xyzz g1_mul_walk(const G1Xyzz* T, uint64_t m, Fr s, uint32_t c, uint32_t W,
                                               uint8_t (*dig)[kG1Threads], uint32_t lane) {
-    g1_digits(s, c, W, dig, lane);
+    g1_signed_digits(s, c, W,
+                     [&](uint32_t w, uint32_t mag, uint32_t neg) { dig[w][lane] = (uint8_t)(mag | neg << 7); });
     G1Xyzz acc = g1_identity();
 #pragma unroll 1
     for (uint32_t w = W; w-- > 0;) {
@@ -145,15 +127,7 @@ __global__ __launch_bounds__(kFbThreads) void k_g1_affine(const G1Xyzz* src, uin
             atomicAdd(&cnt[2], 1ull);
             r.x = r.y = fq_zero();
         } else {
-            const Fq i3 = fq_mul(inv, out[i].x);           // 1 / ZZZ_i
-            inv = fq_mul(inv, acc.zzz);
-            const Fq i2 = fq_sqr(fq_mul(acc.zz, i3));      // 1 / ZZ = (ZZ / ZZZ)^2
-            r.x = fq_mul(acc.x, i2);
-            r.y = fq_mul(acc.y, i3);
-            if (bases_form == 0) {
-                r.x = fq_from_mont(r.x);
-                r.y = fq_from_mont(r.y);
-            }
+            r = g1_affine_shared_inv(acc, out[i].x, inv, bases_form);
         }
         out[i] = r;
     }
@@ -164,13 +138,8 @@ __global__ __launch_bounds__(kCommitThreads) void k_g1_fft_first(const G1Affine*
     const uint64_t t = (uint64_t)blockIdx.x * kCommitThreads + threadIdx.x, half = 1ull << (k - 1);
     if (t >= half) return;
     const uint64_t r = k > 1 ? __brevll(t) >> (65 - k) : 0;   // t reversed over k - 1 bits
-    G1Affine a = in[r], b = in[r + half];
-    if (bases_form == 0) {
-        a.x = fq_to_mont(a.x);
-        a.y = fq_to_mont(a.y);
-        b.x = fq_to_mont(b.x);
-        b.y = fq_to_mont(b.y);
-    }
+    const G1Affine a = g1_affine_to_mont(in[r], bases_form);
+    G1Affine b = g1_affine_to_mont(in[r + half], bases_form);
     const unsigned long long ids = (g1_affine_is_identity(a) ? 1 : 0) + (g1_affine_is_identity(b) ? 1 : 0);
     if (ids) atomicAdd(&cnt[1], ids);
     const G1Xyzz top = g1_from_affine(a);
@@ -181,8 +150,6 @@ __global__ __launch_bounds__(kCommitThreads) void k_g1_fft_first(const G1Affine*
         b.y = fq_neg(b.y);
     }
 }
-
-inline unsigned blocks_of(uint64_t n, uint64_t per) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace
 

@@ -3,10 +3,10 @@
 // over the group that ParamsKZG's g_to_lagrange is (an inverse FFT of the SRS's
 // g), which is what `downsize` of a ceremony file needs.
 //
-// Variable-base multiplication with the signed c-bit digits of commit.hpp: a
-// scalar, as a canonical integer below r < 2^254, is cut into W = ceil(255 / c)
-// digits d_w in (-2^(c-1), 2^(c-1)] with carry. Neither side is known ahead, so
-// every point gets a table of its own and the doublings stay:
+// Variable-base multiplication with signed c-bit digits (g1_signed_digits,
+// g1_mul.hpp): a scalar, as a canonical integer below r < 2^254, is cut into
+// W = ceil(255 / c) digits d_w in (-2^(c-1), 2^(c-1)] with carry. Neither side
+// is known ahead, so every point gets a table of its own and the doublings stay:
 //
 //  k_g1_table   thread i: T[d - 1][i] = [d] P_i for 1 <= d <= B = 2^(c-1), in
 //               XYZZ, by B - 1 complete adds in one rolled loop. The table is
@@ -25,9 +25,10 @@
 //               per lane, apart it costs a 128 B store and load per butterfly
 //  k_g1_affine  XYZZ -> affine, k_fb_mul's forward / invert / backward without
 //               the adds: a thread takes kFbGroup points (srs.hpp), multiplies
-//               their ZZZ up, inverts once (fq_inv) and walks back. The prefix
-//               products wait in the output points themselves, so there is no
-//               scratch. An identity (ZZ = 0) takes no part and is written (0, 0)
+//               their ZZZ up, inverts once (fq_inv) and walks back by the same
+//               step (g1_affine_shared_inv, g1_mul.hpp). The prefix products
+//               wait in the output points themselves, so there is no scratch.
+//               An identity (ZZ = 0) takes no part and is written (0, 0)
 //
 // A multiplication costs 9 c W (doublings) + 14 W (adds, a few less for zero
 // digits) + 14 (B - 1) (table) field products: 4110, 3527, 3298, 3219, 3358 at
@@ -64,7 +65,8 @@
 //
 // As g1.hpp asks: each law is instantiated once per kernel in a rolled loop,
 // no register array is indexed at run time (the digits wait in LDS, the table
-// in global memory), indices are 64-bit, exactly n points are written.
+// in global memory), indices are 64-bit, exactly n points are written. Points
+// change form through g1.hpp's g1_affine_to_mont and g1_affine_to_form alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -22,17 +22,7 @@
 #include "quotient.hpp"
 #include "open.hpp"
 
-// ---- what the families share: argument checks
-// The checks several entries repeat, each under the entry's name f (need_columns: engine_internal.hpp).
-static void need_k(const std::string& f, uint32_t k) {
-    if (k < 1 || k > 28) fail(SVDW_ERANGE, f + ": k must be in [1, 28]");
-}
-static void need_pointer(const std::string& f, const void* p) { REQUIRE(p, f + ": null column pointer"); }
-// [o0, o1) (the output `out`) and [i0, i1) (`in`) do not meet.
-static void need_apart(const std::string& f, const char* out, uintptr_t o0, uintptr_t o1, const char* in, uintptr_t i0,
-                       uintptr_t i1) {
-    REQUIRE(i1 <= o0 || o1 <= i0, f + ": " + out + " overlaps " + in);
-}
+// (The argument checks the families share, need_k and the like: engine_internal.hpp.)
 // ---- lookup argument: multiplicities, permuted columns, their check (lookup.hpp)
 namespace {
 struct LkArgs {
@@ -820,7 +810,7 @@ int svdw_commit(svdw_ctx* c, uint32_t k, int form, int bases_form, const void* b
         sync(c);
         const uint32_t cb = result->window_bits, W = result->windows;
         const uint64_t n = 1ull << k, B = 1ull << (cb - 1), tasks = (uint64_t)ncols * W;
-        const uint64_t per = commit_task_bytes(n, B), cap = (uint64_t)c->opt.commit_scratch_mib << 20;
+        const uint64_t per = commit_task_bytes(n, B), cap = scratch_cap(c);
         const uint32_t T = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(cap / per, 1),
                                                         std::min<uint64_t>(tasks, 65535));
         // the call's window sums, then the arrays of one batch, each from a 128-byte boundary

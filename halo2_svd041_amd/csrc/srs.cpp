@@ -12,36 +12,24 @@
 #include "engine_internal.hpp"
 #include "srs.hpp"
 
-namespace {
-struct FbWindow {
-    uint32_t c, W;
-};
-}  // namespace
-
-static void srs_need_k(const std::string& f, uint32_t k) {
-    if (k < 1 || k > 28) fail(SVDW_ERANGE, f + ": k must be in [1, 28]");
-}
 // A scalar argument: four words, canonical.
 static Fr srs_scalar(const std::string& f, const char* name, const uint64_t w[4]) {
     const Fr x = fr_raw_words(w);
     REQUIRE(fr_reduced(x), f + ": " + name + " must be below p");
     return x;
 }
-// The base as Montgomery affine; (0, 0) is the identity in either form.
+// The base as Montgomery affine.
 static G1Affine fb_base_mont(const std::string& f, const void* base, int base_form) {
     G1Affine p;
     memcpy(&p, base, sizeof p);
     REQUIRE(fq_reduced(p.x) && fq_reduced(p.y), f + ": a base coordinate is not below q");
-    if (base_form == SVDW_FORM_CANONICAL) {
-        p.x = fq_to_mont(p.x);
-        p.y = fq_to_mont(p.y);
-    }
+    p = g1_affine_to_mont(p, base_form);
     REQUIRE(g1_affine_is_identity(p) || g1_on_curve(p), f + ": the base is not on the curve");
     return p;
 }
-static FbWindow fb_window(uint32_t window_bits, uint64_t n) {
+static G1Window fb_window(uint32_t window_bits, uint64_t n) {
     const uint32_t c = window_bits ? window_bits : fb_plan(n ? n : 1);
-    return FbWindow{c, fb_windows(c)};
+    return G1Window{c, fb_windows(c)};
 }
 // The context's table of (base, c), the base given as Montgomery affine: built
 // on the stream on first use, in the slot whose turn it is.
@@ -62,11 +50,9 @@ static const G1Affine* fb_table(svdw_ctx* c, const G1Affine& base, uint32_t cb) 
     t.c = cb;
     return (const G1Affine*)t.buf.p;
 }
-// The scratch cap of a call in bytes (the option "commit_scratch_mib").
-static uint64_t srs_cap(const svdw_ctx* c) { return (uint64_t)c->opt.commit_scratch_mib << 20; }
 // out[i] = [scalars[i]] base for i < split and out2[i - split] for the rest of the n,
 // through acc and pre (n entries each).
-static void fb_mul(svdw_ctx* c, const G1Affine* table, FbWindow w, const Fr* scalars, uint64_t n, int form,
+static void fb_mul(svdw_ctx* c, const G1Affine* table, G1Window w, const Fr* scalars, uint64_t n, int form,
                    int out_form, G1Affine* out, G1Xyzz* acc, Fq* pre, unsigned long long* cnt,
                    G1Affine* out2 = nullptr, uint64_t split = ~0ull) {
     FbMul a{};
@@ -97,17 +83,16 @@ int svdw_fixed_base_mul(svdw_ctx* c, int form, int base_form, const void* base, 
         if (window_bits == 1 || window_bits > kCommitMaxBits) fail(SVDW_ERANGE, f + ": window_bits must be 0 or in [2, 16]");
         need_device(c, f);
         memset(result, 0, sizeof *result);
-        const FbWindow w = fb_window(window_bits, n);
+        const G1Window w = fb_window(window_bits, n);
         result->window_bits = w.c;
         result->windows = w.W;
         result->points = n;
         if (!n) return;
         REQUIRE(scalars && out, "null argument");
-        const uintptr_t o0 = (uintptr_t)out, o1 = o0 + n * sizeof(G1Affine), i0 = (uintptr_t)scalars,
-                        i1 = i0 + n * sizeof(Fr);
-        REQUIRE(i1 <= o0 || o1 <= i0, f + ": out overlaps the scalars");
+        const uintptr_t o0 = (uintptr_t)out, i0 = (uintptr_t)scalars;
+        need_apart(f, "out", o0, o0 + n * sizeof(G1Affine), "the scalars", i0, i0 + n * sizeof(Fr));
         sync(c);
-        const uint64_t rows = std::min<uint64_t>(std::max<uint64_t>(srs_cap(c) / kFbRowBytes, 1), n);
+        const uint64_t rows = std::min<uint64_t>(std::max<uint64_t>(scratch_cap(c) / kFbRowBytes, 1), n);
         ensure_buf(c, c->srs.ws, rows * kFbRowBytes);
         G1Xyzz* acc = (G1Xyzz*)c->srs.ws.p;
         Fq* pre = (Fq*)(acc + rows);
@@ -130,20 +115,20 @@ int svdw_srs_setup(svdw_ctx* c, uint32_t k, const uint64_t s[4], int bases_form,
         REQUIRE(c && s && result, "null argument");
         check_form(bases_form);
         const Fr sc = srs_scalar(f, "s", s);
-        srs_need_k(f, k);
+        need_k(f, k);
         need_device(c, f);
         const uint64_t n = 1ull << k;
         if (g && g_lagrange) {
             const uintptr_t a0 = (uintptr_t)g, b0 = (uintptr_t)g_lagrange, len = n * sizeof(G1Affine);
-            REQUIRE(a0 + len <= b0 || b0 + len <= a0, f + ": g overlaps g_lagrange");
+            need_apart(f, "g", a0, a0 + len, "g_lagrange", b0, b0 + len);
         }
         memset(result, 0, sizeof *result);
         const uint32_t arrays = (g ? 1 : 0) + (g_lagrange ? 1 : 0);
         const uint64_t outputs = n * arrays;
-        const FbWindow w = fb_window(0, outputs);
+        const G1Window w = fb_window(0, outputs);
         const uint64_t per = std::max(arrays, 1u) * (kFbRowBytes + sizeof(Fr));   // a row of every array asked for
         const uint64_t rows = std::min<uint64_t>(
-            c->opt.srs_chunk_rows ? c->opt.srs_chunk_rows : std::max<uint64_t>(srs_cap(c) / per, 1), n);
+            c->opt.srs_chunk_rows ? c->opt.srs_chunk_rows : std::max<uint64_t>(scratch_cap(c) / per, 1), n);
         // s^n by k squarings: the secret is in the domain when it is 1
         const Fr sR = fr_to_mont(sc), one = fr_one_mont();
         Fr snR = sR;
@@ -208,17 +193,8 @@ static G1Xyzz srs_host_mul(const Fr& x) {
     return acc;
 }
 // The point as read from the device equals acc.
-static bool srs_same(const G1Xyzz& acc, G1Affine p, int bases_form) {
-    if (!fq_reduced(p.x) || !fq_reduced(p.y)) return false;
-    if (bases_form == SVDW_FORM_CANONICAL) {
-        p.x = fq_to_mont(p.x);
-        p.y = fq_to_mont(p.y);
-    }
-    return g1_eq_affine(acc, p);
-}
-// A nested call of the interface: its error becomes this call's.
-static void srs_nested(int rc) {
-    if (rc != SVDW_OK) fail(rc, g_err);
+static bool srs_same(const G1Xyzz& acc, const G1Affine& p, int bases_form) {
+    return fq_reduced(p.x) && fq_reduced(p.y) && g1_eq_affine(acc, g1_affine_to_mont(p, bases_form));
 }
 
 int svdw_check_srs(svdw_ctx* c, uint32_t k, int bases_form, const void* g, const void* g_lagrange,
@@ -228,7 +204,7 @@ int svdw_check_srs(svdw_ctx* c, uint32_t k, int bases_form, const void* g, const
         REQUIRE(c && s && rho && result, "null argument");
         check_form(bases_form);
         const Fr sc = srs_scalar(f, "s", s), rc = srs_scalar(f, "rho", rho);
-        srs_need_k(f, k);
+        need_k(f, k);
         need_device(c, f);
         REQUIRE(g && g_lagrange, "null argument");
         memset(result, 0, sizeof *result);
@@ -260,11 +236,11 @@ int svdw_check_srs(svdw_ctx* c, uint32_t k, int bases_form, const void* g, const
         const void* colp = col;
         const void* coefp = coeffs;
         svdw_commit_result cr;
-        srs_nested(svdw_commit(c, k, SVDW_FORM_MONTGOMERY, bases_form, g, &colp, 1, sums, &cr));
-        srs_nested(svdw_commit(c, k, SVDW_FORM_MONTGOMERY, bases_form, g_lagrange, &colp, 1, sums + 1, &cr));
+        nested(svdw_commit(c, k, SVDW_FORM_MONTGOMERY, bases_form, g, &colp, 1, sums, &cr));
+        nested(svdw_commit(c, k, SVDW_FORM_MONTGOMERY, bases_form, g_lagrange, &colp, 1, sums + 1, &cr));
         svdw_ntt_result nr;
-        srs_nested(svdw_ntt(c, k, k, SVDW_FORM_MONTGOMERY, 1, nullptr, &colp, 1, coeffs, &nr));
-        srs_nested(svdw_eval_polynomial(c, k, SVDW_FORM_MONTGOMERY, &coefp, 1, s, 1, value));
+        nested(svdw_ntt(c, k, k, SVDW_FORM_MONTGOMERY, 1, nullptr, &colp, 1, coeffs, &nr));
+        nested(svdw_eval_polynomial(c, k, SVDW_FORM_MONTGOMERY, &coefp, 1, s, 1, value));
         G1Affine hs[2];
         Fr hv;
         hipck(hipMemcpyAsync(hs, sums, sizeof hs, hipMemcpyDeviceToHost, c->st), "D2H");

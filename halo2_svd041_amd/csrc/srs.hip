@@ -6,44 +6,12 @@
 namespace svdw {
 namespace {
 
-// The signed digits of s as commit.hpp defines them: emit(window, |d| - 1,
-// negative) for every d != 0 (commit.hip's commit_digits, restated: that one is
-// private to the Pippenger kernels). The scalar is shifted down c bits per
-// window, so no word is indexed at run time.
-template <class Emit>
-__device__ __forceinline__ void fb_digits(Fr s, uint32_t c, uint32_t W, Emit&& emit) {
-    const uint32_t full = 1u << c, half = full >> 1;
-    uint32_t carry = 0;
-#pragma unroll 1
-    for (uint32_t w = 0; w < W; ++w) {
-        const uint32_t d = (s.w[0] & (full - 1)) + carry;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) s.w[i] = (s.w[i] >> c) | (s.w[i + 1] << (32 - c));
-        s.w[7] >>= c;
-        carry = d > half;
-        const uint32_t mag = carry ? full - d : d;
-        if (mag) emit(w, mag - 1, carry);
-    }
-}
-
-__device__ __forceinline__ G1Affine fb_store_form(G1Affine p, int form) {
-    if (form == 0) {
-        p.x = fq_from_mont(p.x);
-        p.y = fq_from_mont(p.y);
-    }
-    return p;
-}
-
 // Thread w: P_w = [2^(c w)] base by c w doublings, into table[w B].
 __global__ __launch_bounds__(128) void k_fb_windows(G1Affine base, int base_form, uint32_t c, uint32_t W,
                                                     G1Affine* table) {
     const uint32_t w = threadIdx.x;
     if (w >= W) return;
-    if (base_form == 0) {                                  // (0, 0) stays (0, 0)
-        base.x = fq_to_mont(base.x);
-        base.y = fq_to_mont(base.y);
-    }
-    G1Xyzz acc = g1_from_affine(base);
+    G1Xyzz acc = g1_from_affine(g1_affine_to_mont(base, base_form));
     const uint32_t nd = c * w;
 #pragma unroll 1
     for (uint32_t i = 0; i < nd; ++i) acc = g1_double(acc);
@@ -77,8 +45,9 @@ __global__ __launch_bounds__(kFbThreads) void k_fb_mul(FbMul a) {
         if (a.form != 0) s = fr_from_mont(s);
         if (fr_is_zero(s)) atomicAdd(&a.cnt[i >= a.split ? 2 : 0], 1ull);
         G1Xyzz acc = g1_identity();
-        fb_digits(s, a.c, a.W, [&](uint32_t w, uint32_t b, uint32_t neg) {
-            G1Affine p = a.table[((uint64_t)w << (a.c - 1)) + b];
+        g1_signed_digits(s, a.c, a.W, [&](uint32_t w, uint32_t mag, uint32_t neg) {
+            if (!mag) return;                              // a zero digit adds nothing
+            G1Affine p = a.table[((uint64_t)w << (a.c - 1)) + (mag - 1)];
             if (neg) p.y = fq_neg(p.y);
             acc = g1_add_mixed(acc, p);
         });
@@ -98,12 +67,7 @@ __global__ __launch_bounds__(kFbThreads) void k_fb_mul(FbMul a) {
             atomicAdd(&a.cnt[second ? 3 : 1], 1ull);
             r.x = r.y = fq_zero();
         } else {
-            const Fq i3 = fq_mul(inv, a.pre[i]);           // 1 / ZZZ_i
-            inv = fq_mul(inv, acc.zzz);
-            const Fq i2 = fq_sqr(fq_mul(acc.zz, i3));      // 1 / ZZ = (ZZ / ZZZ)^2
-            r.x = fq_mul(acc.x, i2);
-            r.y = fq_mul(acc.y, i3);
-            r = fb_store_form(r, a.base_form);
+            r = g1_affine_shared_inv(acc, a.pre[i], inv, a.base_form);
         }
         if (second) a.out2[i - a.split] = r;
         else a.out[i] = r;
@@ -147,8 +111,6 @@ __global__ __launch_bounds__(kSrsThreads) void k_srs_lagrange(PowTable dom, Fr s
         st_fr(out + j, mont_mul(mont_mul(coef, w), dinv));
     }
 }
-
-inline unsigned blocks_of(uint64_t n, uint64_t per) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace
 

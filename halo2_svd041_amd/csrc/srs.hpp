@@ -2,11 +2,11 @@
 // fixed BN254 G1 base (g1.hpp) by n unrelated scalars, and the two scalar
 // columns ParamsKZG::setup multiplies the generator by, s^i and l_i(s).
 //
-// Fixed-base multiplication with signed c-bit digits, commit.hpp's split: a
-// scalar, as a canonical integer below r < 2^254, is cut into W = ceil(255 / c)
-// digits d_w in (-2^(c-1), 2^(c-1)] with carry (no carry leaves the top
-// window). The base is known, so every digit's multiple is looked up, not
-// accumulated: the table
+// Fixed-base multiplication with signed c-bit digits (g1_signed_digits,
+// g1_mul.hpp): a scalar, as a canonical integer below r < 2^254, is cut into
+// W = ceil(255 / c) digits d_w in (-2^(c-1), 2^(c-1)] with carry (no carry
+// leaves the top window). The base is known, so every digit's multiple is
+// looked up, not accumulated: the table
 //
 //   T[w][d - 1] = [d 2^(c w)] base,  1 <= d <= B = 2^(c-1),  w < W
 //
@@ -30,6 +30,7 @@
 //                   invert    one fq_inv of the product of the group's ZZZ
 //                   backward  1 / ZZZ_i = inv pre[i], inv <- inv ZZZ_i, then
 //                             1 / ZZ = (ZZ / ZZZ)^2, x = X / ZZ, y = Y / ZZZ
+//                             (g1_affine_shared_inv, g1_mul.hpp)
 //                 An identity accumulator (ZZZ = 0) takes no part in the product
 //                 and is written as (0, 0). One launch may serve two arrays
 //                 (FbMul::split): the setup multiplies both columns of a piece
@@ -70,7 +71,8 @@
 //
 // As g1.hpp and commit.hpp ask: loops over points stay rolled, no register
 // array is indexed at run time (the digits shift the scalar down), row indices
-// are 64-bit, and exactly n points are written.
+// are 64-bit, and exactly n points are written. The base and the outputs change
+// form through g1.hpp's g1_affine_to_mont and g1_affine_to_form alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -88,6 +90,10 @@ static constexpr uint32_t kSrsInvGroup = 8;                // rows per thread of
 static constexpr unsigned kSrsThreads = 64;
 
 inline uint32_t fb_windows(uint32_t c) { return (255 + c - 1) / c; }
+// The window of a call: its bits c and W = fb_windows(c).
+struct G1Window {
+    uint32_t c, W;
+};
 inline uint64_t fb_table_points(uint32_t c) { return (uint64_t)fb_windows(c) << (c - 1); }
 // The window of n outputs: the c in [2, kFbMaxTableBits] with the fewest
 // products, 10 W per output and 800 per table entry (an inversion and a

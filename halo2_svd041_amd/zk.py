@@ -940,14 +940,34 @@ class Context:
                                    out.data_ptr() if n else None, log_samples, seed & _M64, ct.byref(r)))
         return {"rows_checked": r.rows_checked, "row_failures": r.row_failures}
 
+    # ---- what the G1 methods (commitments, the SRS, G1 transforms) share
+    @staticmethod
+    def _u8_rows(t, width: int) -> bool:                    # a contiguous [., width] u8 device tensor
+        import torch
+        return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+                and t.dim() == 2 and t.shape[1] == width)
+
+    @classmethod
+    def _points_tensor(cls, what: str, t, rows: int, at_least: bool = False, shown: Optional[str] = None):
+        # shown: the row count as the message names it, where that is not the number
+        if not cls._u8_rows(t, 64) or (t.shape[0] < rows if at_least else t.shape[0] != rows):
+            raise SvdwError(-1, f"{what} must be a contiguous uint8 device tensor "
+                                f"[{'>= ' if at_least else ''}{shown or rows}, 64]")
+
+    @classmethod
+    def _cells_tensor(cls, what: str, t):
+        if not cls._u8_rows(t, 32):
+            raise SvdwError(-1, f"{what} must be a contiguous uint8 device tensor [n, 32]")
+
+    @staticmethod
+    def _result(r) -> dict:                                 # a result struct as a dict, without its padding
+        return {name: getattr(r, name) for name, _ in r._fields_ if name != "_pad"}
+
     # ---- commitments (include/svdw.h, "commitments"; parity unpinned)
     def _commit_args(self, columns, bases, k: int):
-        import torch
         rows = 1 << k if 0 <= k < 32 else 0
         cp, n, dev = self._column_pointers("columns", columns, rows)
-        if (not isinstance(bases, torch.Tensor) or not bases.is_cuda or bases.dtype != torch.uint8
-                or not bases.is_contiguous() or tuple(bases.shape) != (rows, 64)):
-            raise SvdwError(-1, "bases must be a contiguous uint8 device tensor [2^k, 64]")
+        self._points_tensor("bases", bases, rows, shown="2^k")
         return cp, n, dev or bases.device
 
     def commit(self, columns, bases, k: int, form: str = "canonical", bases_form: str = "montgomery", out=None):
@@ -963,15 +983,13 @@ class Context:
         cp, n, dev = self._commit_args(columns, bases, k)
         if out is None:
             out = torch.empty((n, 64), dtype=torch.uint8, device=dev)
-        if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.uint8
-                or not out.is_contiguous() or tuple(out.shape) != (n, 64)):
-            raise SvdwError(-1, "out must be a contiguous uint8 device tensor [ncols, 64]")
+        self._points_tensor("out", out, n, shown="ncols")
         r = CommitResult()
         _after_torch(self)
         check(lib().svdw_commit(self._h, k, _form(form), _form(bases_form), bases.data_ptr(), cp, n,
                                 out.data_ptr() if n else None, ct.byref(r)))
         _before_torch(self)
-        return out, {k_: getattr(r, k_) for k_, _ in CommitResult._fields_}
+        return out, self._result(r)
 
     def commit_lagrange(self, columns, g_lagrange, k: int, form: str = "canonical", out=None):
         """ParamsKZG::commit_lagrange of every column (cells in Lagrange form) on
@@ -990,26 +1008,15 @@ class Context:
         columns and the bases, bit-serial and division-free, sharing nothing with
         commit (svdw_check_commit): columns_checked, commit_failures,
         bases_checked, bases_off_curve."""
-        import torch
         cp, n, _ = self._commit_args(columns, bases, k)
-        if (not isinstance(commitments, torch.Tensor) or not commitments.is_cuda or commitments.dtype != torch.uint8
-                or not commitments.is_contiguous() or tuple(commitments.shape) != (n, 64)):
-            raise SvdwError(-1, "commitments must be a contiguous uint8 device tensor [ncols, 64]")
+        self._points_tensor("commitments", commitments, n, shown="ncols")
         r = CommitCheck()
         _after_torch(self)
         check(lib().svdw_check_commit(self._h, k, _form(form), _form(bases_form), bases.data_ptr(), cp, n,
                                       commitments.data_ptr() if n else None, ct.byref(r)))
-        return {k_: getattr(r, k_) for k_, _ in CommitCheck._fields_}
+        return self._result(r)
 
     # ---- the SRS (include/svdw.h, "SRS"; parity pinned by the reference's file)
-    @staticmethod
-    def _points_tensor(what: str, t, rows: int, at_least: bool = False):
-        import torch
-        if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous()
-                or t.dim() != 2 or t.shape[1] != 64 or (t.shape[0] < rows if at_least else t.shape[0] != rows)):
-            raise SvdwError(-1, f"{what} must be a contiguous uint8 device tensor [{'>= ' if at_least else ''}{rows}, 64]")
-        return t
-
     def fixed_base_mul(self, base, scalars, form: str = "canonical", base_form: str = "montgomery",
                        window_bits: int = 0, out=None):
         """(points, result): [scalars[i]] base for every cell of `scalars`, a
@@ -1024,9 +1031,7 @@ class Context:
         raw = bytes(base) if isinstance(base, (bytes, bytearray)) else np.ascontiguousarray(base, dtype=np.uint8).tobytes()
         if len(raw) != 64:
             raise SvdwError(-1, "base must be the 64 bytes of one affine point")
-        if (not isinstance(scalars, torch.Tensor) or not scalars.is_cuda or scalars.dtype != torch.uint8
-                or not scalars.is_contiguous() or scalars.dim() != 2 or scalars.shape[1] != 32):
-            raise SvdwError(-1, "scalars must be a contiguous uint8 device tensor [n, 32]")
+        self._cells_tensor("scalars", scalars)
         n = scalars.shape[0]
         if out is None:
             out = torch.empty((n, 64), dtype=torch.uint8, device=scalars.device)
@@ -1036,7 +1041,7 @@ class Context:
         check(lib().svdw_fixed_base_mul(self._h, f, bf, raw, scalars.data_ptr() if n else None,
                                         n, window_bits, out.data_ptr() if n else None, ct.byref(r)))
         _before_torch(self)
-        return out, {k_: getattr(r, k_) for k_, _ in FixedBaseResult._fields_}
+        return out, self._result(r)
 
     def srs_setup(self, k: int, s: int, bases_form: str = "montgomery", g=True, g_lagrange=True):
         """(g, g_lagrange, result): ParamsKZG::setup(k, .) for the secret s (an
@@ -1063,7 +1068,7 @@ class Context:
         check(lib().svdw_srs_setup(self._h, k, sw, bf, *[t.data_ptr() if t is not None else None
                                                                         for t in outs], ct.byref(r)))
         _before_torch(self)
-        return outs[0], outs[1], {k_: getattr(r, k_) for k_, _ in SrsResult._fields_ if k_ != "_pad"}
+        return outs[0], outs[1], self._result(r)
 
     def check_srs(self, g, g_lagrange, k: int, s: int, rho: int, bases_form: str = "montgomery") -> dict:
         """Device check of an SRS's two arrays against its secret s with the
@@ -1078,7 +1083,7 @@ class Context:
         _after_torch(self)
         check(lib().svdw_check_srs(self._h, k, bf, g.data_ptr(), g_lagrange.data_ptr(), sw, rw,
                                    ct.byref(r)))
-        return {k_: getattr(r, k_) for k_, _ in SrsCheck._fields_}
+        return self._result(r)
 
     # ---- G1 transforms (include/svdw.h, "G1 transforms"; parity pinned by the reference's file)
     def g1_mul(self, points, scalars, form: str = "canonical", bases_form: str = "montgomery", window_bits: int = 0,
@@ -1092,9 +1097,7 @@ class Context:
         windows, points, zero_scalars, identity_inputs, identity_outputs."""
         import torch
         f, bf = _form(form), _form(bases_form)
-        if (not isinstance(scalars, torch.Tensor) or not scalars.is_cuda or scalars.dtype != torch.uint8
-                or not scalars.is_contiguous() or scalars.dim() != 2 or scalars.shape[1] != 32):
-            raise SvdwError(-1, "scalars must be a contiguous uint8 device tensor [n, 32]")
+        self._cells_tensor("scalars", scalars)
         n = scalars.shape[0]
         self._points_tensor("points", points, n)
         if out is None:
@@ -1105,7 +1108,7 @@ class Context:
         check(lib().svdw_g1_mul(self._h, f, bf, points.data_ptr() if n else None, scalars.data_ptr() if n else None,
                                 n, window_bits, out.data_ptr() if n else None, ct.byref(r)))
         _before_torch(self)
-        return out, {k_: getattr(r, k_) for k_, _ in G1MulResult._fields_}
+        return out, self._result(r)
 
     def g1_fft(self, points, k: int, inverse: bool = False, bases_form: str = "montgomery", out=None):
         """(out, result): the FFT over G1 of the 2^k affine points, natural
@@ -1125,7 +1128,7 @@ class Context:
         _after_torch(self)
         check(lib().svdw_g1_fft(self._h, k, bf, 1 if inverse else 0, points.data_ptr(), out.data_ptr(), ct.byref(r)))
         _before_torch(self)
-        return out, {k_: getattr(r, k_) for k_, _ in G1FftResult._fields_}
+        return out, self._result(r)
 
     def check_lagrange(self, g, g_lagrange, k: int, rho: int, bases_form: str = "montgomery") -> dict:
         """Device check that g_lagrange is the Lagrange form of g, with the
@@ -1140,7 +1143,7 @@ class Context:
         r = LagrangeCheck()
         _after_torch(self)
         check(lib().svdw_check_lagrange(self._h, k, bf, g.data_ptr(), g_lagrange.data_ptr(), rw, ct.byref(r)))
-        return {k_: getattr(r, k_) for k_, _ in LagrangeCheck._fields_ if k_ != "_pad"}
+        return self._result(r)
 
     # ---- quotient polynomial (include/svdw.h, "quotient"; parity unpinned)
     _QUOTIENT_FAMILIES = ("advice", "selectors", "perm_columns", "sigma", "perm_z", "lookup_input", "lookup_table",

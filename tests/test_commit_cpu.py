@@ -163,6 +163,39 @@ def test_digit_edge_scalars_hit_every_edge(c):
     assert any(raw[s][-1] == top - 1 for s in reached) and signed_digits(min(reached) - 1, c, w)[-1] == top - 1
 
 
+def _device_recoder(s: int, c: int, windows: int):
+    """g1_signed_digits (csrc/g1_mul.hpp) restated word for word: eight 32-bit
+    words shifted down c bits per window, the digit from the low word and the
+    carry, and what it emits for every window: (magnitude, negative)."""
+    w = [(s >> (32 * i)) & 0xFFFFFFFF for i in range(8)]
+    full, half, carry, out = 1 << c, 1 << (c - 1), 0, []
+    for _ in range(windows):
+        d = (w[0] & (full - 1)) + carry
+        for i in range(7):
+            w[i] = (w[i] >> c) | ((w[i + 1] << (32 - c)) & 0xFFFFFFFF)
+        w[7] >>= c
+        carry = 1 if d > half else 0
+        out.append((full - d if carry else d, carry))
+    return out, carry, w
+
+
+@pytest.mark.parametrize("c", range(2, 17))
+def test_device_recoder_restates_the_signed_digits(c):
+    """The one recoder the commit, SRS and G1 transform kernels share gives the
+    digits of commit_cases.signed_digits at 0, 1, r - 1 and every window's half
+    and half + 1 edge: they sum back to the scalar, zero digits are emitted with
+    magnitude 0, and nothing is left above the top window."""
+    windows, half = -(-255 // c), 1 << (c - 1)
+    edges = [0, 1, R - 1] + [v << (c * i) for i in range(windows) for v in (half, half + 1)]
+    for s in (v for v in edges if v < R):
+        emitted, carry, left = _device_recoder(s, c, windows)
+        digits = [-mag if neg else mag for mag, neg in emitted]
+        assert digits == signed_digits(s, c, windows), (c, s)
+        assert sum(d << (c * i) for i, d in enumerate(digits)) == s
+        assert carry == 0 and not any(left), (c, s)
+        assert all(0 <= mag <= half and (not neg or mag < half) for mag, neg in emitted)
+
+
 def test_gpu_cases_cover_every_regime():
     """The cases test_commit_gpu.py takes from GPU_CASES reach every window
     size, every depth of the slot tree up to k = 20's, the loops that take a
