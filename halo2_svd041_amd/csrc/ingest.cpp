@@ -43,30 +43,50 @@ struct DevText {                  // small host reads of the device text
         if (len) hipck(hipMemcpy(b.data(), t + at, len, hipMemcpyDeviceToHost), "D2H");
         return b;
     }
+    // byte i of the text (-1 past its end), read forward in 256-byte pieces
+    // that str and next_nonws share
+    uint64_t w0 = 0;
+    std::vector<uint8_t> w;
+    int byte(uint64_t i) {
+        if (i >= n) return -1;
+        if (i < w0 || i >= w0 + w.size()) { w = get(i, 256); w0 = i; }
+        return w[i - w0];
+    }
     // the string starting with the quote at `at`: its content (escapes as the
     // host parser reads them) and the position just past the closing quote
     bool str(uint64_t at, std::string* s, uint64_t* end) {
-        uint64_t p = at + 1;
         bool esc = false;
-        for (;;) {
-            std::vector<uint8_t> b = get(p, 256);
-            if (b.empty()) return false;
-            for (size_t k = 0; k < b.size(); ++k, ++p) {
-                if (esc) { s->push_back((char)b[k]); esc = false; continue; }
-                if (b[k] == '\\') { esc = true; continue; }
-                if (b[k] == '"') { *end = p + 1; return true; }
-                s->push_back((char)b[k]);
+        for (uint64_t p = at + 1;; ++p) {
+            const int b = byte(p);
+            if (b < 0) return false;
+            if (esc) { s->push_back((char)b); esc = false; continue; }
+            if (b == '\\') { esc = true; continue; }
+            if (b == '"') { *end = p + 1; return true; }
+            s->push_back((char)b);
+        }
+    }
+    int next_nonws(uint64_t at, uint64_t* pos = nullptr) {
+        for (;; ++at) {
+            const int b = byte(at);
+            if (b < 0) return -1;
+            if (!(b == ' ' || b == '\n' || b == '\r' || b == '\t')) {
+                if (pos) *pos = at;
+                return b;
             }
         }
     }
-    int next_nonws(uint64_t at) {
-        for (;;) {
-            std::vector<uint8_t> b = get(at, 256);
-            if (b.empty()) return -1;
-            for (uint8_t x : b)
-                if (!(x == ' ' || x == '\n' || x == '\r' || x == '\t')) return x;
-            at += b.size();
+    // the last non-blank byte before `at` (0: none), walking back as next_nonws walks
+    // forward. Its copies are its own (the shared piece holds bytes read forward only):
+    // one per depth-1 string, more only behind a blank run of 256 bytes or longer
+    int prev_nonws(uint64_t at) {
+        while (at > 0) {
+            const uint64_t lo = at >= 256 ? at - 256 : 0;
+            std::vector<uint8_t> b = get(lo, at - lo);
+            for (size_t q = b.size(); q-- > 0;)
+                if (!(b[q] == ' ' || b[q] == '\n' || b[q] == '\r' || b[q] == '\t')) return b[q];
+            at = lo;
         }
+        return 0;
     }
 };
 }  // namespace
@@ -140,17 +160,19 @@ int svdw_parse_svd_input_device(svdw_ctx* c, const void* text, uint64_t len, int
             std::string k;
             uint64_t end = 0;
             REQUIRE(dt.str(kpos[j], &k, &end), "svd input: unterminated string" + at(kpos[j]));
-            const int nx = dt.next_nonws(end);
+            uint64_t colon = 0;
+            const int nx = dt.next_nonws(end, &colon);
             // a key follows '{' or ','; a string value follows ':' and is not followed by ':'
-            std::vector<uint8_t> back = dt.get(kpos[j] >= 256 ? kpos[j] - 256 : 0, kpos[j] >= 256 ? 256 : kpos[j]);
-            int pv = 0;
-            for (size_t q = back.size(); q-- > 0;)
-                if (!(back[q] == ' ' || back[q] == '\n' || back[q] == '\r' || back[q] == '\t')) { pv = back[q]; break; }
+            const int pv = dt.prev_nonws(kpos[j]);
             if (pv == ':') {
                 REQUIRE(nx != ':', "svd input: expected ',' or '}'" + at(end));
                 continue;
             }
             REQUIRE(nx == ':', "svd input: expected ':'" + at(end));
+            // m, u, v, d hold arrays (host parser: array() expects '['); a literal or a
+            // string there has no number and would pass for an empty d
+            if (k == "m" || k == "u" || k == "v" || k == "d")
+                REQUIRE(dt.next_nonws(colon + 1) == '[', "svd input: expected '['" + at(colon + 1));
             mem.push_back({kpos[j], k});
         }
         const uint64_t nsl = sl[0];

@@ -159,7 +159,10 @@ __device__ __forceinline__ Kinds kinds(uint8_t c, uint8_t p, int st, int dp) {
     Kinds k{false, false, false};
     if (st) return k;
     if (num_char(c)) {
-        k.num = !num_char(p) && !is_alpha(p);         // (not the 'e' of true / false)
+        // (not the 'e' of true / false: that spares a spurious token and nothing else, no
+        // result depends on it -- such a token lies in an unknown member or in a text
+        // refused for its structure)
+        k.num = !num_char(p) && !is_alpha(p);
     } else if (c == '[') {
         k.row = dp == 2;
     } else if (c == '"') {
@@ -320,7 +323,9 @@ __device__ __forceinline__ uint32_t struct_bad(const Txt& t, uint64_t i, int dp)
     const uint8_t p = prev_nonws(t, i);
     if (dp >= 2) {
         if (num_char(c)) return 0;                   // tokens: parse_number + separators
-        const bool elem_end = p == ']' || is_digit(p) || p == '.';
+        // (a token's last byte is parse_number's to judge, "1e," is a bad number as on the host;
+        // a string is counted once, at its opening quote, not again at the ',' or ']' after it)
+        const bool elem_end = p == ']' || num_char(p) || p == '"';
         if (c == '[') return (p == '[' || p == ',') ? 0 : 1;
         if (c == ']') return (p == '[' || elem_end) ? 0 : 1;
         if (c == ',') return elem_end ? 0 : 1;
