@@ -13,12 +13,13 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libsvdw.so")
 SOURCES = ["kernels.hip", "gemm.hip", "ingest_dev.hip", "export.hip", "lookup.hip", "lookup_product.hip",
            "permutation_product.hip", "permutation_cycles.hip", "ntt.hip", "quotient.hip", "commit.hip", "open.hip",
-           "srs.hip", "g1_fft.hip", "svd.hip", "engine.cpp", "context.cpp", "export.cpp", "ingest.cpp", "gemm.cpp", "circuit.cpp", "prover.cpp",
+           "srs.hip", "g1_fft.hip", "svd.hip", "engine.cpp", "witness.cpp", "context.cpp", "export.cpp", "ingest.cpp", "gemm.cpp", "circuit.cpp", "prover.cpp",
            "srs.cpp", "g1_fft.cpp", "svd.cpp"]
 HEADERS = ["fr.hpp", "pow_table.hpp", "prog.hpp", "kernels.hpp", "kernel_common.hpp", "gemm.hpp", "crt_tables.hpp",
            "ingest.hpp", "ingest_dev.hpp", "export.hpp", "lookup.hpp", "grand_product.hpp", "lookup_product.hpp",
            "permutation_product.hpp", "permutation_cycles.hpp", "ntt.hpp", "quotient.hpp", "fq.hpp", "g1.hpp",
-           "g1_mul.hpp", "commit.hpp", "open.hpp", "srs.hpp", "g1_fft.hpp", "svd.hpp", "engine_internal.hpp"]
+           "g1_mul.hpp", "commit.hpp", "open.hpp", "srs.hpp", "g1_fft.hpp", "svd.hpp", "engine_internal.hpp",
+           "program_builder.hpp"]
 ARCH = os.environ.get("SVDW_OFFLOAD_ARCH", "gfx950")
 
 

@@ -1,4 +1,4 @@
-// The context apart from the witness engine (engine.cpp): its lifetime and
+// The context apart from the witness engine (engine.cpp, witness.cpp): its lifetime and
 // device memory, the two lanes, options, the hand-off with a caller's stream,
 // completion marks, the event profiler, and the C ABI entries of these.
 #include <stdlib.h>
@@ -9,7 +9,7 @@
 
 void sync(svdw_ctx* c) {
     if (c->dry) return;
-    REQUIRE(!c->call.capturing, "internal: synchronisation during graph capture");
+    REQUIRE(!c->vmg.capturing, "internal: synchronisation during graph capture");
     hipck(hipStreamSynchronize(c->st), "hipStreamSynchronize");
     hipck(hipStreamSynchronize(c->st2), "hipStreamSynchronize");
     if (c->st3) hipck(hipStreamSynchronize(c->st3), "hipStreamSynchronize");
@@ -44,7 +44,7 @@ void clear_streams(svdw_ctx* c) {
 }
 void ensure_buf(svdw_ctx* c, DBuf& b, size_t bytes) {
     if (c->dry || b.cap >= bytes) return;
-    REQUIRE(!c->call.capturing, "internal: allocation during graph capture");
+    REQUIRE(!c->vmg.capturing, "internal: allocation during graph capture");
     ++c->epoch;
     sync(c);
     if (b.p) hipck(hipFree(b.p), "hipFree");
@@ -298,9 +298,7 @@ int svdw_ctx_reset(svdw_ctx* c) {
         REQUIRE(c, "null ctx");
         sync(c);
         clear_streams(c);
-        c->call.pre.clear();
-        c->call.pre_wait_st = nullptr;
-        c->call.pre_wait_ev = nullptr;
+        c->call.reset();
     });
 }
 // Stream-ordered hand-off with a caller's stream (e.g. torch's current stream):

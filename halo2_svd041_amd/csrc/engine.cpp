@@ -1,7 +1,8 @@
 // The witness engine of the SVD-verify library and its C ABI entries
-// (include/svdw.h): the program builder, cell-stream memory, views, stage
-// launches and batches, the checker's notes, the reference functions, the two
-// witness calls, the captured graph and the reference entries. The context's
+// (include/svdw.h): cell-stream memory, views, stage launches and batches, the
+// checker's notes, the reference functions and their entries. The program
+// builder is in program_builder.hpp (this file alone includes it), the two
+// witness calls and the captured graph in witness.cpp. The context's
 // lifetime, lanes, options, stream hand-off, marks and profiling are in
 // context.cpp, read-out in export.cpp, text ingest in ingest.cpp, the exact
 // product in gemm.cpp, the calls on a finished witness (checker, physical
@@ -26,319 +27,10 @@
 
 #include "engine_internal.hpp"
 
-// ------------------------------------------------------- host big integers
-// Unsigned 256-bit integers (BigUint bounds of the range checks).
-struct BigU {
-    Fr v;
-};
-static BigU big_from_words(const uint64_t w[4]) { return BigU{fr_raw_words(w)}; }
-static BigU big_from_u128(unsigned __int128 x) {
-    BigU b;
-    b.v = fr_zero();
-    for (int i = 0; i < 4; ++i) b.v.w[i] = (uint32_t)(x >> (32 * i));
-    return b;
-}
-static int big_bits(const BigU& b) {
-    for (int i = 7; i >= 0; --i)
-        if (b.v.w[i]) return 32 * i + 32 - __builtin_clz(b.v.w[i]);
-    return 0;
-}
-static bool big_is_zero(const BigU& b) { return big_bits(b) == 0; }
-static BigU big_pow2(uint32_t k) {     // k < 256
-    BigU b;
-    b.v = fr_zero();
-    b.v.w[k / 32] = 1u << (k % 32);
-    return b;
-}
-static BigU big_add_u32(const BigU& a, uint32_t s) {
-    BigU r;
-    Fr t = fr_from_u64(s);
-    if (add256(r.v, a.v, t)) fail(SVDW_ERANGE, "bound overflows 256 bits");
-    return r;
-}
-static BigU big_sub_u32(const BigU& a, uint32_t s) {
-    BigU r;
-    Fr t = fr_from_u64(s);
-    if (sub256(r.v, a.v, t)) fail(SVDW_EINVAL, "bound underflow (bound must be >= 1)");
-    return r;
-}
-static BigU big_shl1(const BigU& a) {
-    BigU r;
-    if (a.v.w[7] >> 31) fail(SVDW_ERANGE, "bound overflows 256 bits");
-    for (int i = 7; i > 0; --i) r.v.w[i] = (a.v.w[i] << 1) | (a.v.w[i - 1] >> 31);
-    r.v.w[0] = a.v.w[0] << 1;
-    return r;
-}
-// biguint_to_fe: value mod p.
-static Fr big_to_fr(const BigU& b) {
-    Fr x = b.v, t;
-    while (!sub256(t, x, fr_p())) x = t;   // at most a few subtractions (< 2^256)
-    return x;
-}
-static Fr pow2_fr(uint32_t k) {
-    Fr x = fr_from_u64(1);
-    for (uint32_t i = 0; i < k; ++i) x = fr_add(x, x);
-    return x;
-}
-static Fr fr_from_words(const uint64_t w[4]) { return big_to_fr(big_from_words(w)); }
+#include "program_builder.hpp"
 
-// ------------------------------------------------------- program builder
-// Replays halo2-base 0.4.1 gadgets on symbolic per-element values
-// (SURVEY.md Appendix A); produces the micro-ops, cell and lookup slot ops.
-struct PB {
-    StageArgs a;
-    uint32_t lb;
-    // What MockProver checks on an element's C cells (svdw_check_gates), as
-    // check words (kernels.hpp CHK_*): the offsets where halo2-base's
-    // assign_region enables a basic gate a + b*c = d, and the copy constraints
-    // -- a value's later cells against its first cell, a loaded value's first
-    // cell against its source cell (view), range_check's last running sum
-    // against the checked value (RangeChip::range_check's constrain_equal).
-    std::vector<uint32_t> chk;
-    // halo2-base's equality records of an element's cells (svdw_equalities), in
-    // assign order: a Constant cell's (cell, value), an Existing cell's (source
-    // cell, cell), range_check's constrain_equal(a, last running sum) -- as eq
-    // words (kernels.hpp EQ_*): a constant slot, an earlier cell of the element,
-    // the element's cell of a view (RegionChecks::esrc), or an external cell
-    std::vector<uint32_t> eq;
-    int kext = -1;            // constant slot holding an external cell's value (init_rand)
-    bool vsrc[kMaxViews] = {true, true};   // false: the view holds values produced here
-    static constexpr int EQ_AUTO = -1, EQ_WIT = -2;
-    bool kconst = true;       // its constant-source cells are halo2-base Constants
-    int8_t vload[kMaxV];      // view a value was loaded from (-1: computed)
-    int16_t fullc[kMaxV];     // first cell holding the value in full (-1: none)
-    void gate(uint32_t at) { chk.push_back(chk_gate(at)); }
-    void copy_of(uint8_t v, uint32_t at) {    // cell `at` must equal value v's cell
-        if (fullc[v] >= 0) chk.push_back(chk_copy((uint32_t)fullc[v], at));
-        else if (vload[v] >= 0) chk.push_back(chk_view((uint32_t)vload[v], at));
-    }
-    explicit PB(uint32_t lookup_bits) : lb(lookup_bits) {
-        memset(&a, 0, sizeof(a));
-        memset(vload, -1, sizeof vload);
-        for (auto& f : fullc) f = -1;
-    }
+Fr fr_from_words(const uint64_t w[4]) { return big_to_fr(big_from_words(w)); }
 
-    uint8_t newv() {
-        if (a.nv >= (uint32_t)kMaxV) fail(SVDW_ERANGE, "stage needs too many element values");
-        return (uint8_t)a.nv++;
-    }
-    uint8_t kidx(const Fr& c) {
-        for (uint32_t k = 0; k < a.nk; ++k)
-            if (fr_eq(a.K[k], c)) return (uint8_t)k;
-        if (a.nk >= (uint32_t)kMaxK) fail(SVDW_ERANGE, "stage needs too many constants");
-        a.K[a.nk] = c;
-        return (uint8_t)a.nk++;
-    }
-    uint8_t K(const Fr& c) { return KSRC + kidx(c); }
-    uint8_t K(uint64_t c) { return K(fr_from_u64(c)); }
-    void op(uint8_t code, uint8_t dst, uint8_t x, uint8_t y, uint16_t p0 = 0, uint16_t p1 = 0) {
-        if (a.nmo >= (uint32_t)kMaxMicro) fail(SVDW_ERANGE, "stage needs too many micro-ops");
-        a.mo[a.nmo++] = MicroOp{code, dst, x, y, p0, p1};
-    }
-    static SlotOp slot(uint8_t src, uint32_t lo, uint32_t nbits) {
-        if (nbits >= 256) nbits = 0;
-        return SlotOp{src, (uint8_t)lo, (uint8_t)nbits, 0};
-    }
-    // cell `at` holds a copy of value v (QuantumCell::Existing of v's cell)
-    void eq_of_value(uint8_t v, uint32_t at) {
-        if (vload[v] >= 0 && vsrc[vload[v]]) eq.push_back(eq_word(EQ_VIEW, (uint32_t)vload[v], at));
-        else if (fullc[v] >= 0) eq.push_back(eq_word(EQ_LOCAL, (uint32_t)fullc[v], at));
-    }
-    // eqk: EQ_AUTO -- a Constant for a constant slot (kconst), the external cell
-    // for kext, an Existing copy for a value's full cell seen before (or loaded
-    // from a source view), else a Witness; EQ_WIT: a Witness; >= 0: an Existing
-    // copy of the element's cell eqk (range_check's last limb)
-    void cell(uint8_t src, uint32_t lo = 0, uint32_t nbits = 0, int eqk = EQ_AUTO) {
-        if (a.C >= (uint32_t)kMaxAdv) fail(SVDW_ERANGE, "stage has too many cells per element (raise lookup_bits)");
-        const SlotOp s = slot(src, lo, nbits);
-        if (eqk >= 0) {
-            eq.push_back(eq_word(EQ_LOCAL, (uint32_t)eqk, a.C));
-        } else if (eqk == EQ_AUTO) {
-            if (src >= KSRC) {
-                const int k = src - KSRC;
-                if (k == kext) eq.push_back(eq_word(EQ_EXT, 0, a.C));
-                else if (kconst) eq.push_back(eq_word(EQ_CONST, (uint32_t)k, a.C));
-            } else if (s.lo == 0 && s.nbits == 0) {
-                eq_of_value(src, a.C);
-            }
-        }
-        if (src < KSRC && s.lo == 0 && s.nbits == 0) {      // the value itself: a copy or its first cell
-            copy_of(src, a.C);
-            if (fullc[src] < 0) fullc[src] = (int16_t)a.C;
-        }
-        a.adv[a.C++] = s;
-    }
-    void look(uint8_t src, uint32_t lo = 0, uint32_t nbits = 0) {
-        if (a.L >= (uint32_t)kMaxLk) fail(SVDW_ERANGE, "stage has too many lookups per element (raise lookup_bits)");
-        a.lk[a.L++] = slot(src, lo, nbits);
-    }
-    // --- element values
-    uint8_t load(int view_idx) {
-        uint8_t v = newv();
-        op(MO_LOAD, v, (uint8_t)view_idx, 0);
-        vload[v] = (int8_t)view_idx;
-        return v;
-    }
-    uint8_t addk(uint8_t x, const Fr& k) {
-        uint8_t t = newv();
-        op(MO_ADDK, t, x, kidx(k));
-        return t;
-    }
-    // --- GateChip
-    uint8_t g_add_k(uint8_t x, const Fr& k) {       // add(x, Constant(k)): [x, k, 1, x+k]
-        uint8_t t = addk(x, k);
-        gate(a.C);
-        cell(x); cell(K(k)); cell(K(1)); cell(t);
-        return t;
-    }
-    uint8_t g_sub_k(uint8_t x, const Fr& k) {       // sub(x, Constant(k)): [x-k, k, 1, x]
-        uint8_t d = addk(x, fr_neg(k));
-        gate(a.C);
-        cell(d); cell(K(k)); cell(K(1)); cell(x);
-        return d;
-    }
-    uint8_t g_sub(uint8_t x, uint8_t y) {           // sub: [x-y, y, 1, x]
-        uint8_t d = newv();
-        op(MO_SUB, d, x, y);
-        gate(a.C);
-        cell(d); cell(y); cell(K(1)); cell(x);
-        return d;
-    }
-    uint8_t g_mul(uint8_t x, uint8_t y) {           // mul: [0, x, y, x*y]
-        uint8_t m = newv();
-        op(MO_MUL, m, x, y);
-        gate(a.C);
-        cell(K(0)); cell(x); cell(y); cell(m);
-        return m;
-    }
-    void g_is_equal(uint8_t x, uint8_t y) {         // sub + is_zero: 12 cells
-        uint8_t d = g_sub(x, y);
-        uint8_t z = newv();
-        uint8_t inv = newv();
-        (void)inv;
-        op(MO_ISZERO, z, d, 0);
-        gate(a.C);
-        gate(a.C + 4);
-        cell(z); cell(d); cell((uint8_t)(z + 1)); cell(K(1));
-        cell(K(0)); cell(d); cell(z); cell(K(0));
-    }
-    // --- RangeChip::range_check
-    void range_check(uint8_t v, uint32_t bits) {
-        if (bits == 0) return;    // assert_is_const(a, 0): no cells
-        if (bits > 254 + lb) fail(SVDW_ERANGE, "range_check bits too large");
-        const uint32_t n = (bits + lb - 1) / lb, rem = bits % lb;
-        uint8_t lsrc = v;
-        uint32_t llo = 0, lnb = 0;
-        int lastc = EQ_AUTO;                        // the last limb's cell (n > 1)
-        if (n == 1) {
-            look(v);
-        } else {
-            for (uint32_t i = 0; i < n; ++i) {
-                const uint32_t lo = i * lb;
-                uint8_t src = v;
-                uint32_t slo = lo, snb = lb;
-                if (lo >= 256) { src = K(0); slo = 0; snb = 0; }
-                if (i == 0) {
-                    lastc = (int)a.C;
-                    cell(src, slo, snb, EQ_WIT);   // limbs are witnesses
-                } else {
-                    gate(a.C - 1);                  // [s_(i-1), l_i, 2^(i lb), s_i]
-                    lastc = (int)a.C;
-                    cell(src, slo, snb, EQ_WIT);
-                    cell(K(pow2_fr(lo)));
-                    cell(v, 0, (i + 1) * lb, EQ_WIT);   // running sum = v mod 2^((i+1) lb)
-                    if (i + 1 == n && n * lb < 256) copy_of(v, a.C - 1);   // constrain_equal(a, sum)
-                    if (i + 1 == n) eq_of_value(v, a.C - 1);
-                }
-                look(src, slo, snb);
-                lsrc = src; llo = slo; lnb = snb;
-            }
-        }
-        if (rem == 1) {                             // assert_bit: [0, l, l, l]
-            gate(a.C);
-            cell(K(0)); cell(lsrc, llo, lnb, lastc); cell(lsrc, llo, lnb, lastc); cell(lsrc, llo, lnb, lastc);
-        } else if (rem > 1) {                       // mul(last, 2^(lb-rem)), looked up
-            const uint32_t sh = lb - rem;
-            uint8_t m = newv();
-            if (n == 1) op(MO_FDBL, m, v, (uint8_t)sh);
-            else if ((n - 1) * lb >= 256) op(MO_ADDK, m, v, kidx(fr_zero()));   // unreachable in practice
-            else op(MO_LIMBSHL, m, v, (uint8_t)sh, (uint16_t)((n - 1) * lb), (uint16_t)lb);
-            gate(a.C);
-            cell(K(0)); cell(lsrc, llo, lnb, lastc); cell(K(pow2_fr(sh))); cell(m);
-            look(m);
-        }
-    }
-    // --- RangeChip::check_less_than(a, Constant(b), bits)
-    void check_less_than_k(uint8_t x, const BigU& b, uint32_t bits) {
-        Fr pw = pow2_fr(bits), bf = big_to_fr(b);
-        uint8_t t3 = addk(x, pw);                  // a + 2^bits
-        uint8_t t2 = addk(t3, fr_neg(bf));         // a + 2^bits - b
-        gate(a.C);
-        gate(a.C + 3);
-        cell(t2); cell(K(bf)); cell(K(1)); cell(t3); cell(K(fr_neg(pw))); cell(K(1)); cell(x);
-        range_check(t2, bits);
-    }
-    void check_big_less_than_safe(uint8_t x, const BigU& bnd) {
-        uint32_t rb = (big_bits(bnd) + lb - 1) / lb * lb;
-        range_check(x, rb);
-        check_less_than_k(x, bnd, rb);
-    }
-    // RangeChip::div_mod(t, 2^p, nb) [ext halo2-base 0.4.1]: [r, 2^p, q, t], then
-    // check_big_less_than_safe(q, 2^nb / 2^p + 1), check_big_less_than_safe(r, 2^p)
-    uint8_t div_mod_pow2(uint8_t t, uint32_t p, uint32_t nb) {
-        uint8_t q = newv();
-        op(MO_SHR, q, t, 0, (uint16_t)p);
-        uint8_t r = newv();
-        op(MO_LIMBSHL, r, t, 0, 0, (uint16_t)p);
-        gate(a.C);
-        cell(r); cell(K(pow2_fr(p))); cell(q); cell(t);
-        check_big_less_than_safe(q, big_add_u32(big_pow2(nb - p), 1));
-        check_big_less_than_safe(r, big_pow2(p));
-        return q;
-    }
-    // FixedPointChip041::signed_div_scale, parameterised (oracle/pyoracle.py
-    // signed_div_scale; chip source unavailable, parity unpinned): add 2^s,
-    // div_mod by 2^p on nb bits, subtract 2^(s-p). Returns the quotient value.
-    uint8_t signed_div_scale(uint8_t x, uint32_t p, uint32_t s, uint32_t nb) {
-        uint8_t t = g_add_k(x, pow2_fr(s));
-        uint8_t q = div_mod_pow2(t, p, nb);
-        return g_sub_k(q, pow2_fr(s - p));
-    }
-    // FixedPointChip041::qsqrt (ZkVector::norm / dist, src/matrix/mod.rs:124-131,
-    // 156-164), parameterised (the chip's source is unavailable: PARITY UNPINNED;
-    // oracle/pyoracle.py qsqrt): y = floor(sqrt(a 2^P)) for a fixed-point a in
-    // [0, 2^nbits), as load_witness(y) with range_check(y, ny), t = mul(a, 2^P),
-    // d = sub(t, mul(y, y)) and f = sub(mul(y, 2), d), both range-checked on nd
-    // bits: 0 <= t - y^2 <= 2y, i.e. y^2 <= t < (y + 1)^2.
-    uint8_t qsqrt(uint8_t x, uint32_t p, uint32_t nbits) {
-        const uint32_t ny = (nbits + p + 1) / 2 + 1, nd = ny + 1;
-        uint8_t t = newv();
-        op(MO_FDBL, t, x, (uint8_t)p);                   // a 2^P (< 2^254: an integer)
-        uint8_t y = newv();
-        op(MO_ISQRT, y, t, 0);
-        cell(y);                                          // load_witness(y)
-        range_check(y, ny);
-        gate(a.C);
-        cell(K(0)); cell(x); cell(K(pow2_fr(p))); cell(t);   // mul(a, 2^P)
-        uint8_t y2 = g_mul(y, y);
-        uint8_t d = g_sub(t, y2);
-        range_check(d, nd);
-        uint8_t e = newv();
-        op(MO_FDBL, e, y, 1);
-        gate(a.C);
-        cell(K(0)); cell(y); cell(K(2)); cell(e);          // mul(y, 2)
-        uint8_t f = g_sub(e, d);
-        range_check(f, nd);
-        return y;
-    }
-    // check_abs_less_than (src/matrix/mod.rs:425-435)
-    void check_abs_less_than(uint8_t x, const BigU& bnd) {
-        if (big_is_zero(bnd)) fail(SVDW_EINVAL, "check_abs_less_than: bound must be >= 1");
-        BigU nb = big_sub_u32(big_shl1(bnd), 1);
-        uint8_t t = g_add_k(x, big_to_fr(big_sub_u32(bnd, 1)));
-        check_big_less_than_safe(t, nb);
-    }
-};
 
 // ---------------------- stream dependencies, bit bounds, cell-stream memory
 // debug logs (read once: getenv scans the environment)
@@ -351,8 +43,8 @@ static const bool g_stage_log = env_flag("SVDW_STAGE_LOG");
 // once its flag initialisation was ordered: the suite passed, but 512^2 went
 // 0.417 -> 0.444 ms and 1024^2 2.078 -> 2.100 ms, 8-way ranks unchanged --
 // HIP runs those waits and writes as kernels of their own -- so it was removed.)
-static hipEvent_t stream_dep(svdw_ctx* c, hipStream_t from, hipStream_t to) {
-    if (c->call.linear) {                                   // one stream: order is implicit
+hipEvent_t stream_dep(svdw_ctx* c, hipStream_t from, hipStream_t to) {
+    if (c->vmg.linear) {                                   // one stream: order is implicit
         flush_batch(c, from);
         return c->lin_ev;
     }
@@ -371,33 +63,14 @@ static hipEvent_t stream_dep(svdw_ctx* c, hipStream_t from, hipStream_t to) {
     return e;
 }
 // `s` waits for a dependency stream_dep returned (or any other event)
-static void dep_wait(svdw_ctx* c, hipStream_t s, hipEvent_t e) {
-    if (c->call.linear && e == c->lin_ev) return;
+void dep_wait(svdw_ctx* c, hipStream_t s, hipEvent_t e) {
+    if (c->vmg.linear && e == c->lin_ev) return;
     hipck(hipStreamWaitEvent(s, e, 0), "hipStreamWaitEvent");
 }
 // (Round 4 removed "gemm_priority", a high-priority second stream at 512 <=
 // max(N, M) < 1024: +2 % in round 2's tools/ab.py runs, but bench.py at 512^2
 // P=32 measured 0.68 ms with it and 0.41 ms without -- the stream created
 // mid-run shares a hardware queue with the cell stream, GPU_MAX_HW_QUEUES = 4.)
-// Launches go out on c->st: this scope sends those queued inside it to a side
-// stream instead, by exchanging st with that stream's slot (&c->st2, &c->st3;
-// null: no redirection) until it ends, by end() or by unwinding. (st_cell and
-// stream_id still name the streams as created.)
-struct OnStream {
-    svdw_ctx* c;
-    hipStream_t* slot;
-    OnStream(svdw_ctx* cc, hipStream_t* s) : c(cc), slot(s) {
-        if (slot) std::swap(c->st, *slot);
-    }
-    OnStream(const OnStream&) = delete;
-    OnStream& operator=(const OnStream&) = delete;
-    ~OnStream() { end(); }
-    void end() {
-        if (slot) std::swap(c->st, *slot);
-        slot = nullptr;
-    }
-    bool on() const { return slot != nullptr; }
-};
 static bool same_cells(const svdw_mat& a, const svdw_mat& b) {
     if (a.phase != b.phase || a.off != b.off) return false;
     return (a.rows == b.rows && a.cols == b.cols && a.rs == b.rs && a.cs == b.cs) ||
@@ -431,38 +104,13 @@ static void fetch_bits(svdw_ctx* c) {
         reg_bits(c, c->qmat[i], c->qbits[i]);
     }
 }
-static void host_mark(svdw_ctx* c, const char* what) {
+void host_mark(svdw_ctx* c, const char* what) {
     if (!c->opt.host_trace || c->dry) return;
     const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - c->ht0).count();
     fprintf(stderr, "[svdw host] %9.1f us  %s\n", us, what);
 }
 static void own(svdw_ctx* c, uint32_t phase, bool lookup, uint64_t off, uint64_t n) {
     if (sharded(c) && n) c->owned.push_back({phase, lookup ? 1u : 0u, off, n});
-}
-// The bit-length words out[0 .. nred) folded inside the quantize launch
-// (BitFold) when its first nred segments carry block maxima laid out back to
-// back from qs.blockmax[0]; else k_bits_reduce over `seg`, a launch of its own.
-static void bits_words(svdw_ctx* c, QuantSegs& qs, uint32_t nred, const BitSegs& seg, unsigned* out,
-                       bool* folded) {
-    *folded = false;
-    if (c->dry || !qs.nseg || qs.nseg < nred || nred > 3) return;
-    for (uint32_t s = 0; s < nred; ++s)
-        if (qs.blockmax[s] != qs.blockmax[0] + qs.blk0[s] || qs.blk0[s] != seg.begin[s]) return;
-    const uint32_t nblk = qs.blk0[nred];
-    if (!c->qfold.p) {
-        ensure_buf(c, c->qfold, 256);
-        // the counters start at zero, before the quantize launch on st (a
-        // null-stream hipMemset is not ordered against it)
-        hipck(hipMemsetAsync(c->qfold.p, 0, c->qfold.cap, c->st), "hipMemsetAsync");
-    }
-    BitFold& f = qs.fold;
-    f.bm = qs.blockmax[0];
-    f.cnt = (unsigned*)c->qfold.p;
-    f.wout = out;
-    f.nblk = nblk;
-    f.nred = nred;
-    for (uint32_t s = 0; s <= nred; ++s) f.b[s] = qs.blk0[s];
-    *folded = true;
 }
 // Write rate of the stage kernel's store pattern over `cells` cells at buf: a
 // stage of 61 constant cells per element (no loads, no micro-ops), one warm and
@@ -539,9 +187,9 @@ static Fr* place_cells(svdw_ctx* c, uint64_t cells) {
         if (p != best) hipck(hipFree(p), "hipFree");
     return best;
 }
-static void grow(svdw_ctx* c, Fr*& ptr, uint64_t used, uint64_t& cap, uint64_t need) {
+void grow(svdw_ctx* c, Fr*& ptr, uint64_t used, uint64_t& cap, uint64_t need) {
     if (c->dry || need <= cap) return;
-    REQUIRE(!c->call.capturing, "internal: allocation during graph capture");
+    REQUIRE(!c->vmg.capturing, "internal: allocation during graph capture");
     ++c->epoch;
     uint64_t ncap = std::max(need, cap + cap / 2);
     Fr* np = ptr ? nullptr : place_cells(c, ncap);
@@ -560,8 +208,8 @@ static void grow(svdw_ctx* c, Fr*& ptr, uint64_t used, uint64_t& cap, uint64_t n
 // the layout table (svdw_layout) records what each region is: the gadget /
 // function that appends it and its rows (row-parallel regions hold `rows`
 // equal runs of cells).
-static void append(svdw_ctx* c, uint32_t phase, uint64_t n, uint64_t nl, uint64_t* off,
-                   uint64_t* loff, const char* tag, uint64_t rows = 1) {
+void append(svdw_ctx* c, uint32_t phase, uint64_t n, uint64_t nl, uint64_t* off, uint64_t* loff, const char* tag,
+            uint64_t rows) {
     REQUIRE(phase < 2, "phase must be 0 or 1");
     settle(c);
     Stream& s = c->ph[phase];
@@ -594,10 +242,7 @@ static void append(svdw_ctx* c, uint32_t phase, uint64_t n, uint64_t nl, uint64_
 template <class F>
 static auto run_sized(svdw_ctx* c, F&& fn) {
     if (!c->dry) {
-        svdw_ctx plan;
-        plan.P = c->P;
-        plan.LB = c->LB;
-        for (int p = 0; p < 2; ++p) { plan.ph[p].n = c->ph[p].n; plan.ph[p].nl = c->ph[p].nl; }
+        PlanCtx plan(c->P, c->LB, c);
         fn(&plan);
         for (int p = 0; p < 2; ++p) {
             grow(c, c->ph[p].adv, c->ph[p].n, c->ph[p].cap, plan.ph[p].n);
@@ -614,16 +259,26 @@ static constexpr uintptr_t kDryBase = (uintptr_t)1 << 44;
 static const Fr* dry_ptr(uint32_t phase, uint64_t off) {
     return reinterpret_cast<const Fr*>(kDryBase * (phase + 1) + off * sizeof(Fr));
 }
-DView view_of(svdw_ctx* c, const svdw_mat& m) {
+// rows x cols values at ptr with strides rs, cs, as a strided view
+static DView ptr_view(const Fr* ptr, uint32_t rows, uint32_t cols, int64_t rs, int64_t cs) {
     DView v;
     memset(&v, 0, sizeof v);
-    v.ptr = c->dry ? dry_ptr(m.phase, m.off) : cellp(c, m.phase, m.off);
-    v.rs = m.rs;
-    v.cs = m.cs;
-    v.rows = m.rows;
-    v.cols = m.cols;
+    v.ptr = ptr;
+    v.rs = rs;
+    v.cs = cs;
+    v.rows = rows;
+    v.cols = cols;
     v.mode = VIEW_STRIDED;
     return v;
+}
+DView view_of(svdw_ctx* c, const svdw_mat& m) {
+    return ptr_view(c->dry ? dry_ptr(m.phase, m.off) : cellp(c, m.phase, m.off), m.rows, m.cols, m.rs, m.cs);
+}
+// The lowest and highest cell of a strided view, counted from its cell 0 (signed strides, in cells).
+struct Span { int64_t lo, hi; };
+static Span view_span(const DView& v) {
+    const int64_t dr = (int64_t)(v.rows ? v.rows - 1 : 0) * v.rs, dc = (int64_t)(v.cols ? v.cols - 1 : 0) * v.cs;
+    return {std::min<int64_t>(dr, 0) + std::min<int64_t>(dc, 0), std::max<int64_t>(dr, 0) + std::max<int64_t>(dc, 0)};
 }
 // A launch's view of loaded cells whose f64 source is registered for this call
 // (f64reg): the same elements read from the f64 input and quantized in the
@@ -631,13 +286,11 @@ DView view_of(svdw_ctx* c, const svdw_mat& m) {
 // checker's copies of the views (note_gates) stay cell views.
 static DView f64_view(const svdw_ctx* c, const DView& v) {
     if (!c->opt.f64_views || c->call.f64reg.empty() || v.mode != VIEW_STRIDED || !v.ptr || !v.rows || !v.cols) return v;
+    const Span sp = view_span(v);
     for (const auto& r : c->call.f64reg) {
         const Fr* base = c->ph[r.phase].adv + r.off;
         const int64_t o = v.ptr - base;
-        const int64_t er = (int64_t)(v.rows - 1) * v.rs, ec = (int64_t)(v.cols - 1) * v.cs;
-        const int64_t lo = o + std::min<int64_t>(er, 0) + std::min<int64_t>(ec, 0),
-                      hi = o + std::max<int64_t>(er, 0) + std::max<int64_t>(ec, 0);
-        if (lo < 0 || hi >= (int64_t)r.n) continue;
+        if (o + sp.lo < 0 || o + sp.hi >= (int64_t)r.n) continue;
         DView f = v;
         f.ptr = reinterpret_cast<const Fr*>(r.x + o);
         f.mode = VIEW_F64;
@@ -648,20 +301,24 @@ static DView f64_view(const svdw_ctx* c, const DView& v) {
 }
 
 // ------------------------------------------------------- stage launches
+// A stage of nelem elements in rows of `cols` (0: 1): its R rows, and those of this rank.
+struct StageRows { uint64_t cw, R, r0, r1; };
+static StageRows stage_rows(const svdw_ctx* c, uint32_t nelem, uint32_t cols) {
+    StageRows s{cols ? cols : 1u, 0, 0, 0};
+    s.R = nelem / s.cw;
+    shard_rows(c, s.R, &s.r0, &s.r1);
+    return s;
+}
 // Appends the stage's cells for `nelem` elements; returns the advice offset.
 // Launch a stage whose cells were appended at (off, loff) earlier.
 static void stage_launch(svdw_ctx* c, uint32_t phase, PB& pb, uint32_t nelem, uint32_t cols,
                          uint64_t off, uint64_t loff, const char* tag) {
     StageArgs a = pb.a;
     uint32_t eb = 0, ee = nelem;
-    if (sharded(c) && nelem) {
-        const uint64_t cw = cols ? cols : 1, R = nelem / cw;
-        uint64_t r0, r1;
-        shard_rows(c, R, &r0, &r1);
-        if (R > 1) {                                      // single cells: every rank
-            eb = (uint32_t)(r0 * cw);
-            ee = (uint32_t)(r1 * cw);
-        }
+    const StageRows sr = stage_rows(c, nelem, cols);
+    if (sharded(c) && sr.R > 1) {                         // single cells: every rank
+        eb = (uint32_t)(sr.r0 * sr.cw);
+        ee = (uint32_t)(sr.r1 * sr.cw);
     }
     if (g_stage_log) {
         uint32_t nmul = 0;
@@ -711,13 +368,9 @@ static void stage_launch(svdw_ctx* c, uint32_t phase, PB& pb, uint32_t nelem, ui
             for (int k = 0; k < kMaxViews; ++k) {
                 const DView& v = a.view[k];
                 if (!v.ptr || v.mode == VIEW_DIAGK) continue;
-                // the view's cells lie within [lo, hi) of ptr (signed strides, in cells)
-                const int64_t dr = (int64_t)(v.rows ? v.rows - 1 : 0) * v.rs,
-                              dc = (int64_t)(v.cols ? v.cols - 1 : 0) * v.cs;
-                const int64_t lo = std::min<int64_t>(dr, 0) + std::min<int64_t>(dc, 0),
-                              hi = std::max<int64_t>(dr, 0) + std::max<int64_t>(dc, 0) + 1;
+                const Span sp = view_span(v);
                 const char* p = reinterpret_cast<const char*>(v.ptr);
-                if (p + lo * (int64_t)sizeof(Fr) < w1 && p + hi * (int64_t)sizeof(Fr) > w0) return true;
+                if (p + sp.lo * (int64_t)sizeof(Fr) < w1 && p + (sp.hi + 1) * (int64_t)sizeof(Fr) > w0) return true;
             }
             return false;
         };
@@ -725,13 +378,10 @@ static void stage_launch(svdw_ctx* c, uint32_t phase, PB& pb, uint32_t nelem, ui
         for (size_t k = 0; k < b.groups.size(); ++k)
             for (const auto& q : b.groups[k])
                 if (reads(q)) g = k + 1;
-        if (c->call.stage_front && g == 0) {                   // a launch of its own, ahead of the batch
+        if (c->call.stage_front && g == 0)                     // a launch of its own, ahead of the batch
             b.groups.insert(b.groups.begin(), std::vector<svdw_ctx::Pending>{});
-            b.groups[0].push_back({a, std::string("k_stage:") + tag, bytes});
-            b.last = 0;
-            return;
-        }
-        if (g == b.groups.size()) b.groups.emplace_back();
+        else if (g == b.groups.size())
+            b.groups.emplace_back();
         b.groups[g].push_back({a, std::string("k_stage:") + tag, bytes});
         b.last = g;
         return;
@@ -810,17 +460,9 @@ struct BatchScope {
 // shard ownership of a stage's cells: this rank's rows (single cells: the last rank)
 static void stage_own(svdw_ctx* c, uint32_t phase, const PB& pb, uint32_t nelem, uint32_t cols,
                       uint64_t off, uint64_t loff) {
-    if (!sharded(c) || !nelem) return;
-    const uint64_t cw = cols ? cols : 1, R = nelem / cw;
-    uint64_t r0, r1;
-    shard_rows(c, R, &r0, &r1);
-    own(c, phase, false, off + r0 * cw * pb.a.C, (r1 - r0) * cw * pb.a.C);
-    own(c, phase, true, loff + r0 * cw * pb.a.L, (r1 - r0) * cw * pb.a.L);
-}
-static uint64_t f64_key(double x) {
-    uint64_t k;
-    memcpy(&k, &x, sizeof k);
-    return k;
+    const StageRows s = stage_rows(c, nelem, cols);
+    own(c, phase, false, off + s.r0 * s.cw * pb.a.C, (s.r1 - s.r0) * s.cw * pb.a.C);
+    own(c, phase, true, loff + s.r0 * s.cw * pb.a.L, (s.r1 - s.r0) * s.cw * pb.a.L);
 }
 static void note_const(svdw_ctx* c, const Fr& v) {
     std::array<uint32_t, 8> w;
@@ -871,12 +513,16 @@ static void note_gates(svdw_ctx* c, const PB& pb, uint32_t cols = 1, size_t reg 
     RegionChecks& r = reg == ~size_t(0) ? c->wit.layout_chk.back() : c->wit.layout_chk.at(reg);
     r.eq = pb.eq;
     r.eqk.assign(pb.a.K, pb.a.K + pb.a.nk);
-    for (int k = 0; k < kMaxViews; ++k) {             // the loaded values' source cells
+    // the loaded values' source cells: for the equality records (dry placeholders
+    // too), and for the checker (device contexts only: it reads the cells)
+    for (int k = 0; k < kMaxViews; ++k) {
         const DView& v = pb.a.view[k];
         uint32_t ph;
         uint64_t off;
-        if (v.mode == VIEW_STRIDED && view_source(c, v.ptr, &ph, &off))
-            r.esrc[k] = eqsrc_mat(svdw_mat{ph, v.rows, v.cols, off, v.rs, v.cs});
+        r.src[k].phase = -1;
+        if (v.mode != VIEW_STRIDED || !view_source(c, v.ptr, &ph, &off)) continue;
+        r.esrc[k] = eqsrc_mat(svdw_mat{ph, v.rows, v.cols, off, v.rs, v.cs});
+        if (!c->dry) r.src[k] = RegionChecks::Src{(int)ph, off, v.rs, v.cs, v.rows, v.cols};
     }
     if (pb.kconst)
         for (uint32_t q = 0; q < pb.a.C; ++q)
@@ -885,19 +531,6 @@ static void note_gates(svdw_ctx* c, const PB& pb, uint32_t cols = 1, size_t reg 
     r.words = pb.chk;
     r.unit = pb.a.C;
     r.cols = cols ? cols : 1;
-    for (int k = 0; k < kMaxViews; ++k) {
-        const DView& v = pb.a.view[k];
-        RegionChecks::Src& s = r.src[k];
-        s.phase = -1;
-        if (!v.ptr || v.mode != VIEW_STRIDED) continue;
-        for (int p = 0; p < 2; ++p) {
-            const Fr* base = c->ph[p].adv;
-            if (base && v.ptr >= base && v.ptr < base + c->ph[p].n) {
-                s = RegionChecks::Src{p, (uint64_t)(v.ptr - base), v.rs, v.cs, v.rows, v.cols};
-                break;
-            }
-        }
-    }
     // a view word whose source is not in the streams (host-known constants,
     // the gamma powers buffer) is dropped
     std::vector<uint32_t> keep;
@@ -916,7 +549,7 @@ static uint64_t run_stage(svdw_ctx* c, uint32_t phase, PB& pb, uint32_t nelem, u
     stage_launch(c, phase, pb, nelem, cols, off, loff, tag);
     return off;
 }
-static svdw_vec put_cell(svdw_ctx* c, uint32_t phase, const Fr& v, bool constant = false) {
+svdw_vec put_cell(svdw_ctx* c, uint32_t phase, const Fr& v, bool constant) {
     PB pb(c->LB);                                          // load_witness / load_constant
     pb.kconst = constant;
     pb.cell(pb.K(v));
@@ -940,18 +573,15 @@ static svdw_vec put_cell(svdw_ctx* c, uint32_t phase, const Fr& v, bool constant
 // inputs): store only this rank's rows and its column block, the cells its
 // stages (bounds, u.d, the a and b = X^T scans) read; the bit-length maxima
 // still cover the whole matrix (the GEMM's B operand).
-static svdw_mat zkmatrix_new(svdw_ctx* c, uint32_t phase, const double* data, uint32_t rows,
-                             uint32_t cols, bool on_device, unsigned* blockmax = nullptr,
-                             QuantSegs* qs = nullptr, bool own_rows_only = false,
-                             bool own_rows_cols = false) {
+svdw_mat zkmatrix_new(svdw_ctx* c, uint32_t phase, const double* data, uint32_t rows, uint32_t cols, bool on_device,
+                      unsigned* blockmax, QuantSegs* qs, bool own_rows_only, bool own_rows_cols) {
     REQUIRE(rows >= 1 && cols >= 1, "ZkMatrix::new: empty matrix");
     REQUIRE(data || c->dry, "null data");
     uint64_t n = (uint64_t)rows * cols, off;
     append(c, phase, n, 0, &off, nullptr, "load", rows);
-    uint64_t q0 = 0;                                      // first quantized value
+    uint64_t q0 = 0, r0, r1;                              // first quantized value; this rank's rows
+    shard_rows(c, rows, &r0, &r1);
     if (own_rows_only && sharded(c) && on_device && qs) {
-        uint64_t r0, r1;
-        shard_rows(c, rows, &r0, &r1);
         q0 = r0 * cols;
         n = (r1 - r0) * cols;
     }
@@ -970,11 +600,8 @@ static svdw_mat zkmatrix_new(svdw_ctx* c, uint32_t phase, const double* data, ui
             qs->blockmax[k] = blockmax;
             qs->n[k] = n;
             qs->keep[k] = QuantKeep{0, 0, 0, 0, 0};
-            if (own_rows_cols && sharded(c) && rows == cols) {
-                uint64_t r0, r1;
-                shard_rows(c, rows, &r0, &r1);
+            if (own_rows_cols && sharded(c) && rows == cols)
                 qs->keep[k] = QuantKeep{cols, (uint32_t)r0, (uint32_t)r1, (uint32_t)r0, (uint32_t)r1};
-            }
             const uint32_t pb = qs->per_block ? qs->per_block : kQuantPerBlock;
             qs->blk0[k + 1] = qs->blk0[k] + (uint32_t)((n + pb - 1) / pb);
         } else {
@@ -983,11 +610,8 @@ static svdw_mat zkmatrix_new(svdw_ctx* c, uint32_t phase, const double* data, ui
                   "k_quantize");
         }
     }
-    if (sharded(c)) {            // every rank quantizes all of it (operands of the products)
-        uint64_t r0, r1;
-        shard_rows(c, rows, &r0, &r1);
-        own(c, phase, false, off + r0 * cols, (r1 - r0) * cols);
-    }
+    // (every rank quantizes all of it: operands of the products)
+    own(c, phase, false, off + r0 * cols, (r1 - r0) * cols);
     return svdw_mat{phase, rows, cols, off, (int64_t)cols, 1};
 }
 
@@ -1063,12 +687,8 @@ static void check_mat_diff_views(svdw_ctx* c, uint32_t phase, const DView& a, co
 static void check_mat_id(svdw_ctx* c, const svdw_mat& a, const svdw_vec& sid, const BigU& tol,
                          const Fr* sid_val = nullptr) {
     const svdw_vec zero = put_cell(c, a.phase, fr_zero(), true);   // ctx.load_constant(F::ZERO)
-    DView b;
-    memset(&b, 0, sizeof b);
+    DView b = ptr_view(c->dry || sid_val ? nullptr : cellp(c, sid.phase, sid.off), a.rows, a.cols, 0, 0);
     b.mode = sid_val ? VIEW_DIAGK : VIEW_DIAG;
-    b.ptr = c->dry || sid_val ? nullptr : cellp(c, sid.phase, sid.off);
-    b.rows = a.rows;
-    b.cols = a.cols;
     check_mat_diff_views(c, a.phase, view_of(c, a), b, a.rows, a.cols, tol, sid_val, EqCell{},
                          EqCell{(int)zero.phase, zero.off}, EqCell{(int)sid.phase, sid.off});
 }
@@ -1186,11 +806,8 @@ static svdw_mat honest_prover_mat_mul(svdw_ctx* c, uint32_t phase, const svdw_ma
         shard_rows(c, N, &sr0, &sr1);
         own(c, phase, false, off + sr0 * M, (sr1 - sr0) * M);
     }
-    {   // |c_s| <= K * 2^bits_a * 2^bits_b, resolved when the operand bounds are known
-        uint32_t lk = 0;
-        while ((1ull << lk) < a.cols) ++lk;
-        c->wit.prods.push_back({cs, a, b, lk});
-    }
+    // |c_s| <= K * 2^bits_a * 2^bits_b, resolved when the operand bounds are known
+    c->wit.prods.push_back({cs, a, b, clog2(a.cols)});
     if (bits_a == ~0u) bits_a = bits_of(c, a);
     if (bits_b == ~0u) bits_b = bits_of(c, b);
     if (c->dry) return cs;
@@ -1216,13 +833,8 @@ static svdw_mat honest_prover_mat_mul(svdw_ctx* c, uint32_t phase, const svdw_ma
         reg_bits(c, a, bits_a);
         reg_bits(c, b, bits_b);
     }
-    if (sharded(c)) {
-        if (sr1 > sr0)
-            gemm_exec(c, c->st, row_block(a, sr0, sr1), b, cellp(c, phase, off + sr0 * M), bits_a,
-                      bits_b);
-        return cs;
-    }
-    gemm_exec(c, c->st, a, b, cellp(c, phase, off), bits_a, bits_b);
+    if (sr1 > sr0)                                        // (unsharded: every row)
+        gemm_exec(c, c->st, row_block(a, sr0, sr1), b, cellp(c, phase, off + sr0 * M), bits_a, bits_b);
     return cs;
 }
 // Words of the small operand for the row-scan products: |signed a| < 2^(32 na)
@@ -1269,6 +881,12 @@ static int batch_na_host(const svdw_ctx* c, const svdw_mat* ms, int n) {
     if (host) return na;
     return dev ? 0 : 8;
 }
+// A vector of len values as the scans take it: room for its canonical copy (bc)
+// and its scaled table (bt).
+static void ensure_pair(svdw_ctx* c, DBuf& bc, DBuf& bt, uint32_t len) {
+    ensure_buf(c, bc, (size_t)len * sizeof(Fr));
+    ensure_buf(c, bt, tab_len(len) * sizeof(Fr));
+}
 // mont_mul(w, f[s]) = slot s of w's scaled table: w * 2^(32 (s + 1)) for s < 6,
 // w's Montgomery form for s = 6 (kernels.hpp kTabSlots)
 static ScaleTab scale_tab() {
@@ -1290,51 +908,43 @@ static void note_scan(svdw_ctx* c, const svdw_mat& a, const RegionChecks::EqSrc&
     r.esrc[0] = eqsrc_mat(a);
     r.esrc[1] = w;
 }
+// An inner-product row region of a (a row: 3 a.cols + 1 cells, its total last;
+// `total`: the first row's): this rank's rows, a row's cells, the region's first cell.
+struct ScanRows { uint64_t r0, r1, rowc, base; };
+static ScanRows scan_rows(const svdw_ctx* c, const svdw_mat& a, uint64_t total) {
+    ScanRows s{0, a.rows, 3ull * a.cols + 1, total - 3ull * a.cols};
+    if (sharded(c)) shard_rows(c, a.rows, &s.r0, &s.r1);
+    return s;
+}
 static svdw_vec matvec_rows(svdw_ctx* c, uint32_t phase, const svdw_mat& a, const Fr* wc,
                             const Fr* tab, uint32_t tl, int na, const RegionChecks::EqSrc& wsrc) {
     const uint32_t R = a.rows, L = a.cols;
     uint64_t off;
     append(c, phase, (uint64_t)R * (3ull * L + 1), 0, &off, nullptr, "scan", R);
     note_scan(c, a, wsrc);
-    uint64_t r0 = 0, r1 = R;
-    if (sharded(c)) {
-        shard_rows(c, R, &r0, &r1);
-        own(c, phase, false, off + r0 * (3ull * L + 1), (r1 - r0) * (3ull * L + 1));
-    }
+    const ScanRows s = scan_rows(c, a, off + 3ull * L);
+    own(c, phase, false, off + s.r0 * s.rowc, (s.r1 - s.r0) * s.rowc);
     if (!c->dry) {
         ProfScope ps(c, c->st, a.cs == 1 ? "k_matvec_scan:rows" : "k_matvec_scan:cols", 32.0 * (double)R * (4.0 * L + 1) + 64.0 * L, (double)R * L);
-        hipck(launch_matvec_scan(view_of(c, a), (uint32_t)r0, (uint32_t)r1, L, wc, tab, tl,
-                                 cellp(c, phase, off + r0 * (3ull * L + 1)), na,
-                                 c->st), "k_matvec_scan");
+        hipck(launch_matvec_scan(view_of(c, a), (uint32_t)s.r0, (uint32_t)s.r1, L, wc, tab, tl,
+                                 cellp(c, phase, off + s.r0 * s.rowc), na, c->st), "k_matvec_scan");
     }
     return svdw_vec{phase, R, off + 3ull * L, (int64_t)(3ull * L + 1)};
 }
 // canonical copy into bc, scaled table into bt
 static const Fr* vec_prep_view(svdw_ctx* c, const DView& w, uint32_t len, DBuf& bc, DBuf& bt) {
-    ensure_buf(c, bc, (size_t)len * sizeof(Fr));
-    ensure_buf(c, bt, tab_len(len) * sizeof(Fr));
+    ensure_pair(c, bc, bt, len);
     if (!c->dry) {
         ProfScope ps(c, c->st, "k_vec_prep", 32.0 * len * (2 + tab_len(1)), 0);
         hipck(launch_vec_prep(w, len, (Fr*)bc.p, (Fr*)bt.p, scale_tab(), c->st), "k_vec_prep");
     }
     return (const Fr*)bt.p;
 }
-static const Fr* vec_prep(svdw_ctx* c, const svdw_vec& v, DBuf& bc, DBuf& bt) {
-    return vec_prep_view(c, view_of(c, svdw_mat{v.phase, 1, v.len, v.off, 0, v.stride}), v.len, bc, bt);
-}
-// the same from a device vector of len canonical values
-static const Fr* vec_prep_ptr(svdw_ctx* c, const Fr* src, uint32_t len, DBuf& bc, DBuf& bt) {
-    DView w;
-    memset(&w, 0, sizeof w);
-    w.ptr = src;
-    w.rs = 0; w.cs = 1; w.rows = 1; w.cols = len;
-    return vec_prep_view(c, w, len, bc, bt);
-}
 static svdw_vec field_mat_vec_mul(svdw_ctx* c, uint32_t phase, const svdw_mat& a,
                                   const svdw_vec& v) {
     REQUIRE(a.cols == v.len, "field_mat_vec_mul: a[0].len() != v.len()");
     const int na = scan_na(c, a);
-    const Fr* tab = vec_prep(c, v, c->w1c, c->w1t);
+    const Fr* tab = vec_prep_view(c, view_of(c, svdw_mat{v.phase, 1, v.len, v.off, 0, v.stride}), v.len, c->w1c, c->w1t);
     return matvec_rows(c, phase, a, (const Fr*)c->w1c.p, tab, v.len, na, eqsrc_vec(v));
 }
 // ZkMatrix::verify_mul (src/matrix/mod.rs:251-282) for several (a, b, c_s) triples
@@ -1342,19 +952,15 @@ static svdw_vec field_mat_vec_mul(svdw_ctx* c, uint32_t phase, const svdw_mat& a
 // would append them, then the row scans run as three batched launches (all
 // c_s.v scans, all b.v scans, all a.(b.v) scans) so the rows of every call
 // share one wave of blocks.
-struct VMul {
-    svdw_mat a, b, cs;
-};
 // v = (1, g, g^2, ...): canonical (gpc) + scaled table (gtab), on stream s. The
 // powers come from three host-side Montgomery tables (g^a, g^(16 b), g^(256 c)):
 // three products per element on the device instead of a square-and-multiply chain.
-static void gamma_prep(svdw_ctx* c, uint32_t d, const Fr& gamma, hipStream_t s, const PowCells* pc = nullptr) {
+void gamma_prep(svdw_ctx* c, uint32_t d, const Fr& gamma, hipStream_t s, const PowCells* pc) {
     if (c->dry) return;
-    REQUIRE(!c->call.capturing, "internal: gamma inside a captured graph");
+    REQUIRE(!c->vmg.capturing, "internal: gamma inside a captured graph");
     const uint32_t len = std::max(d, 1u);
     REQUIRE((len + 255) / 256 <= (uint32_t)kGammaTab - 32, "verify_mul: vector too long");
-    ensure_buf(c, c->gpc, (size_t)len * sizeof(Fr));
-    ensure_buf(c, c->gtab, tab_len(len) * sizeof(Fr));
+    ensure_pair(c, c->gpc, c->gtab, len);
     GammaTab g;
     memset(&g, 0, sizeof g);
     const Fr one = fr_one_mont(), gm = fr_to_mont(gamma);
@@ -1386,7 +992,7 @@ static void ensure_gamma_vec(svdw_ctx* c, uint32_t d, const Fr& gamma) {
     gamma_prep(c, d, gamma, c->st);
     c->gp_ev = nullptr;
 }
-static void verify_mul_many(svdw_ctx* c, uint32_t phase, const VMul* vm, int n, const Fr& gamma) {
+void verify_mul_many(svdw_ctx* c, uint32_t phase, const VMul* vm, int n, const Fr& gamma) {
     REQUIRE(n >= 1 && n <= kMaxVerifyBatch, "internal: verify_mul batch size");
     c->ext_gamma = gamma;
     struct Plan {
@@ -1442,10 +1048,8 @@ static void verify_mul_many(svdw_ctx* c, uint32_t phase, const VMul* vm, int n, 
         if (sharded(c)) {                                 // this rank's rows of the three scans
             for (const auto& sv : {std::make_pair(cs, p.csv), std::make_pair(b, p.bv),
                                    std::make_pair(a, p.abv)}) {
-                const uint64_t rowc = 3ull * sv.first.cols + 1, base = sv.second.off - 3ull * sv.first.cols;
-                uint64_t r0, r1;
-                shard_rows(c, sv.first.rows, &r0, &r1);
-                own(c, phase, false, base + r0 * rowc, (r1 - r0) * rowc);
+                const ScanRows s = scan_rows(c, sv.first, sv.second.off);
+                own(c, phase, false, s.base + s.r0 * s.rowc, (s.r1 - s.r0) * s.rowc);
             }
         }
         uint8_t x = p.eq.load(0), y = p.eq.load(1);           // is_equal per row (result unused)
@@ -1475,20 +1079,15 @@ static void verify_mul_many(svdw_ctx* c, uint32_t phase, const VMul* vm, int n, 
     auto pows_launch = [&] {
         if (pre) return;
         // (a captured graph must not hold gamma: the powers' launch carries it)
-        for (int i = 0; i < n; ++i) REQUIRE(!c->call.capturing || vm[i].cs.cols <= 1, "internal: gamma inside a captured graph");
+        for (int i = 0; i < n; ++i) REQUIRE(!c->vmg.capturing || vm[i].cs.cols <= 1, "internal: gamma inside a captured graph");
         BatchScope bs(c);                                 // the one cells and gamma powers: one launch
         for (int i = 0; i < n; ++i) {
             Plan& p = pl[i];
             const uint32_t d = vm[i].cs.cols;
             stage_launch(c, phase, p.one, 1, 1, p.one_off, p.one_loff, "load_cell");
             if (d > 1) {
-                DView w;
-                memset(&w, 0, sizeof w);
-                w.ptr = gpc;
-                w.rs = 1; w.cs = 0; w.rows = d; w.cols = 1;
-                p.pows.a.view[0] = w;
-                p.pows.a.view[1] = w;
-                p.pows.a.view[1].ptr = gpc + 1;
+                p.pows.a.view[0] = ptr_view(gpc, d, 1, 1, 0);
+                p.pows.a.view[1] = ptr_view(gpc + 1, d, 1, 1, 0);
                 stage_launch(c, phase, p.pows, d - 1, 1, p.pows_off, p.pows_loff, "verify_mul_gamma_pows");
             }
         }
@@ -1507,15 +1106,13 @@ static void verify_mul_many(svdw_ctx* c, uint32_t phase, const VMul* vm, int n, 
     auto add_job = [&](Scans& S, const svdw_mat& a, const svdw_vec& v, const Fr* wc, const Fr* tab,
                        uint32_t tl) -> ScanJob& {
         REQUIRE(S.sb.njobs < (uint32_t)kMaxScanJobs, "internal: scan batch full");
-        uint64_t r0 = 0, r1 = a.rows;                     // shard: this rank's rows
-        const uint64_t rowc = 3ull * a.cols + 1, base = v.off - 3ull * a.cols;
-        if (sharded(c)) shard_rows(c, a.rows, &r0, &r1);
+        const ScanRows s = scan_rows(c, a, v.off);        // shard: this rank's rows
         S.ms[S.sb.njobs] = a;
         ScanJob& j = S.sb.job[S.sb.njobs++];
-        j = ScanJob{f64_view(c, view_of(c, a)), wc, tab, tl, cellp(c, phase, base + r0 * rowc),
-                    a.cols, (uint32_t)(r1 - r0), 0, (uint32_t)r0, job_spec(c, a)};
-        S.bytes += 32.0 * (r1 - r0) * (4.0 * a.cols + 1) + 64.0 * a.cols;
-        S.ops += (double)(r1 - r0) * a.cols;
+        j = ScanJob{f64_view(c, view_of(c, a)), wc, tab, tl, cellp(c, phase, s.base + s.r0 * s.rowc),
+                    a.cols, (uint32_t)(s.r1 - s.r0), 0, (uint32_t)s.r0, job_spec(c, a)};
+        S.bytes += 32.0 * (s.r1 - s.r0) * (4.0 * a.cols + 1) + 64.0 * a.cols;
+        S.ops += (double)(s.r1 - s.r0) * a.cols;
         return j;
     };
     auto launch = [&](Scans& S, const char* name) {
@@ -1591,8 +1188,7 @@ static void verify_mul_many(svdw_ctx* c, uint32_t phase, const VMul* vm, int n, 
         for (int i = 0; i < n; ++i) {
             if (src[i] != i) { wt[i] = wt[src[i]]; continue; }
             const uint32_t L = vm[i].b.rows;
-            ensure_buf(c, c->wbc[i], (size_t)L * sizeof(Fr));
-            ensure_buf(c, c->wbt[i], tab_len(L) * sizeof(Fr));
+            ensure_pair(c, c->wbc[i], c->wbt[i], L);
             REQUIRE(vp.njobs < (uint32_t)kMaxColJobs, "internal: too many distinct b for k_vec_prep_sum");
             vp.job[vp.njobs++] = VecPrepJob{cb.job[slot[i]].part, colsum_slices(cb.job[slot[i]].R), L,
                                             (Fr*)c->wbc[i].p, (Fr*)c->wbt[i].p, 0};
@@ -1632,8 +1228,8 @@ static void verify_mul_many(svdw_ctx* c, uint32_t phase, const VMul* vm, int n, 
         }
         for (int i = 0; i < n; ++i)
             wt[i] = src[i] != i ? wt[src[i]]
-                                : vec_prep_ptr(c, (const Fr*)c->bvfull[slot[i]].p, vm[i].b.rows,
-                                               c->wbc[i], c->wbt[i]);
+                                : vec_prep_view(c, ptr_view((const Fr*)c->bvfull[slot[i]].p, 1, vm[i].b.rows, 0, 1),
+                                                vm[i].b.rows, c->wbc[i], c->wbt[i]);
         for (int i = 0; i < n; ++i) add_a(as_, i);
         launch(as_, "k_matvec_scan:a");
     } else {
@@ -1643,8 +1239,7 @@ static void verify_mul_many(svdw_ctx* c, uint32_t phase, const VMul* vm, int n, 
             ScanJob& j = add_b(bs_, i);
             if (src[i] != i) continue;
             const uint32_t L = vm[i].b.rows;
-            ensure_buf(c, c->wbc[i], (size_t)L * sizeof(Fr));
-            ensure_buf(c, c->wbt[i], tab_len(L) * sizeof(Fr));
+            ensure_pair(c, c->wbc[i], c->wbt[i], L);
             j.pc = (Fr*)c->wbc[i].p;
             j.ptab = (Fr*)c->wbt[i].p;
             j.plen = L;
@@ -1673,15 +1268,9 @@ static void verify_mul_many(svdw_ctx* c, uint32_t phase, const VMul* vm, int n, 
     launch(cs_, "k_matvec_scan:cs");
     if (pows_late) pows_launch();
 }
-static void verify_mul(svdw_ctx* c, uint32_t phase, const svdw_mat& a, const svdw_mat& b,
-                       const svdw_mat& cs, const Fr& gamma) {
-    VMul v{a, b, cs};
-    verify_mul_many(c, phase, &v, 1, gamma);
-}
 
 // err_calc (src/svd/mod.rs:155-163). Host f64, built with -ffp-contract=off.
-static void err_calc(uint32_t p, uint64_t size, double max_norm, double eps_svd, double eps_u,
-                     double* es, double* eu) {
+void err_calc(uint32_t p, uint64_t size, double max_norm, double eps_svd, double eps_u, double* es, double* eu) {
     volatile double precision = pow(2.0, -1.0 * ((double)p + 1.0));
     double s = (double)size;
     *es = precision * s * (1.0 + max_norm + eps_svd + precision) + s * max_norm * precision +
@@ -1724,12 +1313,9 @@ static void prelaunch_products_f64(svdw_ctx* c, const svdw_mat (&A)[3], const sv
 }
 
 // check_svd_phase0
-static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const svdw_mat& u,
-                                         const svdw_mat& v, const svdw_vec& d, double err_svd,
-                                         double err_u, uint32_t max_bits_d,
-                                         const uint32_t* known_bits = nullptr,
-                                         const unsigned* dev_bits = nullptr,
-                                         bool dev_quantized = false) {
+svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const svdw_mat& u, const svdw_mat& v,
+                                  const svdw_vec& d, double err_svd, double err_u, uint32_t max_bits_d,
+                                  const uint32_t* known_bits, const unsigned* dev_bits, bool dev_quantized) {
     REQUIRE(m.rows == u.rows, "check_svd_phase0: m.num_rows != u.num_rows");
     REQUIRE(m.cols == v.rows, "check_svd_phase0: m.num_col != v.num_rows");
     REQUIRE(u.rows == u.cols, "check_svd_phase0: u not square");
@@ -1738,6 +1324,7 @@ static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const s
     REQUIRE(d.len == r, "check_svd_phase0: d.len != min(N, M)");
     const uint32_t P = c->P;
     const uint32_t max_bits = max_bits_d + P;
+    const svdw_mat ut = transposed(u), vt = transposed(v);
     uint64_t n0[2], nl0[2];                               // stream state at entry (for the replay)
     for (int p = 0; p < 2; ++p) { n0[p] = c->ph[p].n; nl0[p] = c->ph[p].nl; }
     auto prelaunch = [&] {
@@ -1761,16 +1348,13 @@ static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const s
         if (key == c->log_key) {
             log = c->log_val;
         } else {
-            svdw_ctx plan;
-            plan.P = c->P; plan.LB = c->LB;
-            for (int p = 0; p < 2; ++p) { plan.ph[p].n = n0[p]; plan.ph[p].nl = nl0[p]; }
+            PlanCtx plan(c->P, c->LB, c);              // (nothing appended since entry: n0, nl0)
             plan.gemm_log = &log;
             check_svd_phase0(&plan, m, u, v, d, err_svd, err_u, max_bits_d, known_bits);
             REQUIRE(log.size() == 3, "internal: expected three products in check_svd_phase0");
             c->log_key = key;
             c->log_val = log;
         }
-        const svdw_mat ut = transposed(u), vt = transposed(v);
         // loads of m, u, v done: the quantization event when svd_witness recorded
         // one (the cell stream may already hold later stages), else st's position
         // products on the cell stream (prod_cell): already behind the loads there
@@ -1783,21 +1367,13 @@ static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const s
             stream_dep(c, c->st, c->st2);
         }
         const svdw_mat A[3] = {m, u, v}, B[3] = {vt, ut, vt};
-        const uint32_t ba[3] = {known_bits[0], known_bits[1], known_bits[2]};
-        const uint32_t bb[3] = {known_bits[2], known_bits[1], known_bits[2]};
-        (void)ba; (void)bb;
+        // per product: the operands' known bits, their device words (b's: v, u, v)
+        const int ib[3] = {2, 1, 2};
         const unsigned* sl[3] = {dev_bits, dev_bits ? dev_bits + 1 : nullptr,
                                  dev_bits ? dev_bits + 2 : nullptr};
-        const unsigned* sa[3] = {sl[0], sl[1], sl[2]};
-        const unsigned* sb[3] = {sl[2], sl[1], sl[2]};
-        if (from_f64) {
-            prelaunch_products_f64(c, A, B, log, m.phase, dev_bits, pst);   // (c->bits)
-            c->call.prelaunched = true;
-            host_mark(c, "products queued");
-            return;
-        }
+        if (from_f64) prelaunch_products_f64(c, A, B, log, m.phase, dev_bits, pst);   // (c->bits)
         bool vplanes = false;                            // v's planes built (digB) on this rank
-        for (int g = 0; g < 3; ++g) {
+        for (int g = 0; g < 3 && !from_f64; ++g) {
             // shard: rows [r0, r1) of the product only
             uint64_t r0 = 0, r1 = A[g].rows;
             if (sharded(c)) shard_rows(c, A[g].rows, &r0, &r1);
@@ -1810,11 +1386,11 @@ static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const s
             if (r1 <= r0) {
                 // nothing of this product on this rank
             } else if (on_device)
-                gemm_exec(c, c->st2, Ag, B[g], outg, ~0u, ~0u, sa[g], sb[g], dev_quantized,
+                gemm_exec(c, c->st2, Ag, B[g], outg, ~0u, ~0u, sl[g], sl[ib[g]], dev_quantized,
                           g == 0 ? sl[2] : nullptr, !shd && g == 2,
                           shd && g == 1 ? &c->digC : nullptr, shd && g == 2 && vplanes);
             else
-                gemm_exec(c, c->st2, Ag, B[g], outg, ba[g], bb[g]);
+                gemm_exec(c, c->st2, Ag, B[g], outg, known_bits[g], known_bits[ib[g]]);
             if (g == 0 && r1 > r0 && on_device) vplanes = true;
             c->call.pre.push_back({log[g], stream_dep(c, c->st2, nullptr), c->st2});
             c->call.gemm_done.push_back(c->call.pre.back().ev);
@@ -1856,17 +1432,16 @@ static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const s
         const int p1_at = c->opt.p1_at >= 0 ? c->opt.p1_at
                                          : (!sharded(c) ? 1 : (c->opt.shard_world >= 4 ? 0 : 3));
         if (!c->call.early_p1 || p1_at != at || !c->call.prelaunched || c->call.pre.size() != 3) return;
-        const svdw_mat t_u = transposed(u), t_v = transposed(v);
-        const svdw_svd_payload pl{t_u, t_v, svdw_mat{m.phase, N, M, c->call.pre[0].off, (int64_t)M, 1},
+        const svdw_svd_payload pl{ut, vt, svdw_mat{m.phase, N, M, c->call.pre[0].off, (int64_t)M, 1},
                                   svdw_mat{m.phase, N, N, c->call.pre[1].off, (int64_t)N, 1},
                                   svdw_mat{m.phase, M, M, c->call.pre[2].off, (int64_t)M, 1}};
         // the products' bounds (|c_s| < 2^(bits_a + bits_b + lk)) before
         // honest_prover_mat_mul registers them: the c_s scans then size their
         // operand on the device (NaSpec) instead of falling back to full
         // Montgomery products (8-way shard rank: 81 -> 25 us)
-        c->wit.prods.push_back({pl.m_times_vt, m, t_v, clog2(M)});
-        c->wit.prods.push_back({pl.u_times_ut, u, t_u, clog2(N)});
-        c->wit.prods.push_back({pl.v_times_vt, v, t_v, clog2(M)});
+        c->wit.prods.push_back({pl.m_times_vt, m, vt, clog2(M)});
+        c->wit.prods.push_back({pl.u_times_ut, u, ut, clog2(N)});
+        c->wit.prods.push_back({pl.v_times_vt, v, vt, clog2(M)});
         auto f = std::move(c->call.early_p1);
         c->call.early_p1 = nullptr;
         f(pl);
@@ -1888,7 +1463,6 @@ static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const s
     check_mat_entries_bounded(c, v, unit);
     host_mark(c, "bounds(v) queued");
     if (!batched) early_phase1(2);
-    const svdw_mat ut = transposed(u), vt = transposed(v);
     DView udv;
     EqCell udpad;
     // products on the cell stream: u.d (all the diff needs from st2) in a launch
@@ -1951,606 +1525,13 @@ static svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const s
     host_mark(c, "ids queued");
     return svdw_svd_payload{ut, vt, mvt, uut, vvt};
 }
-static void check_svd_phase1(svdw_ctx* c, const svdw_mat& m, const svdw_mat& u, const svdw_mat& v,
-                             const svdw_svd_payload& pl, const Fr& g) {
+void check_svd_phase1(svdw_ctx* c, const svdw_mat& m, const svdw_mat& u, const svdw_mat& v, const svdw_svd_payload& pl,
+                      const Fr& g) {
     const VMul vm[3] = {{m, pl.v_t, pl.m_times_vt}, {u, pl.u_t, pl.u_times_ut},
                         {v, pl.v_t, pl.v_times_vt}};
     verify_mul_many(c, 1, vm, 3, g);
 }
 
-// Exact cell stream sizes of a witness call from a dry replay of it (planner:
-// the call on a fresh planning context), cached by key: no growth copies
-// inside the step. grow_to_plan sizes the current cell set to them.
-template <class F>
-static void plan_sizes(svdw_ctx* c, const std::vector<uint64_t>& key, F&& planner) {
-    if (key == c->plan_key) return;
-    svdw_ctx plan;
-    plan.P = c->P; plan.LB = c->LB;
-    planner(&plan);
-    c->plan_key = key;
-    c->plan_val = {plan.ph[0].n, plan.ph[0].nl, plan.ph[1].n, plan.ph[1].nl};
-}
-static void grow_to_plan(svdw_ctx* c) {
-    for (int p = 0; p < 2; ++p) {
-        grow(c, c->ph[p].adv, 0, c->ph[p].cap, c->plan_val[2 * p]);
-        grow(c, c->ph[p].lk, 0, c->ph[p].lcap, c->plan_val[2 * p + 1]);
-    }
-}
-template <class F>
-static void plan_and_grow(svdw_ctx* c, const std::vector<uint64_t>& key, F&& planner) {
-    plan_sizes(c, key, planner);
-    grow_to_plan(c);
-}
-// The opening of a witness call: empty streams, and the call's state reset to
-// what both witness functions start from (clear(), never a fresh vector: the
-// 256^2 verify_mul_witness is host-bound, an allocation per call would show).
-static void begin_call(svdw_ctx* c, const char* what) {
-    c->ht0 = std::chrono::steady_clock::now();
-    host_mark(c, what);
-    clear_streams(c);
-    c->dep_next = 0;
-    c->call.prelaunched = false;
-    c->call.prod_on_cell = false;
-    c->call.gemm_batched = false;
-    c->call.gemm_done.clear();
-    c->call.wait_before_cs.clear();
-    c->call.pre.clear();
-    c->call.pre_wait_st = nullptr;
-    c->call.pre_wait_ev = nullptr;
-}
-// The end of a witness call, by return or by unwinding: what the call
-// registered for its own launches (its f64 inputs, phase 1's early enqueue,
-// the events the c_s scans wait for) does not outlive it.
-struct CallEnd {
-    svdw_ctx* c;
-    ~CallEnd() {
-        c->call.early_p1 = nullptr;
-        c->call.svd_f64[0] = c->call.svd_f64[1] = c->call.svd_f64[2] = nullptr;
-        c->call.f64src.clear();
-        c->call.f64reg.clear();
-        c->call.wait_before_cs.clear();
-        c->call.stage_front = false;
-    }
-};
-// A witness call's side streams start after everything queued on st (the
-// previous call's work joins st at its end): without this, the next call's
-// gamma tables (st3) and first stages (st2, f64 views need no load) could
-// overwrite buffers the previous call's kernels still read.
-static void after_previous(svdw_ctx* c) {
-    if (c->dry) return;
-    const hipEvent_t e = stream_dep(c, c->st, c->st2);
-    if (c->st3) dep_wait(c, c->st3, e);
-    c->xwait_side = nullptr;                      // (st waited for the caller's stream)
-}
-static svdw_counts svd_witness(svdw_ctx* c, const double* m, const double* u, const double* v,
-                               const double* d, uint32_t N, uint32_t M, bool on_device,
-                               const svdw_svd_config& cfg, const Fr& gamma) {
-    REQUIRE(N >= 1 && M >= 1, "empty matrix");
-    const uint32_t r = std::min(N, M);
-    begin_call(c, "svd_witness start");
-    c->call.in_pipe = false;
-    struct PipeGuard {                     // an exception inside a pipelined call: its
-        svdw_ctx* c;                       // tail is whatever reached st2 / st3 -- join it
-        ~PipeGuard() {
-            if (!c->call.in_pipe) return;
-            const int par = c->pipe_par;
-            (void)hipEventRecord(c->tail_ev[par][0], c->st2);
-            (void)hipEventRecord(c->tail_ev[par][1], c->st3);
-            c->tail_valid[par] = true;
-            c->tail_pending = true;
-            c->tail_last = par;
-            c->pipe_par ^= 1;
-            c->call.in_pipe = false;
-        }
-    } pguard{c};
-    CallEnd call_end{c};
-    if (!c->dry) {
-        // exact sizes from the dry planner: no growth copies inside the step
-        plan_sizes(c, {N, M, cfg.max_bits_d, f64_key(cfg.max_norm), f64_key(cfg.eps_svd), f64_key(cfg.eps_u),
-                       c->opt.rlc_prefix},
-                   [&](svdw_ctx* plan) {
-                       plan->opt.rlc_prefix = c->opt.rlc_prefix;
-                       svd_witness(plan, nullptr, nullptr, nullptr, nullptr, N, M, false, cfg, gamma);
-                   });
-        // Pipelined (svd_witness_pipe): device inputs on the f64 product path
-        // with the products on the cell stream, and two cell sets that fit in
-        // at most 60 % of the device memory (1024^2 P=63: 2 x 9.3 GB; 4096^2
-        // P=63, 2 x 148 GB, runs unpipelined)
-        const double wbytes = 32.0 * (double)(c->plan_val[0] + c->plan_val[1] + c->plan_val[2] + c->plan_val[3]);
-        const bool qualifies = c->opt.pipeline && on_device && c->opt.overlap && crt_product_f64(c, std::max(N, M)) &&
-                               products_on_cell_stream(c);
-        // The other cell set must already hold this witness, or its growth must
-        // fit in the device's free memory now (other contexts, the lane's state
-        // and torch's allocations count) with 10 % of the device to spare for
-        // scratch; else the call runs unpipelined and the set is released.
-        bool fits = qualifies;
-        if (qualifies) {
-            const double need = wbytes - set_bytes(c->alt);
-            if (need > 0) {
-                size_t fr = 0, tot = 0;
-                hipck(hipMemGetInfo(&fr, &tot), "hipMemGetInfo");
-                fits = need + 0.1 * (double)tot <= (double)fr;
-            }
-        }
-        if (qualifies && !fits) release_alt(c);
-        c->call.in_pipe = fits;
-        if (c->call.in_pipe) {
-            // the other cell set (last written by call j - 2): every stream waits
-            // for that call's tail, the last reader of these cells and bit words
-            // (st2's first stages write cells that call's st3 scans read)
-            for (int p = 0; p < 2; ++p) std::swap(c->ph[p], c->alt[p]);
-            std::swap(c->gpc, c->gpc_alt);        // (call j - 1's scans still read the others)
-            std::swap(c->gtab, c->gtab_alt);
-            clear_streams(c);
-            // (tail_ev[.][0] was recorded on st2, [.][1] on st3: a stream does not
-            // wait for its own earlier work)
-            if (c->tail_valid[c->pipe_par])
-                for (hipStream_t t : {c->st, c->st2, c->st3})
-                    for (int k = 0; k < 2; ++k)
-                        if (t != (k ? c->st3 : c->st2))
-                            hipck(hipStreamWaitEvent(t, c->tail_ev[c->pipe_par][k], 0), "hipStreamWaitEvent");
-            if (c->xwait_side) {                  // the caller's stream (svdw_stream_wait)
-                for (hipStream_t t : {c->st2, c->st3})
-                    hipck(hipStreamWaitEvent(t, c->xwait_side, 0), "hipStreamWaitEvent");
-                c->xwait_side = nullptr;
-            }
-        } else {
-            settle(c);
-            after_previous(c);
-        }
-        if (!c->call.in_pipe) {
-            grow_to_plan(c);
-        } else {
-            try {
-                grow_to_plan(c);
-            } catch (const SvdwError& e) {
-                if (e.code != SVDW_ENOMEM) throw;
-                // the other set could not be allocated after all: back to this
-                // set, unpipelined (the waits already queued are harmless)
-                for (int p = 0; p < 2; ++p) std::swap(c->ph[p], c->alt[p]);
-                std::swap(c->gpc, c->gpc_alt);
-                std::swap(c->gtab, c->gtab_alt);
-                c->call.in_pipe = false;
-                release_alt(c);
-                clear_streams(c);
-                settle(c);
-                after_previous(c);
-                grow_to_plan(c);
-            }
-        }
-    }
-    // examples/svd_example.rs:183-184 run rlc.load_rlc_cache((ctx_gate, ctx_rlc), gate, 1)
-    // on the phase-1 pair before check_svd_phase1. As recalled from axiom-eth's
-    // RlcChip (un-vendored; parity unpinned), an empty cache loads gamma as
-    // compute_rlc_fixed_len(ctx_rlc, [one, zero]) with one = ctx_gate.load_constant(1),
-    // zero = ctx_gate.load_zero(): two constant cells at the head of ctx_gate (the
-    // stream here); [E(one), E(zero), W(gamma)] go to ctx_rlc, whose cell 2 is init_rand.
-    c->wit.ext_off = 0;
-    c->rlc.n = 0;
-    if (c->opt.rlc_prefix) {
-        const svdw_vec one = put_cell(c, 1, fr_from_u64(1), true);
-        const svdw_vec zero = put_cell(c, 1, fr_zero(), true);
-        c->wit.ext_off = 2;
-        c->rlc.n = 3;
-        c->rlc.cells[0] = fr_from_u64(1);
-        c->rlc.cells[1] = fr_zero();
-        c->rlc.cells[2] = gamma;
-        c->rlc.src[0] = (uint64_t)one.phase << 62 | one.off;
-        c->rlc.src[1] = (uint64_t)zero.phase << 62 | zero.off;
-    }
-    c->gp_ev = nullptr;
-    if (!c->dry && c->opt.hold_us) {       // every stream of the step waits for st's hold
-        hipck(launch_hold(c->opt.hold_us, c->st), "k_hold");
-        stream_dep(c, c->st, c->st3);
-        stream_dep(c, c->st, c->st2);  // (st2's first stages need no load with f64 views)
-    }
-    if (!c->dry) {
-        // gamma^j depends on gamma only: queue it first, on its own stream, so it
-        // runs beside quantization instead of on the phase-1 chain (pipelined: on
-        // the cell stream, the least loaded one, into this parity's tables)
-        const bool g3 = c->opt.gamma_at == 1 || (c->opt.gamma_at < 0 && sharded(c));
-        hipStream_t gs = c->call.in_pipe && !(g3 && c->st3) ? c->st_cell : c->st3;
-        gamma_prep(c, std::max(N, M), gamma, gs);
-        c->gp_ev = stream_dep(c, gs, nullptr);
-        c->gp_st = gs;
-        host_mark(c, "gamma_prep queued");
-    }
-    unsigned* dbits = nullptr;
-    // m: only this rank's rows are quantized on a row-sharded rank (zkmatrix_new)
-    uint64_t mr0 = 0, mr1 = N;
-    if (sharded(c) && on_device) shard_rows(c, N, &mr0, &mr1);
-    // (host inputs go through launch_quantize, kQuantPerBlock values per block)
-    const uint32_t qpb = on_device ? quant_per_block((mr1 - mr0) * M + (uint64_t)N * N + (uint64_t)M * M + r)
-                                   : kQuantPerBlock;
-    const uint32_t nbm = (uint32_t)(((mr1 - mr0) * M + qpb - 1) / qpb);
-    const uint32_t nbu = (uint32_t)(((uint64_t)N * N + qpb - 1) / qpb);
-    const uint32_t nbv = (uint32_t)(((uint64_t)M * M + qpb - 1) / qpb);
-    if (!c->dry) {
-        // [0, 3): bit-length maxima of m, u, v; from word 64: per-block maxima
-        // (pipelined: a half per parity, call j - 1's row scans still read theirs)
-        const size_t words = (64 + nbm + nbu + nbv + 63) / 64 * 64;
-        ensure_buf(c, c->bits, 2 * words * sizeof(unsigned));
-        dbits = (unsigned*)c->bits.p + (c->call.in_pipe ? c->pipe_par * words : 0);
-    }
-    QuantSegs qs;
-    memset(&qs, 0, sizeof qs);
-    qs.per_block = qpb;
-    QuantSegs* qp = &qs;
-    svdw_mat zm = zkmatrix_new(c, 0, m, N, M, on_device, dbits ? dbits + 64 : nullptr, qp, true);
-    // (u, v: the rank's rows and column block only, when b.g comes from the f64
-    // inputs and so do the products' residue planes: no kernel reads the rest)
-    const bool part = sharded(c) && on_device && c->opt.overlap && crt_product_f64(c, std::max(N, M));
-    svdw_mat zu = zkmatrix_new(c, 0, u, N, N, on_device, dbits ? dbits + 64 + nbm : nullptr, qp, false, part);
-    svdw_mat zv = zkmatrix_new(c, 0, v, M, M, on_device, dbits ? dbits + 64 + nbm + nbu : nullptr, qp, false,
-                               part);
-    svdw_mat zdm = zkmatrix_new(c, 0, d, r, 1, on_device, nullptr, qp);
-    BitSegs seg{};
-    seg.begin[0] = 0;
-    seg.begin[1] = nbm;
-    seg.begin[2] = nbm + nbu;
-    seg.begin[3] = nbm + nbu + nbv;
-    bool folded = false;
-    bits_words(c, qs, 3, seg, dbits, &folded);
-    // (Round 4 measured the quantization beside the product chain instead: the
-    // bit-length words from a read-only k_bits_f64 on st, the cells on st2; it
-    // was 0.7-4 % slower at 1024^2, 512^2 and on 8-way ranks -- the words'
-    // cross-block reduction costs what the cells' stores did -- and was removed.)
-    if (qs.nseg) {
-        ProfScope ps(c, c->st, "k_quantize", 40.0 * ((double)N * M + (double)N * N + (double)M * M + r), 0);
-        hipck(launch_quantize_multi(qs, (int)c->P, c->st), "k_quantize_multi");
-    }
-    svdw_vec zd{0, r, zdm.off, 1};
-    double es, eu;
-    err_calc(c->P, std::max(N, M), cfg.max_norm, cfg.eps_svd, cfg.eps_u, &es, &eu);
-    if (!c->dry) {   // operand bit lengths (GEMM digit counts): read lazily, see fetch_bits
-        if (!folded) hipck(launch_bits_reduce(dbits + 64, seg, 3, dbits, c->st), "k_bits_reduce");
-        flush_batch(c, c->st);
-        hipck(hipEventRecord(c->ev_bits, c->st), "hipEventRecord");
-        c->bits_pending = true;
-        c->qmat[0] = zm; c->qmat[1] = zu; c->qmat[2] = zv;
-        // the same words for the device-side choices (row-scan operand widths)
-        c->wit.dbitw = dbits;
-        c->wit.dwords = {{zm, 0}, {zu, 1}, {zv, 2}};
-        host_mark(c, "quantize + bits queued");
-    }
-    // Phase 1 needs only the products (queued on st2 by check_svd_phase0), the
-    // quantized operands and gamma: run it on st2 behind the GEMMs, concurrently
-    // with the HBM-bound phase-0 checks still on st (its row scans are
-    // VALU-bound), and join the streams afterwards.
-    // Mode 2: on a third stream that starts after quantization; the b.g and
-    // a.(b.g) scans run at once, the c_s.g scans wait for the products; queued
-    // from inside check_svd_phase0 right after its first stage (p1_at).
-    // Mode 1 on a row-sharded rank becomes mode 2: there the products are only a
-    // row block, the st2 chain (products + phase 1) is the critical path and the
-    // operand-only scans fit beside the products (tools/shard_sim.py, 8 ranks:
-    // 0.62 -> 0.54 ms). So does a small witness (max(N, M) < 1024), where the
-    // st2 chain is also the critical path (tools/ab.py: 512^2 P=32 0.559 ->
-    // 0.454 ms, 768^2 P=63 1.328 -> 1.272 ms); from 1024 on it is neutral to
-    // 1 % slower.
-    const bool p1_small = std::max(N, M) < 1024;
-    // (pipelined: st2 carries the diff and ids after the bounds, phase 1 goes to st3)
-    const int p1mode = c->opt.phase1_overlap == 1 && (sharded(c) || p1_small || c->call.in_pipe) ? 2 : c->opt.phase1_overlap;
-    bool p1_queued = false;
-    auto queue_phase1 = [&](const svdw_svd_payload& pl, bool overlap) {
-        const bool p1_overlap = p1mode && overlap;
-        hipStream_t p1s = p1mode == 2 ? c->st3 : c->st2;
-        // phase 1 beside the products (st3, or st2 while the products run on the
-        // cell stream): it waits for the loads, and its c_s scans for the products
-        if (p1_overlap && (p1s == c->st3 || c->call.prod_on_cell)) {
-            dep_wait(c, p1s, c->ev_bits);
-            c->call.wait_before_cs = c->call.gemm_done;
-        }
-        {
-            OnStream on(c, p1_overlap ? (p1s == c->st3 ? &c->st3 : &c->st2) : nullptr);
-            check_svd_phase1(c, zm, zu, zv, pl, gamma);
-        }
-        c->call.wait_before_cs.clear();
-        p1_queued = true;
-        host_mark(c, "phase 1 (early) queued");
-    };
-    if (p1mode == 2 && !c->dry) c->call.early_p1 = [&](const svdw_svd_payload& pl) { queue_phase1(pl, true); };
-    if (on_device && !c->dry) {
-        c->call.svd_f64[0] = m; c->call.svd_f64[1] = u; c->call.svd_f64[2] = v;
-        c->call.f64src = {{zu, u}, {zv, v}};
-        c->call.f64reg = {{zm.phase, zm.off, (uint64_t)N * M, m}, {zu.phase, zu.off, (uint64_t)N * N, u},
-                     {zv.phase, zv.off, (uint64_t)M * M, v}, {zdm.phase, zdm.off, (uint64_t)r, d}};
-    }
-    svdw_svd_payload pl =
-        check_svd_phase0(c, zm, zu, zv, zd, es, eu, cfg.max_bits_d, c->qbits, dbits, true);
-    c->call.early_p1 = nullptr;
-    const bool p1_overlap = p1mode && c->call.prelaunched && !c->dry;
-    hipStream_t p1s = p1mode == 2 ? c->st3 : c->st2;
-    host_mark(c, "phase 0 queued");
-    if (!p1_queued) queue_phase1(pl, p1_overlap);
-    host_mark(c, "phase 1 queued");
-    if (c->call.in_pipe) {
-        // no join into st: the next call's product chain starts on st while this
-        // call's stages (st2) and row scans (st3) finish; they end at tail_ev
-        const int par = c->pipe_par;
-        flush_batch(c, c->st2);
-        flush_batch(c, c->st3);
-        hipck(hipEventRecord(c->tail_ev[par][0], c->st2), "hipEventRecord");
-        hipck(hipEventRecord(c->tail_ev[par][1], c->st3), "hipEventRecord");
-        c->tail_valid[par] = true;
-        c->tail_pending = true;
-        c->tail_last = par;
-        c->pipe_par ^= 1;
-        c->call.in_pipe = false;
-        host_mark(c, "svd_witness end (pipelined)");
-        return svdw_counts{c->ph[0].n, c->ph[1].n, c->ph[0].nl, c->ph[1].nl};
-    }
-    if (p1_overlap) stream_dep(c, p1s, c->st);
-    // st2 also carries the d checks and single cells queued aside (and, with
-    // phase 1 on st3, nothing else joins it): join it too
-    if (c->call.prelaunched && !c->dry && !(p1_overlap && p1s == c->st2)) stream_dep(c, c->st2, c->st);
-    host_mark(c, "svd_witness end");
-    return svdw_counts{c->ph[0].n, c->ph[1].n, c->ph[0].nl, c->ph[1].nl};
-}
-
-// README.md:32-46 as one call: ZkMatrix::new(a), ZkMatrix::new(b), c_s =
-// honest_prover_mat_mul(a, b) into phase 0, verify_mul(a, b, c_s, gamma) into
-// phase 1 -- the modular calls' cells, enqueued without host waits: a and b
-// quantized in one launch, the GEMM's modulus count and the row scans' operand
-// widths decided on the device from the bit-length words, gamma^j prepared
-// first on the side stream.
-// verify_mul_witness's phase 1 opens with verify_mul's one cell and its d - 1
-// gamma-power elements (verify_mul_many's first appends at phase-1 offsets 0
-// and 1): k_gamma_prep writes them when the phase-1 stream holds them
-static bool vm_pow_cells(svdw_ctx* c, uint32_t M, const Fr& gamma, PowCells* pc) {
-    memset(pc, 0, sizeof *pc);
-    if (M <= 1 || c->ph[1].cap < 1 + 4ull * (M - 1)) return false;
-    pc->one = cellp(c, 1, 0);
-    pc->pows = cellp(c, 1, 1);
-    pc->d = M;
-    pc->gamma = gamma;
-    return true;
-}
-static svdw_counts verify_mul_witness(svdw_ctx* c, const double* a, const double* b, uint32_t N,
-                                      uint32_t K, uint32_t M, bool on_device, const Fr& gamma) {
-    REQUIRE(N >= 1 && K >= 1 && M >= 1, "empty matrix");
-    REQUIRE(!sharded(c), "verify_mul_witness: not for row-sharded contexts");
-    begin_call(c, "verify_mul_witness start");
-    CallEnd call_end{c};
-    settle(c);
-    after_previous(c);
-    if (!c->dry)
-        plan_and_grow(c, {0x766d77ull, N, K, M}, [&](svdw_ctx* plan) {
-            verify_mul_witness(plan, nullptr, nullptr, N, K, M, false, gamma);
-        });
-    c->wit.ext_off = 0;
-    c->gp_ev = nullptr;
-    if (!c->dry && c->opt.hold_us) {       // every stream of the step waits for st's hold
-        hipck(launch_hold(c->opt.hold_us, c->st), "k_hold");
-        stream_dep(c, c->st, c->st3);
-        stream_dep(c, c->st, c->st2);
-    }
-    host_mark(c, "plan + gamma_prep queued");
-    unsigned* dbits = nullptr;
-    const uint32_t qpb = on_device ? quant_per_block((uint64_t)N * K + (uint64_t)K * M) : kQuantPerBlock;
-    const uint32_t nba = (uint32_t)(((uint64_t)N * K + qpb - 1) / qpb),
-                   nbb = (uint32_t)(((uint64_t)K * M + qpb - 1) / qpb);
-    c->call.pows_pre.on = false;
-    if (!c->dry) {
-        // phase 1 opens with verify_mul's one cell and its d - 1 gamma-power
-        // elements (verify_mul_many's first appends): k_gamma_prep writes them
-        PowCells pc;
-        // (queued ahead: only if that launch wrote them where they are now)
-        if (c->ph[1].n == 0 && vm_pow_cells(c, M, gamma, &pc) && (!c->call.gp_external || c->call.gp_ext_one == pc.one))
-            c->call.pows_pre = {true, 0, 1, M};
-        if (c->call.gp_external) {                         // queued on st ahead of the captured graph
-            c->gp_gamma = gamma;
-            c->gp_len = std::max(M, 1u);
-        } else {
-            gamma_prep(c, M, gamma, c->st3, pc.one ? &pc : nullptr);
-        }
-        c->gp_ev = stream_dep(c, c->st3, nullptr);
-        c->gp_st = c->st3;
-        ensure_buf(c, c->bits, (64 + nba + nbb) * sizeof(unsigned));
-        dbits = (unsigned*)c->bits.p;
-    }
-    QuantSegs qs;
-    memset(&qs, 0, sizeof qs);
-    qs.per_block = qpb;
-    QuantSegs* qp = on_device ? &qs : nullptr;
-    const svdw_mat za = zkmatrix_new(c, 0, a, N, K, on_device, dbits ? dbits + 64 : nullptr, qp);
-    const svdw_mat zb = zkmatrix_new(c, 0, b, K, M, on_device, dbits ? dbits + 64 + nba : nullptr, qp);
-    BitSegs seg{};
-    seg.begin[0] = 0;
-    seg.begin[1] = nba;
-    seg.begin[2] = nba + nbb;
-    bool folded = false;
-    bits_words(c, qs, 2, seg, dbits, &folded);
-    // (quantization stays on the chain here: beside it on st2, config 2 measured
-    // 0.091-0.096 -> 0.106 ms, host-bound, round 4)
-    if (qs.nseg) {
-        ProfScope ps(c, c->st, "k_quantize", 40.0 * ((double)N * K + (double)K * M), 0);
-        hipck(launch_quantize_multi(qs, (int)c->P, c->st), "k_quantize_multi");
-    }
-    if (!c->dry) {
-        if (!folded) hipck(launch_bits_reduce(dbits + 64, seg, 2, dbits, c->st), "k_bits_reduce");
-        c->wit.dbitw = dbits;
-        c->wit.dwords = {{za, 0}, {zb, 1}};
-    }
-    host_mark(c, "quantize queued");
-    if (on_device && !c->dry)
-        c->call.f64reg = {{za.phase, za.off, (uint64_t)N * K, a}, {zb.phase, zb.off, (uint64_t)K * M, b}};
-    // c_s = a * b (honest_prover_mat_mul's cells), the CRT GEMM sized on the device
-    uint64_t off;
-    append(c, 0, (uint64_t)N * M, 0, &off, nullptr, "product", N);
-    const svdw_mat cs{0, N, M, off, (int64_t)M, 1};
-    const uint32_t lk = clog2(K);
-    c->wit.prods.push_back({cs, za, zb, lk});
-    // device inputs: residue planes of a and b^T straight from the f64 inputs
-    // (one launch), the GEMM and combine on st, and verify_mul on the third
-    // stream from the loads on: its one / gamma-power cells and the b and a
-    // scans run beside the product, only the c_s scans wait for it
-    const bool f64 = on_device && !c->dry && crt_product_f64(c, K) && qs.nseg == 2;
-    hipEvent_t loaded = nullptr;
-    if (f64) {
-        loaded = stream_dep(c, c->st, nullptr);
-        product_f64(c, c->st, a, b, N, K, M, cellp(c, 0, off), dbits);
-    } else if (!c->dry) {
-        gemm_exec(c, c->st, za, zb, cellp(c, 0, off), ~0u, ~0u, dbits, dbits + 1, true);
-    }
-    host_mark(c, "product queued");
-    const VMul vm{za, zb, cs};
-    if (f64) {
-        c->call.wait_before_cs = {stream_dep(c, c->st, nullptr)};
-        dep_wait(c, c->st3, loaded);
-        {
-            OnStream on(c, &c->st3);
-            verify_mul_many(c, 1, &vm, 1, gamma);
-        }
-        c->call.wait_before_cs.clear();
-        stream_dep(c, c->st3, c->st);                     // join
-    } else {
-        verify_mul_many(c, 1, &vm, 1, gamma);
-    }
-    host_mark(c, "verify_mul_witness end");
-    return svdw_counts{c->ph[0].n, c->ph[1].n, c->ph[0].nl, c->ph[1].nl};
-}
-
-// ---------------------------------------- captured verify_mul_witness (graph)
-// A device-input verify_mul_witness enqueues ~20 HIP calls for a GPU step of
-// ~70 us at 256^2 (BASELINE config 2), so the host bounds it. Every call of
-// one key (shape, input pointers, buffer epoch) enqueues the same launches:
-// nothing in it waits for the device, and gamma reaches the device only as
-// k_gamma_prep's tables. So k_gamma_prep goes out eagerly on st (by value),
-// the rest is captured once (on the second call of a key, when every buffer
-// is sized) and replayed with one hipGraphLaunch; the host state the call
-// leaves (layout, checks, counts) is restored from the capture, with gamma
-// patched into the constants that hold it.
-static void vmg_snapshot(svdw_ctx* c, const svdw_counts& k) {
-    c->vmg.rec = c->wit;
-    c->vmg.counts = k;
-}
-static svdw_counts vmg_restore(svdw_ctx* c, const Fr& gamma) {
-    const auto& g = c->vmg;
-    clear_streams(c);
-    c->wit = g.rec;
-    c->wit.patch_gamma(gamma);
-    c->ext_gamma = gamma;
-    c->ph[0].n = g.counts.advice0;
-    c->ph[1].n = g.counts.advice1;
-    c->ph[0].nl = g.counts.lookup0;
-    c->ph[1].nl = g.counts.lookup1;
-    return g.counts;
-}
-// caller: the caller's stream (svdw_verify_mul_witness_on), waited for by the
-// state that runs the call (after the lane switch)
-static svdw_counts verify_mul_witness_api(svdw_ctx* c, const double* a, const double* b, uint32_t N,
-                                          uint32_t K, uint32_t M, bool on_device, const Fr& gamma,
-                                          hipStream_t caller = nullptr, bool has_caller = false) {
-    const bool plain = on_device && !c->dry && !c->opt.prof && !c->opt.hold_us && !sharded(c) && N >= 1 && K >= 1 &&
-                       M >= 1;
-    if (plain && c->lanes > 1 && lane_fits(c)) lane_switch(c);
-    if (has_caller && !c->dry) {
-        const hipEvent_t e = xevent(c, 0);
-        hipck(hipEventRecord(e, caller), "hipEventRecord");
-        hipck(hipStreamWaitEvent(c->st, e, 0), "hipStreamWaitEvent");
-        c->xwait_side = e;                        // (st2 / st3: through st, see after_previous)
-    }
-    const bool usable = c->opt.graph_vm && plain;
-    if (!usable) {
-        vmg_drop(c);
-        c->vmg.seen.clear();
-        return verify_mul_witness(c, a, b, N, K, M, on_device, gamma);
-    }
-    c->ht0 = std::chrono::steady_clock::now();
-    settle(c);                     // (before any linear scope: it waits on tail events)
-    struct Linear {                // vm_linear: every launch of the call on st
-        svdw_ctx* c;
-        hipStream_t s2 = nullptr, s3 = nullptr;
-        bool on = false;
-        explicit Linear(svdw_ctx* cc) : c(cc) {
-            if (!c->opt.vm_linear) return;
-            if (!c->lin_ev) hipck(hipEventCreateWithFlags(&c->lin_ev, hipEventDisableTiming), "hipEventCreate");
-            s2 = c->st2;
-            s3 = c->st3;
-            c->st2 = c->st3 = c->st;
-            c->call.linear = on = true;
-        }
-        ~Linear() {
-            if (!on) return;
-            c->st2 = s2;
-            c->st3 = s3;
-            c->call.linear = false;
-        }
-    } lin{c};
-    struct Flags {                 // set here, ahead of verify_mul_witness, and kept over its eager
-        svdw_ctx* c;               // rerun below: this function's end clears them, not CallEnd
-        ~Flags() {
-            c->call.gp_external = false;
-            c->call.capturing = false;
-            c->gp_ev = nullptr;
-            c->call.pows_pre.on = false;
-        }
-    } flags{c};
-    // gamma's tables (and the one / gamma-power cells when phase 1 holds them)
-    // on st, ahead of everything the call queues. (Round 4 tried them on st3
-    // beside the graph, the graph's scans waiting through an external event
-    // node (hipEventWaitExternal): the runtime aborted in the capture/replay.)
-    settle(c);
-    PowCells pc;
-    const bool pw = vm_pow_cells(c, M, gamma, &pc);
-    gamma_prep(c, M, gamma, c->st, pw ? &pc : nullptr);
-    host_mark(c, "vm: gamma_prep queued");
-    c->call.gp_external = true;
-    c->call.gp_ext_one = pw ? pc.one : nullptr;
-    // (the cell set and gamma tables too: a pipelined svd_witness alternates between two)
-    auto key_now = [&] {
-        return std::vector<uint64_t>{N, K, M, (uint64_t)(uintptr_t)a, (uint64_t)(uintptr_t)b, c->epoch,
-                                     (uint64_t)(uintptr_t)c->ph[0].adv, (uint64_t)(uintptr_t)c->ph[1].adv,
-                                     (uint64_t)(uintptr_t)c->ph[0].lk, (uint64_t)(uintptr_t)c->ph[1].lk,
-                                     (uint64_t)(uintptr_t)c->gpc.p, (uint64_t)(uintptr_t)c->gtab.p};
-    };
-    const std::vector<uint64_t> key = key_now();
-    if (c->vmg.exec && key == c->vmg.key) {
-        const svdw_counts k = vmg_restore(c, gamma);
-        host_mark(c, "vm: host state restored");
-        hipck(hipGraphLaunch(c->vmg.exec, c->st), "hipGraphLaunch");
-        c->xwait_side = nullptr;                      // (its side streams fork from st)
-        host_mark(c, "vm: graph launched");
-        ++c->vmg.replays;
-        return k;
-    }
-    if (key == c->vmg.seen) {
-        vmg_drop(c);
-        hipGraph_t graph = nullptr;
-        hipck(hipStreamBeginCapture(c->st, hipStreamCaptureModeRelaxed), "hipStreamBeginCapture");
-        c->call.capturing = true;
-        svdw_counts k{};
-        try {
-            k = verify_mul_witness(c, a, b, N, K, M, on_device, gamma);
-            stream_dep(c, c->st2, c->st);                  // every forked stream joins st
-            if (c->st3) stream_dep(c, c->st3, c->st);
-        } catch (...) {
-            // nothing captured ran: end the capture and run the call eagerly
-            c->call.capturing = false;
-            graph = nullptr;
-            if (hipStreamEndCapture(c->st, &graph) == hipSuccess && graph) (void)hipGraphDestroy(graph);
-            (void)hipGetLastError();
-            c->vmg.seen.clear();
-            return verify_mul_witness(c, a, b, N, K, M, on_device, gamma);
-        }
-        c->call.capturing = false;
-        hipck(hipStreamEndCapture(c->st, &graph), "hipStreamEndCapture");
-        hipGraphExec_t exec = nullptr;
-        const hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        hipck(e, "hipGraphInstantiate");
-        c->vmg.exec = exec;
-        c->vmg.key = key;
-        vmg_snapshot(c, k);
-        hipck(hipGraphLaunch(exec, c->st), "hipGraphLaunch");
-        ++c->vmg.captures;
-        return k;
-    }
-    vmg_drop(c);
-    const svdw_counts k = verify_mul_witness(c, a, b, N, K, M, on_device, gamma);
-    c->vmg.seen = key_now();
-    return k;
-}
 
 // ================================================================== C ABI
 extern "C" {
@@ -2753,7 +1734,8 @@ int svdw_verify_mul(svdw_ctx* c, uint32_t phase, const svdw_mat* a, const svdw_m
         check_mat(c, *a);
         check_mat(c, *b);
         check_mat(c, *cs);
-        run_sized(c, [&](svdw_ctx* x) { verify_mul(x, phase, *a, *b, *cs, fr_from_words(gamma)); });
+        const VMul v{*a, *b, *cs};
+        run_sized(c, [&](svdw_ctx* x) { verify_mul_many(x, phase, &v, 1, fr_from_words(gamma)); });
     });
 }
 int svdw_err_calc(uint32_t p, uint64_t size, double max_norm, double eps_svd, double eps_u,
@@ -2781,47 +1763,6 @@ int svdw_check_svd_phase1(svdw_ctx* c, const svdw_mat* m, const svdw_mat* u, con
     return guarded([&] {
         REQUIRE(c && m && u && v && pl && gamma, "null argument");
         run_sized(c, [&](svdw_ctx* x) { check_svd_phase1(x, *m, *u, *v, *pl, fr_from_words(gamma)); });
-    });
-}
-int svdw_svd_witness(svdw_ctx* c, const double* m, const double* u, const double* v,
-                     const double* d, uint32_t N, uint32_t M, int on_device,
-                     const svdw_svd_config* cfg, const uint64_t gamma[4], svdw_counts* counts) {
-    return guarded([&] {
-        REQUIRE(c && cfg && gamma, "null argument");
-        REQUIRE(c->dry || (m && u && v && d), "null input matrix");
-        svdw_counts k = svd_witness(c, m, u, v, d, N, M, on_device != 0, *cfg, fr_from_words(gamma));
-        if (counts) *counts = k;
-    });
-}
-int svdw_verify_mul_witness(svdw_ctx* c, const double* a, const double* b, uint32_t N, uint32_t K,
-                            uint32_t M, int on_device, const uint64_t gamma[4], svdw_counts* counts) {
-    return guarded([&] {
-        REQUIRE(c && gamma, "null argument");
-        REQUIRE(c->dry || (a && b), "null input matrix");
-        svdw_counts k = verify_mul_witness_api(c, a, b, N, K, M, on_device != 0, fr_from_words(gamma));
-        if (counts) *counts = k;
-    });
-}
-int svdw_verify_mul_witness_on(svdw_ctx* c, void* stream, const double* a, const double* b, uint32_t N,
-                               uint32_t K, uint32_t M, const uint64_t gamma[4], svdw_counts* counts) {
-    return guarded([&] {
-        REQUIRE(c && gamma, "null argument");
-        REQUIRE(c->dry || (a && b), "null input matrix");
-        svdw_counts k = verify_mul_witness_api(c, a, b, N, K, M, true, fr_from_words(gamma), (hipStream_t)stream,
-                                               true);
-        if (counts) *counts = k;
-    });
-}
-int svdw_plan_svd(uint32_t N, uint32_t M, uint32_t p, uint32_t lb, const svdw_svd_config* cfg,
-                  svdw_counts* counts) {
-    return guarded([&] {
-        REQUIRE(cfg && counts, "null argument");
-        if (p < 1 || p > 63) fail(SVDW_ERANGE, "precision_bits must be in [1, 63]");
-        if (lb < 8 || lb > 63) fail(SVDW_ERANGE, "lookup_bits must be in [8, 63]");
-        svdw_ctx plan;
-        plan.P = p;
-        plan.LB = lb;
-        *counts = svd_witness(&plan, nullptr, nullptr, nullptr, nullptr, N, M, false, *cfg, fr_zero());
     });
 }
 

@@ -1,4 +1,5 @@
-// What the host files share: engine.cpp (the witness engine), context.cpp (the
+// What the host files share: engine.cpp (the witness engine), witness.cpp (the
+// two witness calls on it), context.cpp (the
 // context's lifetime, lanes, options, stream hand-off, marks, profiling),
 // export.cpp (read-out), ingest.cpp (text ingest), gemm.cpp (the exact field
 // product), circuit.cpp (the assigned-witness calls), prover.cpp (the prover
@@ -326,8 +327,9 @@ struct svdw_ctx {
         bool operator==(const Options& o) const { return tied() == o.tied(); }
     } opt;
     // ---- one witness call (svd_witness, verify_mul_witness): meaningful while the
-    // call is being enqueued. Each call sets it from scratch (begin_call, then the
-    // call's own code); CallEnd drops what must not outlive the call.
+    // call is being enqueued. Call::reset returns all of it to its initial value:
+    // at the call's opening (begin_call), at its end by return or by unwinding
+    // (CallEnd) and in svdw_ctx_reset, so the modular calls find a fresh context's.
     struct PreGemm {
         uint64_t off;
         hipEvent_t ev;
@@ -363,13 +365,21 @@ struct svdw_ctx {
             uint64_t one_off = 0, pows_off = 0;
             uint32_t d = 0;
         } pows_pre;
-        // the captured verify_mul_witness (vm_graph): `linear` is set while a
-        // vm_linear call is queued (stream_dep returns lin_ev, never recorded, and
-        // dep_wait skips it)
-        bool linear = false;
-        bool capturing = false;                 // st is capturing: no allocation, no sync
-        bool gp_external = false;               // k_gamma_prep already queued ahead of the graph
-        const Fr* gp_ext_one = nullptr;         // the one cell it wrote (null: none)
+        // The only list of the members: the vectors are emptied in place (a witness
+        // call allocates nothing here once they have grown, begin_call).
+        void reset() {
+            in_pipe = prelaunched = prod_on_cell = gemm_batched = stage_front = false;
+            pre.clear();
+            pre_wait_st = nullptr;
+            pre_wait_ev = nullptr;
+            gemm_done.clear();
+            wait_before_cs.clear();
+            svd_f64[0] = svd_f64[1] = svd_f64[2] = nullptr;
+            f64reg.clear();
+            f64src.clear();
+            early_p1 = nullptr;
+            pows_pre = PowsPre{};
+        }
     } call;
     // ---- the handle: parameters, streams, cells, caches, scratch
     std::chrono::steady_clock::time_point ht0;   // host_trace: when the call started
@@ -513,11 +523,19 @@ struct svdw_ctx {
     // a shape, when every buffer is sized) and replayed by later calls of the
     // same key; gamma enters only through k_gamma_prep, launched eagerly on st
     // ahead of the graph (gp_external), so the graph itself is gamma-free.
-    hipEvent_t lin_ev = nullptr;            // "vm_linear": stream_dep's placeholder (call.linear)
+    hipEvent_t lin_ev = nullptr;            // "vm_linear": stream_dep's placeholder (vmg.linear)
     uint64_t epoch = 0;                     // bumped by every allocation / option change
     struct VmGraph {
         std::vector<uint64_t> key, seen;    // replay key; the last eager call's key
         hipGraphExec_t exec = nullptr;
+        // Set by svdw_verify_mul_witness's wrapper ahead of the witness call it makes
+        // and kept over it (its Linear and Flags scopes write them, nothing else):
+        // `linear` while a vm_linear call is queued (stream_dep returns lin_ev,
+        // never recorded, and dep_wait skips it)
+        bool linear = false;
+        bool capturing = false;             // st is capturing: no allocation, no sync
+        bool gp_external = false;           // k_gamma_prep already queued ahead of the graph
+        const Fr* gp_ext_one = nullptr;     // the one cell it wrote (null: none)
         WitnessRecord rec;                  // the record the captured call left behind (restored on replay)
         svdw_counts counts{};
         uint64_t replays = 0, captures = 0;
@@ -538,6 +556,30 @@ hipEvent_t xevent(svdw_ctx* c, int i);                     // the i-th hand-off 
 // ---- engine.cpp
 void flush_batch(svdw_ctx* c, hipStream_t s, hipStream_t waiter = nullptr, hipEvent_t then_wait = nullptr);
 DView view_of(svdw_ctx* c, const svdw_mat& m);             // the cells of m as a kernel's operand
+// ---- engine.cpp, for the witness calls (witness.cpp): each is described where it is defined
+Fr fr_from_words(const uint64_t w[4]);                     // an entry's four words as a value mod p
+hipEvent_t stream_dep(svdw_ctx* c, hipStream_t from, hipStream_t to);
+void dep_wait(svdw_ctx* c, hipStream_t s, hipEvent_t e);
+void host_mark(svdw_ctx* c, const char* what);
+void grow(svdw_ctx* c, Fr*& ptr, uint64_t used, uint64_t& cap, uint64_t need);
+void append(svdw_ctx* c, uint32_t phase, uint64_t n, uint64_t nl, uint64_t* off, uint64_t* loff, const char* tag,
+            uint64_t rows = 1);
+svdw_vec put_cell(svdw_ctx* c, uint32_t phase, const Fr& v, bool constant = false);
+svdw_mat zkmatrix_new(svdw_ctx* c, uint32_t phase, const double* data, uint32_t rows, uint32_t cols, bool on_device,
+                      unsigned* blockmax = nullptr, QuantSegs* qs = nullptr, bool own_rows_only = false,
+                      bool own_rows_cols = false);
+void gamma_prep(svdw_ctx* c, uint32_t d, const Fr& gamma, hipStream_t s, const PowCells* pc = nullptr);
+struct VMul {                                              // one verify_mul: c_s = a * b
+    svdw_mat a, b, cs;
+};
+void verify_mul_many(svdw_ctx* c, uint32_t phase, const VMul* vm, int n, const Fr& gamma);
+void err_calc(uint32_t p, uint64_t size, double max_norm, double eps_svd, double eps_u, double* es, double* eu);
+svdw_svd_payload check_svd_phase0(svdw_ctx* c, const svdw_mat& m, const svdw_mat& u, const svdw_mat& v,
+                                  const svdw_vec& d, double err_svd, double err_u, uint32_t max_bits_d,
+                                  const uint32_t* known_bits = nullptr, const unsigned* dev_bits = nullptr,
+                                  bool dev_quantized = false);
+void check_svd_phase1(svdw_ctx* c, const svdw_mat& m, const svdw_mat& u, const svdw_mat& v, const svdw_svd_payload& pl,
+                      const Fr& g);
 // ---- gemm.cpp: the exact field product c_s = a * b
 extern const uint32_t kCrtMaxK;                            // largest inner dimension of the integer GEMMs
 // The rules of a witness call's products: the CRT path applies (inner dimension
@@ -588,6 +630,39 @@ inline void check_mat(const svdw_ctx* c, const svdw_mat& m) {
     REQUIRE(lo >= 0 && (uint64_t)hi < c->ph[m.phase].n, "matrix view outside its phase stream");
 }
 inline void check_vec(const svdw_ctx* c, const svdw_vec& v) { check_mat(c, mat_of_vec(v)); }
+// A dry context of precision p and lookup bits lb, for a replay that plans:
+// empty, or starting at the stream counts of `at`.
+struct PlanCtx : svdw_ctx {
+    PlanCtx(uint32_t p, uint32_t lb, const svdw_ctx* at = nullptr) {
+        P = p;
+        LB = lb;
+        for (int i = 0; at && i < 2; ++i) { ph[i].n = at->ph[i].n; ph[i].nl = at->ph[i].nl; }
+    }
+};
+// Launches go out on c->st: this scope sends those queued inside it to a side
+// stream instead, by exchanging st with that stream's slot (&c->st2, &c->st3;
+// null: no redirection) until it ends, by end() or by unwinding. (st_cell and
+// stream_id still name the streams as created.)
+struct OnStream {
+    svdw_ctx* c;
+    hipStream_t* slot;
+    OnStream(svdw_ctx* cc, hipStream_t* s) : c(cc), slot(s) {
+        if (slot) std::swap(c->st, *slot);
+    }
+    OnStream(const OnStream&) = delete;
+    OnStream& operator=(const OnStream&) = delete;
+    ~OnStream() { end(); }
+    void end() {
+        if (slot) std::swap(c->st, *slot);
+        slot = nullptr;
+    }
+    bool on() const { return slot != nullptr; }
+};
+inline uint64_t f64_key(double x) {                        // a double in a replay's cache key
+    uint64_t k;
+    memcpy(&k, &x, sizeof k);
+    return k;
+}
 #pragma GCC visibility pop
 inline bool sharded(const svdw_ctx* c) { return c->opt.shard_world > 1; }
 // rows of a row-parallel stage (R rows) that this rank computes / owns

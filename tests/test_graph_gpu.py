@@ -1,4 +1,4 @@
-"""Captured verify_mul_witness (option "graph", engine.cpp verify_mul_witness_api).
+"""Captured verify_mul_witness (option "graph", witness.cpp verify_mul_witness_api).
 
 The second device-input call of a key is captured into a HIP graph and later
 calls replay it, with k_gamma_prep queued ahead of the graph. Every call's cells,

@@ -561,6 +561,61 @@ def test_pipelined_witnesses_parity(gpu_ctx_factory, N, M, P, world, hold, opts)
     check(*ins[1], counts)
 
 
+def test_call_state_does_not_outlive_the_call(gpu_ctx_factory):
+    """A witness call's state (svdw_ctx::Call: products queued ahead, products on
+    the cell stream, ...) ends with the call: the modular calls after it queue
+    as on a fresh context, with or without a reset in between. The profiler's
+    names carry the stream of every launch (@cell / @s2 / @s3).
+    Before Call::reset (the parent of the change that added this test) cases 1
+    and 2 recorded k_stage:load_cell@s2: a single cell loaded after a
+    device-input svd_witness went to the second stream, unordered against the
+    modular calls on the cell stream that read it."""
+    import halo2_svd041_amd as hs
+    P = 32
+    m, u, d, v = gen_svd_input(8, 6, seed=48)
+    dev = _on_device(m, u, v, d)
+
+    def after_witness():
+        ctx = gpu_ctx_factory(P)
+        ctx.profile(True)
+        hs.svd_witness(ctx, *dev, gamma_for(14))
+        ctx.profile_collect()
+        return ctx
+
+    def names(ctx):
+        return [r["name"] for r in ctx.profile_collect()]
+
+    # 1: after a reset
+    ctx = after_witness()
+    ctx.reset()
+    ctx.load_constant(5)
+    got = names(ctx)
+    print("case 1:", got)
+    assert got == ["k_stage:load_cell@cell"]
+    # 3: modular calls on the same context after a reset, against a fresh context
+    a = np.random.RandomState(8).uniform(-1, 1, (8, 8))
+
+    def modular(c):
+        c.reset()
+        za = hs.ZkMatrix.new(c, a)
+        hs.check_mat_id(c, za, c.load_constant(1 << (2 * P)), 1 << 40)
+
+    modular(ctx)
+    got = names(ctx)
+    print("case 3:", got)
+    assert got and all(n.endswith("@cell") for n in got)
+    fresh = gpu_ctx_factory(P)
+    modular(fresh)
+    np.testing.assert_array_equal(ctx.advice(0), fresh.advice(0))
+    # 2: no reset between
+    ctx = after_witness()
+    seven = ctx.load_witness(7)
+    got = names(ctx)
+    print("case 2:", got)
+    assert got == ["k_stage:load_cell@cell"]
+    assert ctx.cells(0, off=seven.vec.off, n=1).tolist() == [[7, 0, 0, 0]]
+
+
 @pytest.mark.parametrize("N,M,P,row_lim,device,hold", [(1024, 1024, 63, 64, False, 0), (512, 512, 32, 128, False, 0),
                                                        (2048, 1024, 32, 24, False, 0), (1024, 1024, 63, 32, True, 0),
                                                        (2048, 1024, 32, 16, True, 0),
